@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- MPC solves/s of the RTI hot path on MI355X (contract: the task statement / DESIGN.md section 6).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: set-up, W untimed episodes, K timed ones, the result line (and DIR/<name>.npy with --dump-outputs).
+--full adds everything else this file measures: the supplementary workloads (C3, C5, the per-GPU shares of C4 / C5, qp_tol 1e-8, reset-on-fail, C1 latency)
+and the CPU baseline (`--no-extra` / `--no-cpu-baseline` leave either out again).
 
 One "step" = one EPISODE of the whole per-GPU batch: set_initial_guess() from the initial scenario, then 100 closed-loop control steps,
 each control step ONE kernel launch with everything resident in HBM:
@@ -470,6 +474,33 @@ def measure(torch, dist, loop, world, exch, steps, warmup, dev):
                 fail=float((st_acc % 65536).double().sum().item()) / n, cap=float((st_acc // 65536).double().sum().item()) / n)
 
 
+DUMP_LIMIT = 64_000_000      # bytes --dump-outputs may write in all
+DUMP_SEED = 0                # the fixed sample of instances when the whole batch would exceed DUMP_LIMIT
+
+
+def dump_outputs(loop, exch, path):
+    """--dump-outputs: what the timed path handed its caller after the last control step of the last timed episode, one float64 array per output as
+    path/<name>.npy -- X (B, N+1, 5), U (B, N, 2), u0 (B, 2), cost (B,), status (B,), iters (B,), the plant state x (B, 5) and the obstacle states
+    obstacles (B, n_obst, 4).  A batch whose arrays exceed DUMP_LIMIT is written as a fixed, seeded sample of instances (sorted; instance_index.npy names
+    them).  Multi-rank: this rank's slice.  The caller has synchronised the device."""
+    cost = loop.cost
+    if exch is not None:        # with the cost exchange the kernels write each step's costs into the exchange's history instead
+        last = exch.n - 1
+        cost = exch.hist[(last // GATHER_EVERY) % 2, last % GATHER_EVERY]
+    arrays = {"X": loop.X, "U": loop.U, "u0": loop.u0, "cost": cost, "status": loop.status, "iters": loop.iters, "x": loop.x0, "obstacles": loop.obst}
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in arrays.items()}
+    per_instance = sum(a[0].nbytes for a in arrays.values())
+    if per_instance * loop.B > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (per_instance + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(loop.B, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def roofline(loop, N, no, r):
     """FP64 vector ALU is the roof that binds this path (~175 flop per algorithmic byte); HBM is the secondary figure.
     Everything from THIS run: kernel time from HIP events on the launch stream, flops from the measured mean iteration count."""
@@ -752,8 +783,14 @@ def main():
                          "communicator exists and another after its all-gathers) -- with --force-exchange the exact process state of a rank of `--gpus N`")
     ap.add_argument("--allow-exchange-fallback", action="store_true",
                     help="if the C-ABI exchange cannot be set up on every rank, run the torch.distributed exchange instead of exiting non-zero")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the supplementary C3, C5 and C1 measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the supplementary measurements (one GPU, default workload) and the CPU baseline "
+                         "(one GPU); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last control step to DIR/<name>.npy (float64; rank 0's slice; a fixed seeded sample "
+                         "of instances beyond 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the supplementary C3, C5 and C1 measurements")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the multi-rank plumbing (gloo), no kernels")
     ap.add_argument("--record", default=None, help="where the full record (every note and nested detail) goes; default $MPC_BENCH_RECORD or gpurun_out/bench_last.json")
     args = ap.parse_args()
@@ -875,6 +912,8 @@ def main():
         else:
             exch = CostExchange(torch, world, hi - lo, dev, gather_costs, join=loop.join)
     r = measure(torch, dist, loop, world, exch, args.steps, args.warmup, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loop, exch, args.dump_outputs)
     torch_pg = None
     if dist is not None:
         # the launcher's (or --with-torch-pg's) process group still works after the library's communicator has run beside it
@@ -916,7 +955,7 @@ def main():
            "waves_per_simd": loop.m.waves_per_simd(loop.B),
            "roofline": roofline(loop, N, no, r)}
 
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == "c2":
+    if rank == 0 and world == 1 and args.full and not args.no_extra and args.workload == "c2":
         # supplementary: the other BASELINE configurations on this one GPU.  Each is measured twice: on ONE stream (the kernel alone on the chip: `roofline`,
         # `value_one_stream`) and with its sub-batches pipelined on two streams (`value`: what `--workload` of that name reports; mpc_gpu.pipeline)
         def extra(wl, share, steps, what):
@@ -961,7 +1000,7 @@ def main():
                                       "note": "the C2 workload with MPC_STEP_RESET_ON_FAIL | MPC_STEP_ALIAS_BUG (the reference's own protocol on a failed QP); every instance still solved 100 times per episode"}
         del lr
         out["c1"] = c1_latency(mpc_gpu, N, no)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(N, no, x0, goal, obst)
     if rank == 0:
         emit(out)

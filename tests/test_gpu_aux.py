@@ -595,3 +595,46 @@ def test_bench_two_ranks_on_one_gpu_run_the_default_workload(env, tmp_path):
     assert line["value"] > 2e6                                # two ranks share one GPU here: about the one-GPU rate in total
     assert abs(line["ms_per_step"] * 1e-3 * line["value"] - 2048 * 100) < 10.0      # value = global batch x 100 control steps / time of one step
     assert "cpu_baseline" not in line                       # rank 0 of a multi-rank run does not time the host
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_what_the_timed_path_computed(env, tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` (no --full): the headline line only -- no supplementary workloads, no CPU baseline --, `value` and
+    `ms_per_step` of exactly the steps asked for, and DIR/<name>.npy equal, bit for bit, to the same three episodes of the C2 workload driven here through
+    bench.Loop."""
+    import json
+    import subprocess
+    import torch
+    import bench
+    from mpc_gpu.sharding import shard_slice
+    mpc_gpu, _ = env
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    envv = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        envv.pop(k, None)
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out),
+                        "--record", str(tmp_path / "record.json")], env=envv, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "MPC solves/sec (N=20, 3 obstacles)" and line["unit"] == "solves/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 2 and line["warmup"] == 1 and abs(line["ms_per_step"] * 1e-3 * line["value"] - 1024 * 100) < 10.0
+    for k in ("c3", "c5", "c4_share", "c5_share", "value_qp_tol_1e-8", "value_reset_on_fail", "c1_ms_per_solve", "cpu_baseline"):
+        assert k not in line, k
+    N, no = bench.WORKLOADS["c2"][:2]
+    x0, goal, obst, _, (lo, hi), _ = bench.make_workload("c2", 1, 0, shard_slice)
+    dev = torch.device("cuda", 0)
+    with torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        loop = bench.Loop(mpc_gpu, torch, N, no, x0, goal, obst, dev, streams=bench.pick_streams(hi - lo))
+        for _ in range(3):
+            loop.reset()
+            for _ in range(bench.EPISODE):
+                loop.control_step()
+        torch.cuda.current_stream().synchronize()
+        want = dict(X=loop.X, U=loop.U, u0=loop.u0, cost=loop.cost, status=loop.status, iters=loop.iters, x=loop.x0, obstacles=loop.obst)
+        want = {k: v.cpu().numpy().astype(np.float64) for k, v in want.items()}
+        loop.m.close()
+    assert sorted(f[:-4] for f in os.listdir(out)) == sorted(want)
+    for k, w in want.items():
+        a = np.load(out / f"{k}.npy")
+        assert a.dtype == np.float64 and a.shape[0] == 1024 and np.array_equal(a, w), k

@@ -252,6 +252,45 @@ def test_cpu_baseline_of_the_bench_runs_and_reports_its_spread():
     assert steps > 100, r["sample"]           # 16 scenarios at >= 2e3 solves/s for 1 s: more than one episode of 100 control steps
 
 
+def test_bench_dump_outputs_writes_the_last_step_and_samples_large_batches(tmp_path, monkeypatch):
+    """--dump-outputs: the arrays the timed path hands its caller after its last control step, float64, one DIR/<name>.npy each; the costs come from the
+    exchange's history when the kernels wrote them there; a batch beyond DUMP_LIMIT is a fixed seeded sample of instances, the same in every run."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def loop(B, N=20, no=3):
+        g = torch.Generator().manual_seed(B)
+        r = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)
+        class L:
+            pass
+        L.B, L.X, L.U, L.u0, L.cost, L.x0, L.obst = B, r(B, N + 1, 5), r(B, N, 2), r(B, 2), r(B), r(B, 5), r(B, no, 4)
+        L.status, L.iters = torch.arange(B, dtype=torch.int32) % 5, torch.arange(B, dtype=torch.int32) % 13
+        return L
+    lp = loop(64)
+    names = bench.dump_outputs(lp, None, str(tmp_path / "a"))
+    assert names == sorted(["X", "U", "u0", "cost", "status", "iters", "x", "obstacles"])
+    for k, t in dict(X=lp.X, U=lp.U, u0=lp.u0, cost=lp.cost, status=lp.status, iters=lp.iters, x=lp.x0, obstacles=lp.obst).items():
+        a = np.load(tmp_path / "a" / f"{k}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, t.double().numpy()), k
+
+    class Exch:                                      # 75 control steps into the run: the last row written is history 1, row 24
+        n, hist = 75, torch.rand(2, bench.GATHER_EVERY, 64, dtype=torch.float64)
+    bench.dump_outputs(lp, Exch, str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "cost.npy"), Exch.hist[1, 24].numpy())
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100_000)
+    big = loop(1000)
+    bench.dump_outputs(big, None, str(tmp_path / "c"))
+    bench.dump_outputs(big, None, str(tmp_path / "d"))
+    idx = np.load(tmp_path / "c" / "instance_index.npy")
+    files = sorted(os.listdir(tmp_path / "c"))
+    assert sum(np.load(tmp_path / "c" / f).nbytes for f in files) <= 100_000 and 0 < len(idx) < 1000 and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "c" / "X.npy"), big.X.numpy()[idx.astype(int)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "c" / f), np.load(tmp_path / "d" / f)), f
+
+
 def test_bench_dry_run_last_stdout_line_parses(built):
     import json
     for wl in ("c2", "c4"):
