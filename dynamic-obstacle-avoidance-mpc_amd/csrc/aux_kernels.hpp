@@ -205,6 +205,27 @@ __global__ void noise_init_kernel(int count, int n_obst, int scenario, unsigned 
     for (int k = 0; k < draws; k++) (void)g.next_double();
 }
 
+// scenario_kernel for more than 10 obstacles: 8 n_obst > 227 outputs reach past the words the first regeneration can take from the seeded state, so the
+// whole MT19937 state is kept (NoiseGen, private memory) and regenerated in place -- the same draws, the same values
+__global__ void scenario_wide_kernel(int count, int n_obst, int scenario, unsigned seed0, double x_lo, double x_hi, double y_lo, double y_hi,
+                                     double v_max, double edge, double *__restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= count) return;
+    unsigned st[kNoiseStateWords];
+    st[0] = seed0 + (unsigned)s;
+    for (int k = 1; k < 624; k++) st[k] = 1812433253u * (st[k - 1] ^ (st[k - 1] >> 30)) + (unsigned)k;
+    st[624] = 624u; st[625] = 0u; st[626] = 0u; st[627] = 0u;
+    NoiseGen g{st};
+    auto uniform = [&](double lo, double hi) { const double u = g.next_double(); return lo + (hi - lo) * u; };
+    double *o = out + (size_t)s * n_obst * 4;
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 0] = scenario == kScenarioRandom ? uniform(x_lo, x_hi) : (scenario == kScenarioEdge ? edge : 0.0);
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 1] = scenario == kScenarioRandom ? uniform(y_lo, y_hi) : (scenario == kScenarioEdge ? edge : 0.0);
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 2] = uniform(-v_max, v_max);
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 3] = uniform(-v_max, v_max);
+}
+
 // one control step's np.random.normal(size=2) per obstacle, in the reference's order (obstacle 0 first): noise[s][j][0..1]
 __global__ void noise_draw_kernel(int count, int n_obst, unsigned *__restrict__ state, double *__restrict__ noise, const int32_t *__restrict__ ep_flags)
 {

@@ -4,6 +4,7 @@
 #include "aux_kernels.hpp"
 #include "rti_kernel.hpp"
 #include "rti_split_kernel.hpp"
+#include "rti_wide_kernel.hpp"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -85,8 +86,10 @@ namespace {
 
 // Row capacity of the kernel instantiation that runs a problem with n obstacles (NOBST of rti_solve_kernel / rti_split_kernel), and whether
 // the problem leaves some of it unused (then only the mappings that take a run-time obstacle count are dispatched: the stage-split kernel for
-// N <= 31, one instance per wavefront with row-parallel sweeps beyond)
-int row_capacity(int n) { return n <= 3 ? 3 : (n <= 5 ? 5 : 10); }
+// N <= 31, one instance per wavefront with row-parallel sweeps beyond).  20 and 32: the multi-wavefront kernel (rti_wide_kernel.hpp, N <= 31 only)
+int row_capacity(int n) { return n <= 3 ? 3 : (n <= 5 ? 5 : (n <= 10 ? 10 : (n <= 20 ? 20 : 32))); }
+constexpr int kMaxSplitN = 31;   // longest horizon of the two-lanes-per-stage mapping, hence of rti_wide_kernel
+bool wide_rows(int n) { return n > 10; }
 constexpr int kPackBatch = 64;   // host-pointer solves of at most this many instances use the packed transfer (solve_common)
 bool partial_rows(const mpc_handle *h);
 
@@ -181,6 +184,7 @@ int pick_lanes(mpc_handle *h, int batch)
 //   20 < N <= 31 beyond; with more obstacles the 256-register build spills 500 - 1150 bytes per lane and loses.
 int pick_split(mpc_handle *h, int batch)
 {
+    if (wide_rows(h->cfg.n_obst)) return 2;       // rti_wide_kernel: two lanes per stage, whatever the batch
     const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
     const int fit = N <= 20 ? 3 : (N <= 31 ? 2 : 1);
     if (partial_rows(h)) return (h->split_override > 1 && h->split_override <= fit) ? h->split_override : fit;
@@ -193,7 +197,7 @@ int pick_split(mpc_handle *h, int batch)
 
 int pick_waves(mpc_handle *h, int batch)
 {
-    if (partial_rows(h)) return 1;
+    if (partial_rows(h) || wide_rows(h->cfg.n_obst)) return 1;
     if (h->waves_override) return h->waves_override;
     return (h->cfg.n_obst == 3 && batch > 4 * h->simd_count) ? 2 : 1;
 }
@@ -233,6 +237,27 @@ int launch_split(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
     if (p.n_obst != NO) return launch_split_w<NO, LPS, false, true>(h, p, s);      // fewer obstacles than rows: the run-time-count variant
     return pick_waves(h, p.batch) == 2 ? launch_split_w<NO, LPS, true>(h, p, s) : launch_split_w<NO, LPS, false>(h, p, s);
+}
+
+// 11 .. 32 obstacles: one instance per workgroup of WideShape<CAP>::W wavefronts
+template <int CAP, bool MASKED>
+int launch_wide(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
+{
+    static int granted[kMaxDevices] = {};
+    const size_t lds = (size_t)mpc::WideLds<CAP>::total(p.N, p.obst != nullptr) * sizeof(double);
+    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
+    return MPC_OK;
+}
+
+// what rti_wide_kernel cannot run: horizons beyond two lanes per stage, and the mapping overrides that name a layout it does not have
+int check_wide(const mpc_handle *h)
+{
+    if (h->cfg.N > kMaxSplitN) return fail(MPC_ERR_ARG, "more than 10 obstacles need N <= 31 (two lanes per horizon stage)");
+    if (h->split_override != 0 && h->split_override != 2) return fail(MPC_ERR_ARG, "more than 10 obstacles run with two lanes per horizon stage only");
+    if (h->lanes_override != 0 && h->lanes_override != 64) return fail(MPC_ERR_ARG, "more than 10 obstacles run with one instance per workgroup only");
+    if (h->waves_override == 2) return fail(MPC_ERR_ARG, "more than 10 obstacles run with one wavefront per SIMD only");
+    return MPC_OK;
 }
 
 template <int NO, int G, int FACT, bool MASKED = false>
@@ -302,7 +327,12 @@ int launch_one_lane_g(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 
 int dispatch_solve(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
 {
     int rc = MPC_OK;
-    if (q.lps > 1) {
+    if (wide_rows(h->cfg.n_obst)) {
+        rc = check_wide(h); if (rc) return rc;
+        const bool masked = partial_rows(h);
+        if (row_capacity(h->cfg.n_obst) == 20) rc = masked ? launch_wide<20, true>(h, p, s) : launch_wide<20, false>(h, p, s);
+        else rc = masked ? launch_wide<32, true>(h, p, s) : launch_wide<32, false>(h, p, s);
+    } else if (q.lps > 1) {
         switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
         case 32: rc = launch_split<3, 2>(h, p, s); break;
         case 33: rc = launch_split<3, 3>(h, p, s); break;
@@ -453,11 +483,13 @@ int mpc_default_config(mpc_config *c, int N, int n_obst, double Tf)
     return MPC_OK;
 }
 
-int mpc_create(const mpc_config *cfg, int device, int max_batch, mpc_handle **out)
+// mpc_create (1 .. 10 obstacles) and mpc_create2 (1 .. MPC_MAX_OBST; beyond 10 with N <= 31): one validation, one construction
+static int create_handle(const mpc_config *cfg, int device, int max_batch, mpc_handle **out, int max_obst)
 {
     if (!cfg || !out) return fail(MPC_ERR_ARG, "null argument");
     if (cfg->N < 2 || cfg->N > 62) return fail(MPC_ERR_ARG, "N must be in [2, 62] (one horizon stage per lane, N + 1 < 64)");
-    if (cfg->n_obst < 1 || cfg->n_obst > 10) return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
+    if (cfg->n_obst < 1 || cfg->n_obst > max_obst) return fail(MPC_ERR_ARG, max_obst == 10 ? "n_obst must be in [1, 10]" : "n_obst must be in [1, 32]");
+    if (wide_rows(cfg->n_obst) && cfg->N > kMaxSplitN) return fail(MPC_ERR_ARG, "more than 10 obstacles need N <= 31 (two lanes per horizon stage)");
     if (max_batch < 1) return fail(MPC_ERR_ARG, "max_batch must be >= 1");
     if (!(cfg->Tf > 0) || !(cfg->qp_tol > 0) || cfg->qp_iter_max < 1) return fail(MPC_ERR_ARG, "Tf, qp_tol, qp_iter_max must be positive");
     if (cfg->qp_fail_policy != 0 && cfg->qp_fail_policy != 1) return fail(MPC_ERR_ARG, "qp_fail_policy must be 0 (divergence tests) or 1 (truncate at qp_iter_max)");
@@ -478,6 +510,10 @@ int mpc_create(const mpc_config *cfg, int device, int max_batch, mpc_handle **ou
     *out = h;
     return MPC_OK;
 }
+
+int mpc_create(const mpc_config *cfg, int device, int max_batch, mpc_handle **out) { return create_handle(cfg, device, max_batch, out, 10); }
+
+int mpc_create2(const mpc_config *cfg, int device, int max_batch, mpc_handle **out) { return create_handle(cfg, device, max_batch, out, MPC_MAX_OBST); }
 
 int mpc_destroy(mpc_handle *h)
 {
@@ -626,8 +662,12 @@ int mpc_generate_scenarios_dev(mpc_handle *h, int count, int scenario, unsigned 
     if (count == 0) return MPC_OK;
     if (!box || !d_obst) return fail(MPC_ERR_ARG, "null pointer");
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mpc::scenario_kernel, dim3((count + 63) / 64), dim3(64), 0, pick(h, stream), count, h->cfg.n_obst, scenario, seed0,
-                       box[0], box[1], box[2], box[3], box[4], box[5], d_obst);
+    if (wide_rows(h->cfg.n_obst))      // (more draws than the first regeneration of the generator's state covers from the seeded words)
+        hipLaunchKernelGGL(mpc::scenario_wide_kernel, dim3((count + 63) / 64), dim3(64), 0, pick(h, stream), count, h->cfg.n_obst, scenario, seed0,
+                           box[0], box[1], box[2], box[3], box[4], box[5], d_obst);
+    else
+        hipLaunchKernelGGL(mpc::scenario_kernel, dim3((count + 63) / 64), dim3(64), 0, pick(h, stream), count, h->cfg.n_obst, scenario, seed0,
+                           box[0], box[1], box[2], box[3], box[4], box[5], d_obst);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -1151,7 +1191,11 @@ int mpc_get_kernel_name(mpc_handle *h, int batch, int lookahead, char *buf, int 
     const SolvePlan q = plan_solve(h, batch, lookahead != 0);
     const int cap = row_capacity(h->cfg.n_obst);
     const char *masked = partial_rows(h) ? "true" : "false";      // (all template arguments, as rocprofv3 prints the instantiation)
-    if (q.lps > 1) {
+    if (wide_rows(h->cfg.n_obst)) {
+        const int rc = check_wide(h); if (rc) return rc;
+        snprintf(buf, (size_t)len, "rti_wide_kernel<%d, 2, %s>", cap, masked);
+    }
+    else if (q.lps > 1) {
         const bool w2 = q.waves == 2 && !partial_rows(h);
         snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, %s>", cap, q.lps, w2 ? "true" : "false", masked, use_block2(h, w2, partial_rows(h)) ? "true" : "false");
     }

@@ -11,7 +11,8 @@ from .world import Obstacle, generate_random_moving_obstacles, obstacle_states
 from .acados_shim import AcadosOcpSolverShim, AcadosSimSolverShim
 from .closed_loop import RobotOcpProblem
 from .episodes import run_episodes, visualisation_inputs, write_experiment
+from .experiments import run_grid
 
 __all__ = ["MpcConfig", "MpcError", "build", "default_config", "BatchedMpc", "solve", "get_solver", "Obstacle",
            "generate_random_moving_obstacles", "obstacle_states", "AcadosOcpSolverShim", "AcadosSimSolverShim",
-           "RobotOcpProblem", "run_episodes", "visualisation_inputs", "write_experiment"]
+           "RobotOcpProblem", "run_episodes", "visualisation_inputs", "write_experiment", "run_grid"]

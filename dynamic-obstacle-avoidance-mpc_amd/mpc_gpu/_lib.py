@@ -51,6 +51,7 @@ SYMBOLS = {
     "mpc_device_count": (C.c_int, []),
     "mpc_default_config": (C.c_int, [_cfgp, C.c_int, C.c_int, _d]),
     "mpc_create": (C.c_int, [_cfgp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "mpc_create2": (C.c_int, [_cfgp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mpc_destroy": (C.c_int, [_vp]),
     "mpc_iterate_ptrs": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mpc_set_warmstart": (C.c_int, [_vp, C.c_int, _vp, _vp]),

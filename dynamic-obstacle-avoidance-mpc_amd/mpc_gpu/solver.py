@@ -44,7 +44,7 @@ class BatchedMpc:
         self.max_batch = int(max_batch)
         self.device = int(device)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().mpc_create(C.byref(self.cfg), self.device, self.max_batch, C.byref(self._h)))
+        _lib.check(_lib.lib().mpc_create2(C.byref(self.cfg), self.device, self.max_batch, C.byref(self._h)))
         if BatchedMpc.default_lanes_per_stage:
             _lib.check(_lib.lib().mpc_set_lanes_per_stage(self._h, int(BatchedMpc.default_lanes_per_stage)))
         if BatchedMpc.default_waves_per_simd:

@@ -47,10 +47,13 @@ extern "C" {
  * regenerates and recompiles its C interface per problem.) */
 #define MPC_ABI_VERSION 7
 
+/* largest obstacle count a handle takes (mpc_create2; mpc_create keeps 1..10) */
+#define MPC_MAX_OBST 32
+
 /* Problem definition.  Defaults (mpc_default_config) are the reference's constants. */
 typedef struct mpc_config {
     int32_t N;              /* N_SOLV                     src/models/world_specification.py:44   */
-    int32_t n_obst;         /* N_OBST, 1..10              world_specification.py:25              */
+    int32_t n_obst;         /* N_OBST, 1..10 (mpc_create2: 1..32, beyond 10 with N <= 31)  world_specification.py:25 */
     double Tf;              /* TF                         world_specification.py:43              */
     double W[6];            /* diag W, y=[x,y,v,w,ua,ual] robot_ocp_problem.py:24-26,78-80       */
     double We[4];           /* diag W_e, y_e=[x,y,v,w]    robot_ocp_problem.py:27,83             */
@@ -114,6 +117,9 @@ int mpc_default_config(mpc_config *cfg, int N, int n_obst, double Tf);
 /* Replaces AcadosOcpSolver(...) / AcadosSimSolver(...) construction, robot_ocp_problem.py:135-136.
  * Allocates device buffers for up to max_batch instances on `device`; warm start is zero-initialised. */
 int mpc_create(const mpc_config *cfg, int device, int max_batch, mpc_handle **out);
+/* mpc_create for up to MPC_MAX_OBST obstacles: the same for n_obst 1..10; 11..32 need N <= 31 and run on the multi-wavefront solve kernel
+ * (rti_wide_kernel: one instance per workgroup of 2 or 4 wavefronts).  MPC_ERR_ARG for n_obst outside [1, 32] or N > 31 with more than 10. */
+int mpc_create2(const mpc_config *cfg, int device, int max_batch, mpc_handle **out);
 int mpc_destroy(mpc_handle *h);
 
 /* Device pointers of the handle-owned iterate (X[max_batch][N+1][5], U[max_batch][N][2]) and the handle's stream */
@@ -288,7 +294,7 @@ int mpc_set_instance_scheduling(mpc_handle *h, int on);
 int mpc_get_instance_order(mpc_handle *h, int batch, int32_t *order);
 /* name of the solve kernel instantiation a batch of this size runs (as rocprofv3 prints it, without the namespace), for measurement
  * records: "rti_split_kernel<row capacity, lanes per stage, two wavefronts per SIMD, masked, block-2 recursions>" or "rti_solve_kernel<row capacity, lanes per
- * instance, sweeps, masked>" (row capacity: 3, 5 or 10 obstacle row pairs per stage, the smallest that holds n_obst; masked: n_obst is below it;
+ * instance, sweeps, masked>" or, beyond 10 obstacles, "rti_wide_kernel<row capacity, lanes per stage, masked>" (row capacity: 3, 5, 10, 20 or 32 obstacle row pairs per stage, the smallest that holds n_obst; masked: n_obst is below it;
  * sweeps: 0 systolic, 1 matrix cores, 2 row-parallel on dense LDS blocks, 3 row-parallel on compact LDS blocks).  lookahead: whether the
  * obstacle look-ahead runs inside the kernel (mpc_closed_loop_step_dev) -- it enters the LDS budget that selects the block layout. */
 int mpc_get_kernel_name(mpc_handle *h, int batch, int lookahead, char *buf, int len);
