@@ -411,7 +411,9 @@ __global__ __launch_bounds__(64) void adjoint_check_kernel(KParams p, const doub
     if (own && has_u) ru[(size_t)inst * N + i] = r;
 }
 
-// Dense dump of the linearisation of the iterate (tests only): same device functions the solve kernel uses.
+// Dense dump of the linearisation of the iterate (tests only): same device functions the solve kernel uses.  REF: the gradient against the per-stage
+// reference (KParams::yref) instead of the goal, formed as the REF solve kernels form it
+template <bool REF = false>
 __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict__ Xin, const double *__restrict__ Uin,
                                  double *__restrict__ A, double *__restrict__ B, double *__restrict__ b, double *__restrict__ q,
                                  double *__restrict__ hval, double *__restrict__ dh)
@@ -439,8 +441,20 @@ __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict
         Ao[2 * 5 + 4] = p.dt;
         Bo[0] = be[0]; Bo[1] = be[1]; Bo[2] = be[2]; Bo[3] = be[3];
         Bo[2 * 2 + 1] = p.h2; Bo[3 * 2 + 0] = p.dt; Bo[4 * 2 + 1] = p.dt;
+        if constexpr (REF) {
+            double r[6];
+            load_ref(p, inst, i, true, r);
+            qo[0] = p.Wg[4] * (ui[0] - r[4]); qo[1] = p.Wg[5] * (ui[1] - r[5]);
+            qo[2] = p.Wg[0] * (xi[0] - r[0]); qo[3] = p.Wg[1] * (xi[1] - r[1]); qo[4] = 0.0; qo[5] = p.Wg[2] * (xi[3] - r[2]); qo[6] = p.Wg[3] * (xi[4] - r[3]);
+        } else {
         qo[0] = p.Wg[4] * ui[0]; qo[1] = p.Wg[5] * ui[1];
         qo[2] = p.Wg[0] * (xi[0] - gx); qo[3] = p.Wg[1] * (xi[1] - gy); qo[4] = 0.0; qo[5] = p.Wg[2] * xi[3]; qo[6] = p.Wg[3] * xi[4];
+        }
+    } else if constexpr (REF) {
+        double r[6];
+        load_ref(p, inst, i, false, r);
+        qo[0] = qo[1] = 0.0;
+        qo[2] = p.Weg[0] * (xi[0] - r[0]); qo[3] = p.Weg[1] * (xi[1] - r[1]); qo[4] = 0.0; qo[5] = p.Weg[2] * (xi[3] - r[2]); qo[6] = p.Weg[3] * (xi[4] - r[3]);
     } else {
         qo[0] = qo[1] = 0.0;
         qo[2] = p.Weg[0] * (xi[0] - gx); qo[3] = p.Weg[1] * (xi[1] - gy); qo[4] = 0.0; qo[5] = p.Weg[2] * xi[3]; qo[6] = p.Weg[3] * xi[4];

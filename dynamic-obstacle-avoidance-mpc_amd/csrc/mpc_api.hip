@@ -80,6 +80,12 @@ struct mpc_handle {
     int comm_rank, comm_world;
     double *d_gather_in, *d_gather_out;   // staging of the host-pointer all-gather
     size_t gather_cap;                // ... and its capacity in doubles of d_gather_in
+    const double *d_yref;             // per-stage reference in effect (mpc_set_reference[_dev]): d_yref_own or a caller's device array; null = the goal's
+    int32_t *d_ref_off;               // ... its row offsets (d_ref_off_own, a caller's device array, or null = 0)
+    int ref_T, ref_batch;             // ... rows per instance, and the instances it covers (a solve of more is refused)
+    double *d_yref_own;               // handle-owned copies of a host reference (mpc_set_reference)
+    int32_t *d_ref_off_own;
+    size_t yref_own_cap;              // ... capacity of d_yref_own in doubles
 };
 
 namespace {
@@ -219,34 +225,34 @@ int grant_lds(K kernel, int (&granted)[kMaxDevices], int device, size_t lds)
 // Block-2 (partially condensed) stage recursions: the stage-split mapping on dense blocks, even horizons, all rows of the kernel's capacity in use
 bool use_block2(const mpc_handle *h, bool w2, bool masked) { return h->block2 && !w2 && !masked && (h->cfg.N % 2 == 0) && h->cfg.N >= 4; }
 
-template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false>
+template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false, bool REF = false>
 int launch_split_w(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
-    if constexpr (!BLK2 && !W2 && !MASKED) {
+    if constexpr (!BLK2 && !W2 && !MASKED && !REF) {
         if (use_block2(h, W2, MASKED)) return launch_split_w<NO, LPS, W2, MASKED, true>(h, p, s);
     }
     static int granted[kMaxDevices] = {};
     const size_t lds = (size_t)mpc::SplitLds<LPS, NO, W2, BLK2>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2>), dim3(p.batch), dim3(64), lds, s, p);
+    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF>), dim3(p.batch), dim3(64), lds, s, p);
     return MPC_OK;
 }
 
-template <int NO, int LPS>
+template <int NO, int LPS, bool REF = false>
 int launch_split(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
-    if (p.n_obst != NO) return launch_split_w<NO, LPS, false, true>(h, p, s);      // fewer obstacles than rows: the run-time-count variant
-    return pick_waves(h, p.batch) == 2 ? launch_split_w<NO, LPS, true>(h, p, s) : launch_split_w<NO, LPS, false>(h, p, s);
+    if (p.n_obst != NO) return launch_split_w<NO, LPS, false, true, false, REF>(h, p, s);      // fewer obstacles than rows: the run-time-count variant
+    return pick_waves(h, p.batch) == 2 ? launch_split_w<NO, LPS, true, false, false, REF>(h, p, s) : launch_split_w<NO, LPS, false, false, false, REF>(h, p, s);
 }
 
 // 11 .. 32 obstacles: one instance per workgroup of WideShape<CAP>::W wavefronts
-template <int CAP, bool MASKED>
+template <int CAP, bool MASKED, bool REF = false>
 int launch_wide(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
     static int granted[kMaxDevices] = {};
     const size_t lds = (size_t)mpc::WideLds<CAP>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
+    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED, REF>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED, REF>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
     return MPC_OK;
 }
 
@@ -260,12 +266,12 @@ int check_wide(const mpc_handle *h)
     return MPC_OK;
 }
 
-template <int NO, int G, int FACT, bool MASKED = false>
+template <int NO, int G, int FACT, bool MASKED = false, bool REF = false>
 int launch_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 grid, size_t lds)
 {
     static int granted[kMaxDevices] = {};
-    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED>), grid, dim3(64), lds, s, p);
+    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF>), grid, dim3(64), lds, s, p);
     return MPC_OK;
 }
 
@@ -276,8 +282,38 @@ struct SolvePlan {
     size_t lds;
 };
 
+// Per-stage reference (mpc_set_reference): the REF instantiations exist for the stage-split kernel (every horizon up to 31, at every batch size --
+// where the goal path would pack 3 or 4 instances into a wavefront the reference path stays on the split mapping), the multi-wavefront kernel,
+// and one instance per wavefront on compact stage blocks (N > 31, or one lane per stage asked for).  The evidence mappings have none.
+bool ref_active(const mpc_handle *h) { return h->d_yref != nullptr; }
+
+int check_ref_mapping(const mpc_handle *h)
+{
+    if (h->use_mfma) return fail(MPC_ERR_ARG, "a per-stage reference does not run with the matrix-core factorisation (mpc_set_matrix_cores)");
+    if (!h->row_parallel) return fail(MPC_ERR_ARG, "a per-stage reference does not run with the systolic sweeps (mpc_set_row_parallel(0))");
+    if (h->block2) return fail(MPC_ERR_ARG, "a per-stage reference does not run with the block-2 recursions (mpc_set_block_riccati)");
+    if (h->lanes_override != 0 && h->lanes_override != 64) return fail(MPC_ERR_ARG, "a per-stage reference runs with one instance per wavefront only (mpc_set_lanes_per_instance 0 or 64)");
+    return MPC_OK;
+}
+
+SolvePlan plan_solve_ref(mpc_handle *h, int batch)
+{
+    SolvePlan q = {1, 1, 64, 3, 0};
+    const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
+    const int fit = N <= 20 ? 3 : (N <= 31 ? 2 : 1);
+    q.lps = pick_split(h, batch);
+    if (q.lps == 1 && fit > 1 && h->split_override != 1 && h->lanes_override != 64) q.lps = fit;
+    if (q.lps > 1) {
+        q.waves = pick_waves(h, batch);
+        return q;
+    }
+    q.lds = (size_t)(no >= 10 ? mpc::RowLdsC::total_with_positions(N, 1, no) : mpc::RowLdsC::total(N, 1)) * sizeof(double);
+    return q;
+}
+
 SolvePlan plan_solve(mpc_handle *h, int batch, bool lookahead)
 {
+    if (ref_active(h)) return plan_solve_ref(h, batch);
     SolvePlan q = {1, 1, 64, 2, 0};
     const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
     q.lps = pick_split(h, batch);
@@ -323,9 +359,51 @@ int launch_one_lane_g(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 
     return fail(MPC_ERR_ARG, "no kernel variant for this lane mapping (three instances per wavefront need the row-parallel sweeps)");
 }
 
+// the REF instantiations (plan_solve_ref)
+template <int NO>
+int launch_ref_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
+{
+    if (p.n_obst != NO) return launch_one_lane<NO, 64, 3, true, true>(h, p, s, dim3(p.batch), q.lds);
+    return launch_one_lane<NO, 64, 3, false, true>(h, p, s, dim3(p.batch), q.lds);
+}
+
+int dispatch_solve_ref(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
+{
+    int rc = MPC_OK;
+    if (wide_rows(h->cfg.n_obst)) {
+        rc = check_wide(h); if (rc) return rc;
+        const bool masked = partial_rows(h);
+        if (row_capacity(h->cfg.n_obst) == 20) rc = masked ? launch_wide<20, true, true>(h, p, s) : launch_wide<20, false, true>(h, p, s);
+        else rc = masked ? launch_wide<32, true, true>(h, p, s) : launch_wide<32, false, true>(h, p, s);
+    } else if ((rc = check_ref_mapping(h)) != MPC_OK) {
+        return rc;
+    } else if (q.lps > 1) {
+        switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
+        case 32: rc = launch_split<3, 2, true>(h, p, s); break;
+        case 33: rc = launch_split<3, 3, true>(h, p, s); break;
+        case 52: rc = launch_split<5, 2, true>(h, p, s); break;
+        case 53: rc = launch_split<5, 3, true>(h, p, s); break;
+        case 102: rc = launch_split<10, 2, true>(h, p, s); break;
+        case 103: rc = launch_split<10, 3, true>(h, p, s); break;
+        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
+        }
+    } else {
+        switch (row_capacity(h->cfg.n_obst)) {
+        case 3: rc = launch_ref_one_lane<3>(h, p, s, q); break;
+        case 5: rc = launch_ref_one_lane<5>(h, p, s, q); break;
+        case 10: rc = launch_ref_one_lane<10>(h, p, s, q); break;
+        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
+        }
+    }
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 // launches the variant the plan names; no event handling here
 int dispatch_solve(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
 {
+    if (p.yref) return dispatch_solve_ref(h, p, s, q);
     int rc = MPC_OK;
     if (wide_rows(h->cfg.n_obst)) {
         rc = check_wide(h); if (rc) return rc;
@@ -403,6 +481,10 @@ int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
 {
     p.iters_acc = h->d_iters_acc; p.status_acc = h->d_status_acc;
     p.alpha = h->d_alpha;
+    p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
+    if (h->d_yref && p.batch > h->ref_batch) return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this solve");
+    if ((p.fused & MPC_STEP_ADVANCE_REF) && (!h->d_yref || !h->d_ref_off))
+        return fail(MPC_ERR_ARG, "MPC_STEP_ADVANCE_REF needs a per-stage reference with offsets (mpc_set_reference[_dev])");
     // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
     if (h->d_alpha && h->d_alpha == h->d_alpha_own && p.batch > h->alpha_batch)
         return fail(MPC_ERR_ARG, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
@@ -521,7 +603,7 @@ int mpc_destroy(mpc_handle *h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
-                    h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist};
+                    h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->h_pack) (void)hipHostFree(h->h_pack);
@@ -680,11 +762,17 @@ int mpc_linearize_dev(mpc_handle *h, int batch, const double *d_x0, const double
     if (batch == 0) return MPC_OK;
     if (!d_x0 || !d_P || !d_goal || !d_X || !d_U || !d_A || !d_B || !d_b || !d_q || !d_hval || !d_dh) return fail(MPC_ERR_ARG, "null device pointer");
     HIPCHK(hipSetDevice(h->device));
+    if (h->d_yref && batch > h->ref_batch) return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this call");
     mpc::KParams p = make_params(h->cfg, batch);
     p.x0 = d_x0; p.P = d_P; p.goal = d_goal;
+    p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
     const int count = batch * (h->cfg.N + 1);
-    hipLaunchKernelGGL(mpc::linearize_kernel, dim3((count + 127) / 128), dim3(128), 0, pick(h, stream), p, h->cfg.n_obst, d_X, d_U,
-                       d_A, d_B, d_b, d_q, d_hval, d_dh);
+    if (h->d_yref)
+        hipLaunchKernelGGL(mpc::linearize_kernel<true>, dim3((count + 127) / 128), dim3(128), 0, pick(h, stream), p, h->cfg.n_obst, d_X, d_U,
+                           d_A, d_B, d_b, d_q, d_hval, d_dh);
+    else
+        hipLaunchKernelGGL(mpc::linearize_kernel<false>, dim3((count + 127) / 128), dim3(128), 0, pick(h, stream), p, h->cfg.n_obst, d_X, d_U,
+                           d_A, d_B, d_b, d_q, d_hval, d_dh);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -1058,6 +1146,50 @@ int mpc_set_slack_schedule(mpc_handle *h, int batch, const double *alpha)
     return MPC_OK;
 }
 
+/* ------------------------------------------------ per-stage reference ------------------------------------------------ */
+
+int mpc_set_reference(mpc_handle *h, int batch, int T, const double *yref, const int32_t *offset)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!yref) { h->d_yref = nullptr; h->d_ref_off = nullptr; h->ref_T = 0; h->ref_batch = 0; return MPC_OK; }
+    if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "a per-stage reference needs batch in [1, max_batch]");
+    if (T < 1) return fail(MPC_ERR_ARG, "a per-stage reference needs T >= 1 rows");
+    const size_t n = (size_t)batch * T * 6;
+    for (size_t k = 0; k < n; k++)
+        if (!(yref[k] >= -1e300 && yref[k] <= 1e300)) return fail(MPC_ERR_ARG, "reference entries must be finite");
+    if (offset)
+        for (int b = 0; b < batch; b++)
+            if (offset[b] < 0) return fail(MPC_ERR_ARG, "reference offsets must be >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t cap = (size_t)h->max_batch * T * 6;
+    if (h->yref_own_cap < cap) {
+        HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the old copy)
+        if (h->d_yref_own) HIPCHK(hipFree(h->d_yref_own));
+        h->d_yref_own = nullptr; h->yref_own_cap = 0; h->d_yref = nullptr;
+        HIPCHK(hipMalloc(&h->d_yref_own, cap * sizeof(double)));
+        h->yref_own_cap = cap;
+    }
+    HIPCHK(hipMemcpyAsync(h->d_yref_own, yref, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (offset) {
+        if (!h->d_ref_off_own) HIPCHK(hipMalloc(&h->d_ref_off_own, (size_t)h->max_batch * sizeof(int32_t)));
+        HIPCHK(hipMemcpyAsync(h->d_ref_off_own, offset, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->d_yref = h->d_yref_own; h->d_ref_off = offset ? h->d_ref_off_own : nullptr;
+    h->ref_T = T; h->ref_batch = batch;
+    return MPC_OK;
+}
+
+int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d_offset)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!d_yref) { h->d_yref = nullptr; h->d_ref_off = nullptr; h->ref_T = 0; h->ref_batch = 0; return MPC_OK; }
+    if (T < 1) return fail(MPC_ERR_ARG, "a per-stage reference needs T >= 1 rows");
+    h->d_yref = d_yref; h->d_ref_off = d_offset;
+    h->ref_T = T; h->ref_batch = h->max_batch;
+    return MPC_OK;
+}
+
 /* --------------------------------------------------- measurement --------------------------------------------------- */
 
 int mpc_profile_enable(mpc_handle *h, int on)
@@ -1193,7 +1325,12 @@ int mpc_get_kernel_name(mpc_handle *h, int batch, int lookahead, char *buf, int 
     const char *masked = partial_rows(h) ? "true" : "false";      // (all template arguments, as rocprofv3 prints the instantiation)
     if (wide_rows(h->cfg.n_obst)) {
         const int rc = check_wide(h); if (rc) return rc;
-        snprintf(buf, (size_t)len, "rti_wide_kernel<%d, 2, %s>", cap, masked);
+        snprintf(buf, (size_t)len, ref_active(h) ? "rti_wide_kernel<%d, 2, %s, true>" : "rti_wide_kernel<%d, 2, %s>", cap, masked);
+    }
+    else if (ref_active(h)) {      // (the REF instantiations carry one more template argument)
+        const int rc = check_ref_mapping(h); if (rc) return rc;
+        if (q.lps > 1) snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, false, true>", cap, q.lps, q.waves == 2 && !partial_rows(h) ? "true" : "false", masked);
+        else snprintf(buf, (size_t)len, "rti_solve_kernel<%d, 64, 3, %s, true>", cap, masked);
     }
     else if (q.lps > 1) {
         const bool w2 = q.waves == 2 && !partial_rows(h);

@@ -54,7 +54,8 @@ enum : int {
     kFuseResetOnFail = 8,  // status 4 -> set_initial_guess() before the plant step (:203-205)
     kFuseAliasBug = 16,    // ... which in the reference also zeroes the plant's v, omega (defect D2, :301-302)
     kFuseMetrics = 32,     // episode bookkeeping of RobotOcpProblem.step (:213-250)
-    kFuseInterpGuess = 64  // ... and that set_initial_guess() is the straight-line variant the reference keeps commented out (:293-300, interp_guess below)
+    kFuseInterpGuess = 64, // ... and that set_initial_guess() is the straight-line variant the reference keeps commented out (:293-300, interp_guess below)
+    kFuseAdvanceRef = 128  // per-stage reference: offset[inst] += 1 for every instance that stepped (mpc_set_reference; REF instantiations only)
 };
 
 struct KParams {
@@ -95,7 +96,45 @@ struct KParams {
     int32_t *ep_flags;        // [B] bit0 reached goal (episode finished), bit1 left the arena, bit2 hit an obstacle
     int32_t *ep_steps;        // [B] completed control steps (the reference's `i`)
     double *trace;            // optional [batch][iter_max][4] = (mu, sigma, alpha, cmax) per IPM iteration (debug)
+    // ---- per-stage reference (mpc_set_reference; read only by the REF instantiations).  Kept at the end: the fields above keep their offsets ----
+    const double *yref;       // [B][ref_T][6], y order (x, y, v, om, ua, ual); stage i uses row min(off + i, ref_T - 1), the terminal stage columns 0..3 of row min(off + N, ref_T - 1)
+    int32_t *ref_off;         // [B] row offsets, or null (0); kFuseAdvanceRef adds 1 behind a step
+    int ref_T;
 };
+
+// Row of the per-stage reference that stage i of instance inst uses: min(off + i, T - 1), floored at 0 (device offsets are not validated; a negative one
+// reads row 0 instead of memory in front of the array)
+__device__ __forceinline__ const double *ref_row(const double *yref, const int32_t *off, int T, int inst, int i)
+{
+    // the offset is read through a vector load, the way MPC_STEP_ADVANCE_REF writes it (a wave-uniform read would otherwise become a scalar load
+    // through the scalar data cache)
+    const int32_t *op = off;
+    asm volatile("" : "+v"(op));
+    const int o = off ? op[inst] : 0;
+    int r = o > T - 1 - i ? T - 1 : o + i;
+    r = r < 0 ? 0 : r;
+    return yref + ((size_t)inst * T + r) * 6;
+}
+
+// The six reference values of stage i in y order, the input columns zero at the terminal stage (its cost has no input part)
+__device__ __forceinline__ void load_ref(const KParams &p, int inst, int i, bool has_u, double r[6])
+{
+    const double *row = ref_row(p.yref, p.ref_off, p.ref_T, inst, i);
+#pragma unroll
+    for (int c = 0; c < 4; c++) r[c] = row[c];
+    r[4] = has_u ? row[4] : 0.0; r[5] = has_u ? row[5] : 0.0;
+}
+
+// LS cost of one stage at (x, u) against the reference r (y order): the goal path's expression with every residual written as (value - r)
+__device__ __forceinline__ double ls_cost_ref(const double Wg[6], const double Weg[4], const double xi[5], const double ui[2], const double r[6], bool has_u)
+{
+    const double ex = xi[0] - r[0], ey = xi[1] - r[1], ev = xi[3] - r[2], eo = xi[4] - r[3];
+    if (has_u) {
+        const double ea = ui[0] - r[4], eal = ui[1] - r[5];
+        return 0.5 * (Wg[0] * ex * ex + Wg[1] * ey * ey + Wg[2] * ev * ev + Wg[3] * eo * eo + Wg[4] * ea * ea + Wg[5] * eal * eal);
+    }
+    return 0.5 * (Weg[0] * ex * ex + Weg[1] * ey * ey + Weg[2] * ev * ev + Weg[3] * eo * eo);
+}
 
 static constexpr double kTLMin = 1e-11;  // floor for lam and t (oracle/mpc_oracle.c TL_MIN: 1e-13 until round 3 -- the weights lam / t of collapsed pairs then cost the
                                          // end-game's Newton step its last digits: worst distance from the exact QP solution 7e-4 -> 8e-6 on first solves of C5's problem)
@@ -2061,9 +2100,10 @@ __device__ __forceinline__ void systolic_rollout(int stage, int N, const StageLi
 // MASKED: the problem has p.n_obst < NOBST obstacles (any count the reference's N_OBST may take); the rows of obstacle j >= p.n_obst do not exist
 // (skipped by wave-uniform branches), the input arrays are strided by p.n_obst, and the unused position slots replicate the last obstacle so
 // that everything computed from them stays finite.  Instantiated for one instance per wavefront only; the stage-split kernel takes any count.
-template <int NOBST, int G, int FACT, bool MASKED = false>
+template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false>
 __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 {
+    static_assert(!REF || (G == 64 && FACT == 3), "the per-stage reference runs on one instance per wavefront, compact stage blocks");
     const int nact = MASKED ? p.n_obst : NOBST;
 #define ROW_OFF(j) (MASKED && (j) >= nact)
 #define OBST_IN(j) (MASKED ? ((j) < nact ? (j) : nact - 1) : (j))
@@ -2105,6 +2145,9 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     gl[0] = p.goal[(size_t)inst * 2]; gl[1] = p.goal[(size_t)inst * 2 + 1];
     if constexpr (G == 64) { gl[0] = wave_uniform(gl[0]); gl[1] = wave_uniform(gl[1]); }      // one instance per wavefront: the goal is the same in every lane -> scalar registers
                                                                                               // (with ten obstacles these four registers are the difference between 28 and 0 B of scratch)
+    // REF: this lane's stage reference, read once and held in vector registers through the interior point (the predictor re-forms the gradient every iteration)
+    double yr[REF ? 6 : 1];
+    if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
     double *Xg = p.X + (size_t)inst * (N + 1) * 5, *Ug = p.U + (size_t)inst * N * 2;
     // episode already finished (goal reached): the instance idles, nothing of it is touched
     const bool ep_done = (p.fused & kFuseMetrics) && p.ep_flags && (p.ep_flags[inst] & 1);
@@ -2472,9 +2515,15 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
         Hd[0] = has_u ? hs[0] : 0.0; Hd[1] = has_u ? hs[1] : 0.0;
 #pragma unroll
         for (int c = 0; c < 5; c++) Hd[2 + c] = has_u ? hs[2 + c] : ht[c];
+        if constexpr (REF) {
+        gloc[0] = (has_u ? wg[4] : 0.0) * (vals[0] - yr[4]); gloc[1] = (has_u ? wg[5] : 0.0) * (vals[1] - yr[5]);
+        gloc[2] = (has_u ? wg[0] : we[0]) * (vals[2] - yr[0]); gloc[3] = (has_u ? wg[1] : we[1]) * (vals[3] - yr[1]); gloc[4] = 0.0;
+        gloc[5] = (has_u ? wg[2] : we[2]) * (vals[4] - yr[2]); gloc[6] = (has_u ? wg[3] : we[3]) * (vals[5] - yr[3]);
+        } else {
         gloc[0] = (has_u ? wg[4] : 0.0) * vals[0]; gloc[1] = (has_u ? wg[5] : 0.0) * vals[1];
         gloc[2] = (has_u ? wg[0] : we[0]) * (vals[2] - gl[0]); gloc[3] = (has_u ? wg[1] : we[1]) * (vals[3] - gl[1]); gloc[4] = 0.0;
         gloc[5] = (has_u ? wg[2] : we[2]) * vals[4]; gloc[6] = (has_u ? wg[3] : we[3]) * vals[5];
+        }
     }
     Hq[0] = has_u ? Hd[0] : 1.0; Hq[1] = has_u ? Hd[1] : 1.0; Hq[2] = Hd[2]; Hq[3] = Hd[3]; Hq[4] = Hd[4]; Hq[5] = Hd[5]; Hq[6] = Hd[6]; Hq[7] = 0.0;   // diagonal in z order, then Qxy
 #pragma unroll
@@ -3391,7 +3440,19 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     // NLP objective at the returned iterate: LS cost + exact penalty of the obstacle violation
     if (t_cost) {
         double J = 0.0;
-        if (act) {
+        if (REF && act) {
+            const double *row = ref_row(pt->yref, pt->ref_off, pt->ref_T, inst, i);
+            const double r[6] = {row[0], row[1], row[2], row[3], has_u ? row[4] : 0.0, has_u ? row[5] : 0.0};
+            J = ls_cost_ref(t_Wg, t_Weg, xi, ui, r, has_u);
+#pragma unroll
+            for (int j = 0; j < NOBST; j++) {
+                if (ROW_OFF(j)) continue;
+                const double dx = xi[0] - pos_x(j), dy = xi[1] - pos_y(j);
+                const double hv = dx * dx + dy * dy - t_r2;
+                const double v = hv < 0 ? -hv : 0.0;
+                J += zpen * (v + 0.5 * v * v);
+            }
+        } else if (act) {
             const double ex = xi[0] - gl[0], ey = xi[1] - gl[1];
             if (has_u) J = 0.5 * (t_Wg[0] * ex * ex + t_Wg[1] * ey * ey + t_Wg[2] * xi[3] * xi[3] + t_Wg[3] * xi[4] * xi[4]
                                   + t_Wg[4] * ui[0] * ui[0] + t_Wg[5] * ui[1] * ui[1]);
@@ -3413,6 +3474,9 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
         if (t_status_acc) t_status_acc[inst] += (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
         if (t_status) t_status[inst] = status;
         if (t_iters) t_iters[inst] = it_done;
+    }
+    if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
+        if ((t_fused & kFuseAdvanceRef) && i == 0 && store && pt->ref_off) pt->ref_off[inst] += 1;
     }
 }
 #undef ROW_OFF

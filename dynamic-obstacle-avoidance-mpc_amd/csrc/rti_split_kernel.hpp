@@ -57,9 +57,10 @@ __device__ __forceinline__ double nth_of_six(double a0, double a1, double a2, do
 // MASKED: fewer obstacles than row pairs (p.n_obst < NOBST, see rti_solve_kernel): a template flag, because with the count known at compile time
 // the per-slot row flags fold into the stage flags (measured: the run-time count costs 1 % at C2)
 // BLK2: the stage recursions run on PAIRS of stages (Blk2Lds / rowpar_factor2, rti_kernel.hpp): even horizons, dense blocks, one wavefront per SIMD
-template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false>
+template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false>
 __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 {
+    static_assert(!REF || !BLK2, "the per-stage reference is not built for the block-2 recursions");
     static_assert(LPS == 2 || LPS == 3, "two or three lanes per horizon stage");
     static_assert(!BLK2 || !W2, "the block-2 recursions exist on the dense layout only");
     using SL = SplitLds<LPS, NOBST, W2, BLK2>;
@@ -304,6 +305,9 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     bool bp[NBL];
     double cl0[NBL], ch0[NBL], hq[NBL], hd[NBL], gc0[NBL];
     double ll[NBL], tl[NBL], lh[NBL], th[NBL], rtl[NBL], rth[NBL], zs[NBL];
+    // REF: this lane's stage reference, needed only here (gc0 carries it through the interior point); the cost at the end reads it again
+    double yr[REF ? 6 : 1];
+    if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
     {
         auto slot_init = [&](auto sc) {     // slot index as a compile-time constant
             constexpr int s = decltype(sc)::value;
@@ -317,7 +321,8 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             hq[s] = (is_u && !has_u) ? 1.0 : hd[s];       // the terminal stage has no inputs: unit block keeps Muu regular
             const double wg = part_of(sc, has_u ? p.Wg[4] : 0.0, has_u ? p.Wg[5] : 0.0, has_u ? p.Wg[0] : p.Weg[0], has_u ? p.Wg[1] : p.Weg[1],
                                       has_u ? p.Wg[2] : p.Weg[2], has_u ? p.Wg[3] : p.Weg[3]);
-            gc0[s] = wg * (val - part_of(sc, 0.0, 0.0, gl[0], gl[1], 0.0, 0.0));
+            if constexpr (REF) gc0[s] = wg * (val - part_of(sc, yr[4], yr[5], yr[0], yr[1], yr[2], yr[3]));
+            else gc0[s] = wg * (val - part_of(sc, 0.0, 0.0, gl[0], gl[1], 0.0, 0.0));
             cl0[s] = val - lo; ch0[s] = hi - val;
             tl[s] = fmax(cl0[s], p.thr0); th[s] = fmax(ch0[s], p.thr0);
             rtl[s] = rcp_nr(tl[s]); rth[s] = rcp_nr(th[s]);
@@ -1119,7 +1124,11 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     if (p.cost) {
         double J = 0.0;
         if (act) {
-            if (own) {
+            if (REF && own) {
+                const double *row = ref_row(p.yref, p.ref_off, p.ref_T, inst, i);
+                const double r[6] = {row[0], row[1], row[2], row[3], has_u ? row[4] : 0.0, has_u ? row[5] : 0.0};
+                J = ls_cost_ref(p.Wg, p.Weg, xi, ui, r, has_u);
+            } else if (own) {
                 const double ex = xi[0] - gl[0], ey = xi[1] - gl[1];
                 if (has_u) J = 0.5 * (p.Wg[0] * ex * ex + p.Wg[1] * ey * ey + p.Wg[2] * xi[3] * xi[3] + p.Wg[3] * xi[4] * xi[4]
                                       + p.Wg[4] * ui[0] * ui[0] + p.Wg[5] * ui[1] * ui[1]);
@@ -1141,6 +1150,9 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         if (p.status_acc) p.status_acc[inst] += (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
         if (p.status) p.status[inst] = status;
         if (p.iters) p.iters[inst] = it_done;
+    }
+    if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
+        if ((p.fused & kFuseAdvanceRef) && lane == 0 && store && p.ref_off) p.ref_off[inst] += 1;
     }
 #ifdef MPC_PHASE_TIMING
     __builtin_amdgcn_s_waitcnt(0);

@@ -59,7 +59,7 @@ __device__ __forceinline__ void group_sync()
 }
 
 // MASKED: fewer obstacles than row pairs (p.n_obst < CAP): the run-time count, as in rti_split_kernel
-template <int CAP, int LPS, bool MASKED = false>
+template <int CAP, int LPS, bool MASKED = false, bool REF = false>
 __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(const KParams p)
 {
     static_assert(LPS == 2, "two lanes per horizon stage (N <= 31)");
@@ -227,6 +227,9 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     bool bp[NBL];
     double cl0[NBL], ch0[NBL], hq[NBL], hd[NBL], gc0[NBL];
     double ll[NBL], tl[NBL], lh[NBL], th[NBL], rtl[NBL], rth[NBL], zs[NBL];
+    // REF: this lane's stage reference, needed only here (gc0 carries it through the interior point); the cost at the end reads it again
+    double yr[REF ? 6 : 1];
+    if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
     {
         auto slot_init = [&](auto sc) {
             constexpr int s = decltype(sc)::value;
@@ -240,7 +243,8 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
             hq[s] = (is_u && !has_u) ? 1.0 : hd[s];
             const double wg = part_of(sc, has_u ? p.Wg[4] : 0.0, has_u ? p.Wg[5] : 0.0, has_u ? p.Wg[0] : p.Weg[0], has_u ? p.Wg[1] : p.Weg[1],
                                       has_u ? p.Wg[2] : p.Weg[2], has_u ? p.Wg[3] : p.Weg[3]);
-            gc0[s] = wg * (val - part_of(sc, 0.0, 0.0, gl[0], gl[1], 0.0, 0.0));
+            if constexpr (REF) gc0[s] = wg * (val - part_of(sc, yr[4], yr[5], yr[0], yr[1], yr[2], yr[3]));
+            else gc0[s] = wg * (val - part_of(sc, 0.0, 0.0, gl[0], gl[1], 0.0, 0.0));
             cl0[s] = val - lo; ch0[s] = hi - val;
             tl[s] = fmax(cl0[s], p.thr0); th[s] = fmax(ch0[s], p.thr0);
             rtl[s] = rcp_nr(tl[s]); rth[s] = rcp_nr(th[s]);
@@ -781,7 +785,11 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     if (p.cost) {
         double J = 0.0;
         if (act) {
-            if (w0 && own) {
+            if (REF && w0 && own) {
+                const double *row = ref_row(p.yref, p.ref_off, p.ref_T, inst, i);
+                const double r[6] = {row[0], row[1], row[2], row[3], has_u ? row[4] : 0.0, has_u ? row[5] : 0.0};
+                J = ls_cost_ref(p.Wg, p.Weg, xi, ui, r, has_u);
+            } else if (w0 && own) {
                 const double ex = xi[0] - gl[0], ey = xi[1] - gl[1];
                 if (has_u) J = 0.5 * (p.Wg[0] * ex * ex + p.Wg[1] * ey * ey + p.Wg[2] * xi[3] * xi[3] + p.Wg[3] * xi[4] * xi[4]
                                       + p.Wg[4] * ui[0] * ui[0] + p.Wg[5] * ui[1] * ui[1]);
@@ -844,6 +852,9 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
         if (p.status_acc) p.status_acc[inst] += (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
         if (p.status) p.status[inst] = status;
         if (p.iters) p.iters[inst] = it_done;
+    }
+    if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
+        if ((p.fused & kFuseAdvanceRef) && lane == 0 && store && p.ref_off) p.ref_off[inst] += 1;
     }
 }
 

@@ -4,6 +4,7 @@
 Only the methods and fields the reference actually calls exist:
   ocp:  set(stage, 'x'|'u'|'p'|'lbx'|'ubx', v), set_params_sparse(stage, idx, v), cost_set(stage, 'zl'|'Zl'|'yref', v),
         solve() -> int, get(stage, 'x'|'u'), reset()
+        (stage_yref=True: cost_set(i, 'yref', v) sets stage i's reference, as in acados; by default only the position is kept, for every stage)
   sim:  set('x'|'u', v), solve(), get('x')
 Host arrays are copied in on set and fresh copies are returned by get, as acados does.
 """
@@ -13,7 +14,7 @@ from .solver import BatchedMpc
 
 
 class AcadosOcpSolverShim:
-    def __init__(self, N=20, n_obst=5, Tf=2.0, goal=(0.0, 0.0), x0=None, device=0, mpc=None, **cfg):
+    def __init__(self, N=20, n_obst=5, Tf=2.0, goal=(0.0, 0.0), x0=None, device=0, mpc=None, stage_yref=False, **cfg):
         self.N, self.n_obst = N, n_obst
         self.mpc = mpc if mpc is not None else BatchedMpc(N, n_obst, Tf, max_batch=1, device=device, **cfg)
         self.X = np.zeros((N + 1, 5)); self.U = np.zeros((N, 2))
@@ -23,6 +24,9 @@ class AcadosOcpSolverShim:
         self.zl = np.zeros((N + 1, n_obst)); self.Zl = np.zeros((N + 1, n_obst))
         self._slack_touched = False     # until cost_set('zl'|'Zl') is called the kernel's built-in schedule (:145-148) applies
         self.status = 0; self.iters = 0; self.cost = 0.0
+        # stage_yref: a per-stage reference [N+1][6] (y order x, y, v, omega, u_a, u_alpha; row N uses columns 0..3), forwarded with every solve
+        self.stage_yref = bool(stage_yref)
+        self.yref = np.zeros((N + 1, 6)); self.yref[:, :2] = self.goal
 
     # -- setters ---------------------------------------------------------------------------------------------------
     def set(self, stage, field, value):
@@ -52,6 +56,12 @@ class AcadosOcpSolverShim:
                 raise ValueError("libmpcgpu takes one finite slack weight >= 0 per stage (zl_i = Zl_i = alpha_i * ones, robot_ocp_problem.py:149-150)")
             (self.zl if field == "zl" else self.Zl)[stage] = v
             self._slack_touched = True
+        elif field == "yref" and self.stage_yref:      # acados: stage i < N takes ny = 6 values, the terminal stage ny_e = 4
+            n = 4 if stage == self.N else 6
+            if v.size != n or not np.all(np.isfinite(v)):
+                raise ValueError(f"stage {stage} takes {n} finite reference values, got {v.size}")
+            self.yref[stage] = 0.0
+            self.yref[stage, :n] = v
         elif field == "yref":
             self.goal = v[:2].copy()    # set_subgoal writes [x, y, 0, 0, 0] (:284): only the position is meaningful
         else:
@@ -69,6 +79,8 @@ class AcadosOcpSolverShim:
             if not np.array_equal(self.zl, self.Zl):
                 raise ValueError("zl and Zl differ: libmpcgpu implements the reference's zl_i = Zl_i (robot_ocp_problem.py:149-152)")
             self.mpc.set_slack_schedule(self.zl[None, :, 0])
+        if self.stage_yref:
+            self.mpc.set_reference(self.yref[None])
         self.mpc.set_warmstart(self.X[None], self.U[None])
         out = self.mpc.solve(self.x0[None], self.P[None], self.goal[None])
         X, U = self.mpc.get_traj(1)

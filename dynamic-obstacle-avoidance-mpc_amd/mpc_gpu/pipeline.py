@@ -89,6 +89,12 @@ class PipelinedMpc:
                                    self._sl(status, lo, hi), self._sl(iters, lo, hi), self._sl(noise, lo, hi), randomness, vmax, flags,
                                    self._sl(min_margin, lo, hi), self._sl(ep_flags, lo, hi), self._sl(ep_steps, lo, hi), stream=s.cuda_stream)
 
+    def set_reference_dev(self, yref, offset=None):
+        """per-stage reference (BatchedMpc.set_reference) from device tensors (max_batch, T, 6) and optional int32 offsets (max_batch,):
+        every sub-handle gets its contiguous slice (same T), used in place; None clears it"""
+        for lo, hi, m, _ in self.parts:
+            m.set_reference(None if yref is None else yref[lo:hi], None if yref is None else self._sl(offset, lo, hi))
+
     # ------------------------------------------------------------------ the cost exchange lives on the first sub-batch's handle (include/mpc_gpu.h mpc_comm_*)
     def comm_init(self, rank, world, unique_id):
         self.parts[0][2].comm_init(rank, world, unique_id)

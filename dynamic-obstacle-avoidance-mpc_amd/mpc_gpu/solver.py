@@ -136,6 +136,30 @@ class BatchedMpc:
                 raise ValueError(f"a device schedule must be ({self.max_batch}, {self.N + 1})")
             _lib.check(_lib.lib().mpc_set_slack_schedule_dev(self._h, _ptr(alpha)))
 
+    def set_reference(self, yref, offset=None):
+        """Per-stage reference, acados cost_set(stage, 'yref', v) (include/mpc_gpu.h mpc_set_reference): stage i of instance b tracks
+        yref[b, min(offset[b] + i, T - 1)] in y order (x, y, v, omega, u_a, u_alpha); the terminal stage columns 0..3 of row min(offset[b] + N, T - 1).
+        yref: a numpy array (B, T, 6) -- (B, N+1, 6) is a plain per-solve reference -- with an optional offset array (B,) (int32, copied), or a
+        device tensor (max_batch, T, 6) used in place with an optional int32 device tensor (max_batch,) of offsets.  None clears it."""
+        if yref is None:
+            _lib.check(_lib.lib().mpc_set_reference(self._h, 0, 0, None, None))
+        elif isinstance(yref, (np.ndarray, list, tuple)):
+            yref = _f64(yref)
+            if yref.ndim != 3 or yref.shape[2] != 6:
+                raise ValueError(f"yref must be (B, T, 6), got {yref.shape}")
+            off = None
+            if offset is not None:
+                off = np.ascontiguousarray(offset, dtype=np.int32)
+                if off.shape != (yref.shape[0],):
+                    raise ValueError(f"offset must be ({yref.shape[0]},), got {off.shape}")
+            _lib.check(_lib.lib().mpc_set_reference(self._h, yref.shape[0], yref.shape[1], _ptr(yref), _ptr(off)))
+        else:
+            if len(yref.shape) != 3 or yref.shape[0] != self.max_batch or yref.shape[2] != 6 or not yref.is_contiguous():
+                raise ValueError(f"a device reference must be a contiguous ({self.max_batch}, T, 6) tensor")
+            if offset is not None and (tuple(offset.shape) != (self.max_batch,) or str(offset.dtype) != "torch.int32" or not offset.is_contiguous()):
+                raise ValueError(f"device offsets must be a contiguous int32 tensor ({self.max_batch},)")
+            _lib.check(_lib.lib().mpc_set_reference_dev(self._h, int(yref.shape[1]), _ptr(yref), _ptr(offset)))
+
     def plant_step(self, x, u):
         """ocp_integrator set/solve/get, robot_ocp_problem.py:207-212."""
         x = _f64(np.atleast_2d(x)); u = _f64(np.atleast_2d(u), (x.shape[0], 2))
@@ -237,7 +261,8 @@ class BatchedMpc:
     def closed_loop_step_dev(self, batch, x0, obst, goal, X, U, u0=None, cost=None, status=None, iters=None, noise=None,
                              randomness=0.1, vmax=2.0, flags=_lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES,
                              min_margin=None, ep_flags=None, ep_steps=None, stream=None):
-        """One whole control step (look-ahead, solve, plant, obstacle motion, bookkeeping, shift) in one launch."""
+        """One whole control step (look-ahead, solve, plant, obstacle motion, bookkeeping, shift) in one launch.  flags | STEP_ADVANCE_REF moves
+        the per-stage reference window (set_reference with offsets) one row on for every instance that stepped."""
         _lib.check(_lib.lib().mpc_closed_loop_step_dev(self._h, batch, _ptr(x0), _ptr(obst), _ptr(goal), _ptr(X), _ptr(U), _ptr(u0),
                                                        _ptr(cost), _ptr(status), _ptr(iters), _ptr(noise), randomness, vmax, flags,
                                                        _ptr(min_margin), _ptr(ep_flags), _ptr(ep_steps), _ptr(stream)))

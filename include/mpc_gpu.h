@@ -157,6 +157,21 @@ int mpc_solve_obst(mpc_handle *h, int batch, const double *x0, const double *obs
 int mpc_set_slack_schedule(mpc_handle *h, int batch, const double *alpha);
 int mpc_set_slack_schedule_dev(mpc_handle *h, const double *d_alpha);
 
+/* Per-stage reference (acados cost_set(stage, 'yref', v) / cost_set(N, 'yref_e', v), robot_ocp_problem.py:284): yref[batch][T][6] in y order
+ * (x, y, v, omega, u_a, u_alpha), optional row offsets offset[batch] (int32, NULL = 0).  Stage i < N of instance b tracks row
+ * min(offset[b] + i, T - 1), the terminal stage columns 0..3 of row min(offset[b] + N, T - 1): the gradient is cs W (y - yref_i) and the
+ * reported cost is the LS cost against it.  Everything else (slack schedule, interpolated guess, goal-reached test, distances) still reads
+ * the per-call goal.  Host arrays, copied; applies to every following solve (mpc_solve, mpc_solve_obst, mpc_solve_dev,
+ * mpc_closed_loop_step_dev, mpc_linearize_dev) of the first `batch` instances until it is replaced; yref = NULL returns to the goal-derived
+ * reference.  MPC_ERR_ARG for non-finite entries, T < 1, batch outside [1, max_batch] and negative offsets.
+ * _dev: device arrays d_yref[max_batch][T][6] and d_offset[max_batch] (or NULL), used in place and not validated.
+ * A solve with a reference runs the stage-split mapping for N <= 31 (also where the goal path would pack several instances into a wavefront),
+ * one instance per wavefront on compact stage blocks beyond (or with mpc_set_lanes_per_stage(1)), and the multi-wavefront kernel for more than
+ * 10 obstacles; with mpc_set_matrix_cores(1), mpc_set_row_parallel(0), mpc_set_block_riccati(1) or lanes per instance 16, 21 or 32 it
+ * returns MPC_ERR_ARG. */
+int mpc_set_reference(mpc_handle *h, int batch, int T, const double *yref, const int32_t *offset);
+int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d_offset);
+
 /* Plant integrator, ocp_integrator.set/solve/get, robot_ocp_problem.py:207-212 (same IRK as the OCP) */
 int mpc_plant_step(mpc_handle *h, int batch, const double *x, const double *u, double *x_next);
 /* Obstacle look-ahead only: obst[B][n_obst][4] -> P[B][N+1][n_obst][2] (visualization.py:62-79) */
@@ -182,6 +197,7 @@ int mpc_predict_dev(mpc_handle *h, int batch, const double *d_obst, double *d_P,
 #define MPC_STEP_ALIAS_BUG 16
 #define MPC_STEP_METRICS 32
 #define MPC_STEP_INTERP_GUESS 64   /* with MPC_STEP_RESET_ON_FAIL: the reset writes the straight-line guess of mpc_reset_guess_interp */
+#define MPC_STEP_ADVANCE_REF 128   /* behind the step, offset[b] += 1 of the per-stage reference for every instance that stepped (idle ones do not); needs offsets */
 int mpc_closed_loop_step_dev(mpc_handle *h, int batch, double *d_x0, double *d_obst, const double *d_goal, double *d_X, double *d_U,
                              double *d_u0, double *d_cost, int32_t *d_status, int32_t *d_iters, const double *d_noise,
                              double randomness, double vmax, int flags, double *d_min_margin, int32_t *d_ep_flags,
