@@ -411,9 +411,53 @@ __global__ __launch_bounds__(64) void adjoint_check_kernel(KParams p, const doub
     if (own && has_u) ru[(size_t)inst * N + i] = r;
 }
 
+// ---- per-instance parameters (mpc_set_instance_params): the derived tables the IPAR kernels read ----
+// What a null group falls back to, and the handle's scalings (mpc_api.hip::ip_defaults)
+struct IpDefaults {
+    double cs, lm_stage, lm_term;      // as make_params: cost scale of the stages (dt or 1), LM term of the stages and of the terminal stage
+    double W[6], We[4], r_safe;        // mpc_config
+    double r_hit, hit_off;             // the fused step's hit radius, and cfg.r_safe - r_hit
+};
+
+// Row b of the three tables from row b of W[B][6], We[B][4], r_safe[B][n_obst], r_hit[B][n_obst] (each may be null): the expressions of make_params,
+// entry for entry (z order of the diagonals: ua, ual, x, y, psi, v, om; y order of the weights: x, y, v, om, ua, ual).
+// Unfused arithmetic on both sides: the host compiler emits no fused multiply-add for `cs * W + lm` (make_params), device code contracts it -- also
+// when written with __dmul_rn / __dadd_rn, which are plain operators in HIP's headers -- so contraction is switched off for this function's body
+__host__ __device__ inline void derive_instance_params(const IpDefaults &d, int b, int n_obst, const double *W, const double *We, const double *r_safe,
+                                                       const double *r_hit, double *tab_w, double *tab_r2, double *tab_rhit)
+{
+#pragma clang fp contract(off)
+    double w[6], we[4];
+    for (int k = 0; k < 6; k++) w[k] = W ? W[(size_t)b * 6 + k] : d.W[k];
+    for (int k = 0; k < 4; k++) we[k] = We ? We[(size_t)b * 4 + k] : d.We[k];
+    double *o = tab_w + (size_t)b * kIpW;
+    o[kIpHs + 0] = d.cs * w[4] + d.lm_stage; o[kIpHs + 1] = d.cs * w[5] + d.lm_stage;
+    o[kIpHs + 2] = d.cs * w[0] + d.lm_stage; o[kIpHs + 3] = d.cs * w[1] + d.lm_stage; o[kIpHs + 4] = d.lm_stage;
+    o[kIpHs + 5] = d.cs * w[2] + d.lm_stage; o[kIpHs + 6] = d.cs * w[3] + d.lm_stage;
+    o[kIpHt + 0] = we[0] + d.lm_term; o[kIpHt + 1] = we[1] + d.lm_term; o[kIpHt + 2] = d.lm_term;
+    o[kIpHt + 3] = we[2] + d.lm_term; o[kIpHt + 4] = we[3] + d.lm_term;
+    for (int k = 0; k < 6; k++) o[kIpWg + k] = d.cs * w[k];
+    for (int k = 0; k < 4; k++) o[kIpWe + k] = we[k];
+    for (int j = 0; j < n_obst; j++) {
+        const size_t e = (size_t)b * n_obst + j;
+        const double rs = r_safe ? r_safe[e] : d.r_safe;
+        tab_r2[e] = rs * rs;
+        tab_rhit[e] = r_hit ? r_hit[e] : (r_safe ? rs - d.hit_off : d.r_hit);
+    }
+}
+
+__global__ void instance_params_kernel(IpDefaults d, int batch, int n_obst, const double *__restrict__ W, const double *__restrict__ We,
+                                       const double *__restrict__ r_safe, const double *__restrict__ r_hit, double *__restrict__ tab_w,
+                                       double *__restrict__ tab_r2, double *__restrict__ tab_rhit)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < batch) derive_instance_params(d, b, n_obst, W, We, r_safe, r_hit, tab_w, tab_r2, tab_rhit);
+}
+
 // Dense dump of the linearisation of the iterate (tests only): same device functions the solve kernel uses.  REF: the gradient against the per-stage
-// reference (KParams::yref) instead of the goal, formed as the REF solve kernels form it
-template <bool REF = false>
+// reference (KParams::yref) instead of the goal, formed as the REF solve kernels form it.  IPAR: the instance's own weights and the obstacles' own radii
+// (KParams::ip_w, ip_r2), on the REF code with the goal as the reference where none is set
+template <bool REF = false, bool IPAR = false>
 __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict__ Xin, const double *__restrict__ Uin,
                                  double *__restrict__ A, double *__restrict__ B, double *__restrict__ b, double *__restrict__ q,
                                  double *__restrict__ hval, double *__restrict__ dh)
@@ -428,6 +472,10 @@ __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict
     for (int c = 0; c < 5; c++) xi[c] = Xg[i * 5 + c];
     const double gx = p.goal[(size_t)inst * 2], gy = p.goal[(size_t)inst * 2 + 1];
     double *qo = q + (size_t)t * 7;
+    static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
+    // IPAR: this instance's weights from its row of the derived table, the goal as the reference where none is set
+    const double *const ipw = IPAR ? p.ip_w + (size_t)inst * kIpW : nullptr;
+    const double gl[2] = {gx, gy};
     if (i < N) {
         ui[0] = Ug[i * 2]; ui[1] = Ug[i * 2 + 1];
         double xn[5], ae[6], be[4];
@@ -441,7 +489,13 @@ __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict
         Ao[2 * 5 + 4] = p.dt;
         Bo[0] = be[0]; Bo[1] = be[1]; Bo[2] = be[2]; Bo[3] = be[3];
         Bo[2 * 2 + 1] = p.h2; Bo[3 * 2 + 0] = p.dt; Bo[4 * 2 + 1] = p.dt;
-        if constexpr (REF) {
+        if constexpr (IPAR) {
+            const double *Wg = ipw + kIpWg;
+            double r[6];
+            load_ref_or_goal<IPAR>(p.yref, p.ref_off, p.ref_T, inst, i, true, gl, r);
+            qo[0] = Wg[4] * (ui[0] - r[4]); qo[1] = Wg[5] * (ui[1] - r[5]);
+            qo[2] = Wg[0] * (xi[0] - r[0]); qo[3] = Wg[1] * (xi[1] - r[1]); qo[4] = 0.0; qo[5] = Wg[2] * (xi[3] - r[2]); qo[6] = Wg[3] * (xi[4] - r[3]);
+        } else if constexpr (REF) {
             double r[6];
             load_ref(p, inst, i, true, r);
             qo[0] = p.Wg[4] * (ui[0] - r[4]); qo[1] = p.Wg[5] * (ui[1] - r[5]);
@@ -450,6 +504,12 @@ __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict
         qo[0] = p.Wg[4] * ui[0]; qo[1] = p.Wg[5] * ui[1];
         qo[2] = p.Wg[0] * (xi[0] - gx); qo[3] = p.Wg[1] * (xi[1] - gy); qo[4] = 0.0; qo[5] = p.Wg[2] * xi[3]; qo[6] = p.Wg[3] * xi[4];
         }
+    } else if constexpr (IPAR) {
+        const double *Weg = ipw + kIpWe;
+        double r[6];
+        load_ref_or_goal<IPAR>(p.yref, p.ref_off, p.ref_T, inst, i, false, gl, r);
+        qo[0] = qo[1] = 0.0;
+        qo[2] = Weg[0] * (xi[0] - r[0]); qo[3] = Weg[1] * (xi[1] - r[1]); qo[4] = 0.0; qo[5] = Weg[2] * (xi[3] - r[2]); qo[6] = Weg[3] * (xi[4] - r[3]);
     } else if constexpr (REF) {
         double r[6];
         load_ref(p, inst, i, false, r);
@@ -462,7 +522,7 @@ __global__ void linearize_kernel(KParams p, int n_obst, const double *__restrict
     const double *Pg = p.P + (size_t)t * n_obst * 2;
     for (int j = 0; j < n_obst; j++) {
         const double ex = xi[0] - Pg[2 * j], ey = xi[1] - Pg[2 * j + 1];
-        hval[(size_t)t * n_obst + j] = ex * ex + ey * ey - p.r2;
+        hval[(size_t)t * n_obst + j] = ex * ex + ey * ey - (IPAR ? p.ip_r2[(size_t)inst * n_obst + j] : p.r2);
         dh[((size_t)t * n_obst + j) * 2] = 2 * ex; dh[((size_t)t * n_obst + j) * 2 + 1] = 2 * ey;
     }
 }

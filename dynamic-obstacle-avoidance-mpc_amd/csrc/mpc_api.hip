@@ -86,6 +86,11 @@ struct mpc_handle {
     double *d_yref_own;               // handle-owned copies of a host reference (mpc_set_reference)
     int32_t *d_ref_off_own;
     size_t yref_own_cap;              // ... capacity of d_yref_own in doubles
+    int ip_mode;                      // per-instance parameters (mpc_set_instance_params[_dev]): 0 off, 1 host arrays (the tables below are final), 2 device arrays
+                                      // (used in place: the tables are derived again in front of every solve, on its stream)
+    int ip_batch;                     // ... the instances they cover (a solve of more is refused)
+    double *d_ip_w, *d_ip_r2, *d_ip_rhit;   // ... the derived tables the IPAR kernels read (KParams::ip_w, ip_r2, ip_rhit), max_batch rows, allocated on first use
+    const double *ip_dev[4];          // ... mode 2: the caller's W, We, r_safe, r_hit (null = the handle's value)
 };
 
 namespace {
@@ -225,7 +230,7 @@ int grant_lds(K kernel, int (&granted)[kMaxDevices], int device, size_t lds)
 // Block-2 (partially condensed) stage recursions: the stage-split mapping on dense blocks, even horizons, all rows of the kernel's capacity in use
 bool use_block2(const mpc_handle *h, bool w2, bool masked) { return h->block2 && !w2 && !masked && (h->cfg.N % 2 == 0) && h->cfg.N >= 4; }
 
-template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false, bool REF = false>
+template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false>
 int launch_split_w(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
     if constexpr (!BLK2 && !W2 && !MASKED && !REF) {
@@ -233,26 +238,26 @@ int launch_split_w(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
     }
     static int granted[kMaxDevices] = {};
     const size_t lds = (size_t)mpc::SplitLds<LPS, NO, W2, BLK2>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF>), dim3(p.batch), dim3(64), lds, s, p);
+    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR>), dim3(p.batch), dim3(64), lds, s, p);
     return MPC_OK;
 }
 
-template <int NO, int LPS, bool REF = false>
+template <int NO, int LPS, bool REF = false, bool IPAR = false>
 int launch_split(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
-    if (p.n_obst != NO) return launch_split_w<NO, LPS, false, true, false, REF>(h, p, s);      // fewer obstacles than rows: the run-time-count variant
-    return pick_waves(h, p.batch) == 2 ? launch_split_w<NO, LPS, true, false, false, REF>(h, p, s) : launch_split_w<NO, LPS, false, false, false, REF>(h, p, s);
+    if (p.n_obst != NO) return launch_split_w<NO, LPS, false, true, false, REF, IPAR>(h, p, s);      // fewer obstacles than rows: the run-time-count variant
+    return pick_waves(h, p.batch) == 2 ? launch_split_w<NO, LPS, true, false, false, REF, IPAR>(h, p, s) : launch_split_w<NO, LPS, false, false, false, REF, IPAR>(h, p, s);
 }
 
 // 11 .. 32 obstacles: one instance per workgroup of WideShape<CAP>::W wavefronts
-template <int CAP, bool MASKED, bool REF = false>
+template <int CAP, bool MASKED, bool REF = false, bool IPAR = false>
 int launch_wide(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
     static int granted[kMaxDevices] = {};
     const size_t lds = (size_t)mpc::WideLds<CAP>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED, REF>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED, REF>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
+    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
     return MPC_OK;
 }
 
@@ -266,12 +271,12 @@ int check_wide(const mpc_handle *h)
     return MPC_OK;
 }
 
-template <int NO, int G, int FACT, bool MASKED = false, bool REF = false>
+template <int NO, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false>
 int launch_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 grid, size_t lds)
 {
     static int granted[kMaxDevices] = {};
-    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF>), grid, dim3(64), lds, s, p);
+    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR>), grid, dim3(64), lds, s, p);
     return MPC_OK;
 }
 
@@ -286,13 +291,17 @@ struct SolvePlan {
 // where the goal path would pack 3 or 4 instances into a wavefront the reference path stays on the split mapping), the multi-wavefront kernel,
 // and one instance per wavefront on compact stage blocks (N > 31, or one lane per stage asked for).  The evidence mappings have none.
 bool ref_active(const mpc_handle *h) { return h->d_yref != nullptr; }
+// Per-instance parameters (mpc_set_instance_params): the IPAR instantiations are the REF ones with one more flag, with or without a reference -- the
+// same mappings, the same plan (plan_solve_ref), the same refusals
+bool ip_active(const mpc_handle *h) { return h->ip_mode != 0; }
 
 int check_ref_mapping(const mpc_handle *h)
 {
-    if (h->use_mfma) return fail(MPC_ERR_ARG, "a per-stage reference does not run with the matrix-core factorisation (mpc_set_matrix_cores)");
-    if (!h->row_parallel) return fail(MPC_ERR_ARG, "a per-stage reference does not run with the systolic sweeps (mpc_set_row_parallel(0))");
-    if (h->block2) return fail(MPC_ERR_ARG, "a per-stage reference does not run with the block-2 recursions (mpc_set_block_riccati)");
-    if (h->lanes_override != 0 && h->lanes_override != 64) return fail(MPC_ERR_ARG, "a per-stage reference runs with one instance per wavefront only (mpc_set_lanes_per_instance 0 or 64)");
+    const char *what = ip_active(h) ? "per-instance parameters" : "a per-stage reference";
+    if (h->use_mfma) return fail(MPC_ERR_ARG, "%s: no build for the matrix-core factorisation (mpc_set_matrix_cores)", what);
+    if (!h->row_parallel) return fail(MPC_ERR_ARG, "%s: no build for the systolic sweeps (mpc_set_row_parallel(0))", what);
+    if (h->block2) return fail(MPC_ERR_ARG, "%s: no build for the block-2 recursions (mpc_set_block_riccati)", what);
+    if (h->lanes_override != 0 && h->lanes_override != 64) return fail(MPC_ERR_ARG, "%s: one instance per wavefront only (mpc_set_lanes_per_instance 0 or 64)", what);
     return MPC_OK;
 }
 
@@ -313,7 +322,7 @@ SolvePlan plan_solve_ref(mpc_handle *h, int batch)
 
 SolvePlan plan_solve(mpc_handle *h, int batch, bool lookahead)
 {
-    if (ref_active(h)) return plan_solve_ref(h, batch);
+    if (ref_active(h) || ip_active(h)) return plan_solve_ref(h, batch);
     SolvePlan q = {1, 1, 64, 2, 0};
     const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
     q.lps = pick_split(h, batch);
@@ -359,39 +368,40 @@ int launch_one_lane_g(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 
     return fail(MPC_ERR_ARG, "no kernel variant for this lane mapping (three instances per wavefront need the row-parallel sweeps)");
 }
 
-// the REF instantiations (plan_solve_ref)
-template <int NO>
+// the REF instantiations (plan_solve_ref), and the IPAR ones built on them
+template <int NO, bool IPAR>
 int launch_ref_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
 {
-    if (p.n_obst != NO) return launch_one_lane<NO, 64, 3, true, true>(h, p, s, dim3(p.batch), q.lds);
-    return launch_one_lane<NO, 64, 3, false, true>(h, p, s, dim3(p.batch), q.lds);
+    if (p.n_obst != NO) return launch_one_lane<NO, 64, 3, true, true, IPAR>(h, p, s, dim3(p.batch), q.lds);
+    return launch_one_lane<NO, 64, 3, false, true, IPAR>(h, p, s, dim3(p.batch), q.lds);
 }
 
+template <bool IPAR>
 int dispatch_solve_ref(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
 {
     int rc = MPC_OK;
     if (wide_rows(h->cfg.n_obst)) {
         rc = check_wide(h); if (rc) return rc;
         const bool masked = partial_rows(h);
-        if (row_capacity(h->cfg.n_obst) == 20) rc = masked ? launch_wide<20, true, true>(h, p, s) : launch_wide<20, false, true>(h, p, s);
-        else rc = masked ? launch_wide<32, true, true>(h, p, s) : launch_wide<32, false, true>(h, p, s);
+        if (row_capacity(h->cfg.n_obst) == 20) rc = masked ? launch_wide<20, true, true, IPAR>(h, p, s) : launch_wide<20, false, true, IPAR>(h, p, s);
+        else rc = masked ? launch_wide<32, true, true, IPAR>(h, p, s) : launch_wide<32, false, true, IPAR>(h, p, s);
     } else if ((rc = check_ref_mapping(h)) != MPC_OK) {
         return rc;
     } else if (q.lps > 1) {
         switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
-        case 32: rc = launch_split<3, 2, true>(h, p, s); break;
-        case 33: rc = launch_split<3, 3, true>(h, p, s); break;
-        case 52: rc = launch_split<5, 2, true>(h, p, s); break;
-        case 53: rc = launch_split<5, 3, true>(h, p, s); break;
-        case 102: rc = launch_split<10, 2, true>(h, p, s); break;
-        case 103: rc = launch_split<10, 3, true>(h, p, s); break;
+        case 32: rc = launch_split<3, 2, true, IPAR>(h, p, s); break;
+        case 33: rc = launch_split<3, 3, true, IPAR>(h, p, s); break;
+        case 52: rc = launch_split<5, 2, true, IPAR>(h, p, s); break;
+        case 53: rc = launch_split<5, 3, true, IPAR>(h, p, s); break;
+        case 102: rc = launch_split<10, 2, true, IPAR>(h, p, s); break;
+        case 103: rc = launch_split<10, 3, true, IPAR>(h, p, s); break;
         default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
         }
     } else {
         switch (row_capacity(h->cfg.n_obst)) {
-        case 3: rc = launch_ref_one_lane<3>(h, p, s, q); break;
-        case 5: rc = launch_ref_one_lane<5>(h, p, s, q); break;
-        case 10: rc = launch_ref_one_lane<10>(h, p, s, q); break;
+        case 3: rc = launch_ref_one_lane<3, IPAR>(h, p, s, q); break;
+        case 5: rc = launch_ref_one_lane<5, IPAR>(h, p, s, q); break;
+        case 10: rc = launch_ref_one_lane<10, IPAR>(h, p, s, q); break;
         default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
         }
     }
@@ -403,7 +413,8 @@ int dispatch_solve_ref(mpc_handle *h, const mpc::KParams &p, hipStream_t s, cons
 // launches the variant the plan names; no event handling here
 int dispatch_solve(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
 {
-    if (p.yref) return dispatch_solve_ref(h, p, s, q);
+    if (p.ip_w) return dispatch_solve_ref<true>(h, p, s, q);
+    if (p.yref) return dispatch_solve_ref<false>(h, p, s, q);
     int rc = MPC_OK;
     if (wide_rows(h->cfg.n_obst)) {
         rc = check_wide(h); if (rc) return rc;
@@ -477,6 +488,47 @@ int launch_schedule(mpc_handle *h, int batch, const int32_t *d_iters, hipStream_
     return MPC_OK;
 }
 
+// The derived per-instance tables (KParams::ip_w, ip_r2, ip_rhit) from the W, We, r_safe, r_hit in effect -- a null group takes the handle's mpc_config value.
+// ONE definition of every derived value for the host and the device (instance_params_kernel): each product and sum is a separately rounded operation,
+// as make_params forms Hd_stage, Hd_term, Wg, Weg and r2 on the host, so a batch that repeats the handle's own values reproduces the handle path bit for bit
+mpc::IpDefaults ip_defaults(const mpc_config &c)
+{
+    mpc::IpDefaults d;
+    const double dt = c.Tf / c.N;
+    d.cs = c.cost_scale_dt ? dt : 1.0;
+    d.lm_stage = c.lm_scaled ? c.lm * dt : c.lm;
+    d.lm_term = c.lm;
+    for (int k = 0; k < 6; k++) d.W[k] = c.W[k];
+    for (int k = 0; k < 4; k++) d.We[k] = c.We[k];
+    d.r_safe = c.r_safe;
+    d.r_hit = 1.0 + 0.2;               // o.r + R_ROBOT, as mpc_closed_loop_step_dev sets it
+    d.hit_off = c.r_safe - d.r_hit;    // r_safe given, r_hit not: r_hit[b][j] = r_safe[b][j] - (cfg.r_safe - 1.2), the handle's margin between the two radii
+    return d;
+}
+
+int alloc_instance_tables(mpc_handle *h)
+{
+    const size_t B = (size_t)h->max_batch, no = (size_t)h->cfg.n_obst;
+    if (!h->d_ip_w) HIPCHK(hipMalloc(&h->d_ip_w, B * mpc::kIpW * sizeof(double)));
+    if (!h->d_ip_r2) HIPCHK(hipMalloc(&h->d_ip_r2, B * no * sizeof(double)));
+    if (!h->d_ip_rhit) HIPCHK(hipMalloc(&h->d_ip_rhit, B * no * sizeof(double)));
+    return MPC_OK;
+}
+
+// in front of a launch that reads the tables: the coverage check, the derivation from device arrays (mode 2), the kernel arguments
+int attach_instance_params(mpc_handle *h, mpc::KParams &p, hipStream_t s)
+{
+    if (!h->ip_mode) return MPC_OK;
+    if (p.batch > h->ip_batch) return fail(MPC_ERR_ARG, "the per-instance parameters set by mpc_set_instance_params cover fewer instances than this solve");
+    if (h->ip_mode == 2) {
+        hipLaunchKernelGGL(mpc::instance_params_kernel, dim3((p.batch + 127) / 128), dim3(128), 0, s, ip_defaults(h->cfg), p.batch, h->cfg.n_obst,
+                           h->ip_dev[0], h->ip_dev[1], h->ip_dev[2], h->ip_dev[3], h->d_ip_w, h->d_ip_r2, h->d_ip_rhit);
+        HIPCHK(hipGetLastError());
+    }
+    p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
+    return MPC_OK;
+}
+
 int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
 {
     p.iters_acc = h->d_iters_acc; p.status_acc = h->d_status_acc;
@@ -485,6 +537,7 @@ int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
     if (h->d_yref && p.batch > h->ref_batch) return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this solve");
     if ((p.fused & MPC_STEP_ADVANCE_REF) && (!h->d_yref || !h->d_ref_off))
         return fail(MPC_ERR_ARG, "MPC_STEP_ADVANCE_REF needs a per-stage reference with offsets (mpc_set_reference[_dev])");
+    int rc_ip = attach_instance_params(h, p, s); if (rc_ip) return rc_ip;
     // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
     if (h->d_alpha && h->d_alpha == h->d_alpha_own && p.batch > h->alpha_batch)
         return fail(MPC_ERR_ARG, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
@@ -603,7 +656,8 @@ int mpc_destroy(mpc_handle *h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
-                    h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own};
+                    h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own,
+                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->h_pack) (void)hipHostFree(h->h_pack);
@@ -767,7 +821,11 @@ int mpc_linearize_dev(mpc_handle *h, int batch, const double *d_x0, const double
     p.x0 = d_x0; p.P = d_P; p.goal = d_goal;
     p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
     const int count = batch * (h->cfg.N + 1);
-    if (h->d_yref)
+    rc = attach_instance_params(h, p, pick(h, stream)); if (rc) return rc;
+    if (p.ip_w)
+        hipLaunchKernelGGL((mpc::linearize_kernel<true, true>), dim3((count + 127) / 128), dim3(128), 0, pick(h, stream), p, h->cfg.n_obst, d_X, d_U,
+                           d_A, d_B, d_b, d_q, d_hval, d_dh);
+    else if (h->d_yref)
         hipLaunchKernelGGL(mpc::linearize_kernel<true>, dim3((count + 127) / 128), dim3(128), 0, pick(h, stream), p, h->cfg.n_obst, d_X, d_U,
                            d_A, d_B, d_b, d_q, d_hval, d_dh);
     else
@@ -1190,6 +1248,48 @@ int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d
     return MPC_OK;
 }
 
+/* ---------------------------------------------- per-instance parameters ---------------------------------------------- */
+
+int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const double *We, const double *r_safe, const double *r_hit)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!W && !We && !r_safe && !r_hit) { h->ip_mode = 0; h->ip_batch = 0; return MPC_OK; }
+    if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "per-instance parameters need batch in [1, max_batch]");
+    const size_t B = (size_t)batch, no = (size_t)h->cfg.n_obst;
+    auto all_in = [](const double *v, size_t n, double lo, bool open) {      // finite and >= lo (open: > lo); NaN fails every comparison
+        if (!v) return true;
+        for (size_t k = 0; k < n; k++)
+            if (!((open ? v[k] > lo : v[k] >= lo) && v[k] <= 1e300)) return false;
+        return true;
+    };
+    if (!all_in(W, B * 6, 0.0, false) || !all_in(We, B * 4, 0.0, false)) return fail(MPC_ERR_ARG, "per-instance weights must be finite and >= 0");
+    if (!all_in(r_safe, B * no, 0.0, true) || !all_in(r_hit, B * no, 0.0, true)) return fail(MPC_ERR_ARG, "per-instance radii must be finite and > 0");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = alloc_instance_tables(h); if (rc) return rc;
+    const mpc::IpDefaults d = ip_defaults(h->cfg);
+    std::vector<double> tw(B * mpc::kIpW), t2(B * no), th(B * no);
+    for (int b = 0; b < batch; b++)
+        mpc::derive_instance_params(d, b, (int)no, W, We, r_safe, r_hit, tw.data(), t2.data(), th.data());
+    HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the tables)
+    HIPCHK(hipMemcpyAsync(h->d_ip_w, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ip_r2, t2.data(), t2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ip_rhit, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->ip_mode = 1; h->ip_batch = batch;
+    return MPC_OK;
+}
+
+int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *d_We, const double *d_r_safe, const double *d_r_hit)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!d_W && !d_We && !d_r_safe && !d_r_hit) { h->ip_mode = 0; h->ip_batch = 0; return MPC_OK; }
+    HIPCHK(hipSetDevice(h->device));
+    int rc = alloc_instance_tables(h); if (rc) return rc;
+    h->ip_dev[0] = d_W; h->ip_dev[1] = d_We; h->ip_dev[2] = d_r_safe; h->ip_dev[3] = d_r_hit;
+    h->ip_mode = 2; h->ip_batch = h->max_batch;
+    return MPC_OK;
+}
+
 /* --------------------------------------------------- measurement --------------------------------------------------- */
 
 int mpc_profile_enable(mpc_handle *h, int on)
@@ -1325,12 +1425,13 @@ int mpc_get_kernel_name(mpc_handle *h, int batch, int lookahead, char *buf, int 
     const char *masked = partial_rows(h) ? "true" : "false";      // (all template arguments, as rocprofv3 prints the instantiation)
     if (wide_rows(h->cfg.n_obst)) {
         const int rc = check_wide(h); if (rc) return rc;
-        snprintf(buf, (size_t)len, ref_active(h) ? "rti_wide_kernel<%d, 2, %s, true>" : "rti_wide_kernel<%d, 2, %s>", cap, masked);
+        snprintf(buf, (size_t)len, ip_active(h) ? "rti_wide_kernel<%d, 2, %s, true, true>" : (ref_active(h) ? "rti_wide_kernel<%d, 2, %s, true>" : "rti_wide_kernel<%d, 2, %s>"), cap, masked);
     }
-    else if (ref_active(h)) {      // (the REF instantiations carry one more template argument)
+    else if (ref_active(h) || ip_active(h)) {      // (the REF instantiations carry one more template argument, the IPAR ones two)
         const int rc = check_ref_mapping(h); if (rc) return rc;
-        if (q.lps > 1) snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, false, true>", cap, q.lps, q.waves == 2 && !partial_rows(h) ? "true" : "false", masked);
-        else snprintf(buf, (size_t)len, "rti_solve_kernel<%d, 64, 3, %s, true>", cap, masked);
+        const char *ip = ip_active(h) ? ", true" : "";
+        if (q.lps > 1) snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, false, true%s>", cap, q.lps, q.waves == 2 && !partial_rows(h) ? "true" : "false", masked, ip);
+        else snprintf(buf, (size_t)len, "rti_solve_kernel<%d, 64, 3, %s, true%s>", cap, masked, ip);
     }
     else if (q.lps > 1) {
         const bool w2 = q.waves == 2 && !partial_rows(h);

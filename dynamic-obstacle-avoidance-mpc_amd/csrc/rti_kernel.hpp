@@ -100,7 +100,18 @@ struct KParams {
     const double *yref;       // [B][ref_T][6], y order (x, y, v, om, ua, ual); stage i uses row min(off + i, ref_T - 1), the terminal stage columns 0..3 of row min(off + N, ref_T - 1)
     int32_t *ref_off;         // [B] row offsets, or null (0); kFuseAdvanceRef adds 1 behind a step
     int ref_T;
+    // ---- per-instance parameters (mpc_set_instance_params; read only by the IPAR instantiations, which read NONE of Hd_stage, Hd_term, Wg, Weg, r2, r_hit above) ----
+    const double *ip_w;       // [B][kIpW]: the derived cost constants of an instance in the order Hd_stage[7], Hd_term[5], Wg[6], Weg[4], rounded as make_params rounds them
+    const double *ip_r2;      // [B][n_obst]: r_safe^2 of obstacle row j (every stage of the instance)
+    const double *ip_rhit;    // [B][n_obst]: hit radius of obstacle j in the fused step's bookkeeping (margin, hit flag)
 };
+
+// Layout of one row of KParams::ip_w
+enum : int { kIpHs = 0, kIpHt = 7, kIpWg = 12, kIpWe = 18, kIpW = 22 };
+// The per-instance tables are never written by a solve kernel: they are read through the constant address space, so that a wave-uniform row (one
+// instance per wavefront or per workgroup in every IPAR mapping) is a handful of scalar loads and the values stay in scalar registers
+typedef const __attribute__((address_space(4))) double IpConst;
+__device__ __forceinline__ IpConst *ip_const(const double *tab, size_t off) { return (IpConst *)(tab + off); }
 
 // Row of the per-stage reference that stage i of instance inst uses: min(off + i, T - 1), floored at 0 (device offsets are not validated; a negative one
 // reads row 0 instead of memory in front of the array)
@@ -120,6 +131,21 @@ __device__ __forceinline__ const double *ref_row(const double *yref, const int32
 __device__ __forceinline__ void load_ref(const KParams &p, int inst, int i, bool has_u, double r[6])
 {
     const double *row = ref_row(p.yref, p.ref_off, p.ref_T, inst, i);
+#pragma unroll
+    for (int c = 0; c < 4; c++) r[c] = row[c];
+    r[4] = has_u ? row[4] : 0.0; r[5] = has_u ? row[5] : 0.0;
+}
+
+// IPAR instantiations are built on the REF code only: without a reference (yref null: a wave-uniform branch) the goal is the reference, (gx, gy, 0, 0, 0, 0),
+// which gives the goal path's gradient bit for bit (v - 0.0 == v)
+template <bool IPAR>
+__device__ __forceinline__ void load_ref_or_goal(const double *yref, const int32_t *off, int T, int inst, int i, bool has_u, const double gl[2], double r[6])
+{
+    if (IPAR && !yref) {
+        r[0] = gl[0]; r[1] = gl[1]; r[2] = r[3] = r[4] = r[5] = 0.0;
+        return;
+    }
+    const double *row = ref_row(yref, off, T, inst, i);
 #pragma unroll
     for (int c = 0; c < 4; c++) r[c] = row[c];
     r[4] = has_u ? row[4] : 0.0; r[5] = has_u ? row[5] : 0.0;
@@ -2100,10 +2126,13 @@ __device__ __forceinline__ void systolic_rollout(int stage, int N, const StageLi
 // MASKED: the problem has p.n_obst < NOBST obstacles (any count the reference's N_OBST may take); the rows of obstacle j >= p.n_obst do not exist
 // (skipped by wave-uniform branches), the input arrays are strided by p.n_obst, and the unused position slots replicate the last obstacle so
 // that everything computed from them stays finite.  Instantiated for one instance per wavefront only; the stage-split kernel takes any count.
-template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false>
+// IPAR: per-instance cost constants and per-obstacle radii (KParams::ip_w, ip_r2, ip_rhit; mpc_set_instance_params) in place of the kernel-argument
+// constants Hd_stage, Hd_term, Wg, Weg, r2, r_hit.  Built on the REF code (load_ref_or_goal), so one family serves solves with and without a reference
+template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false>
 __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 {
     static_assert(!REF || (G == 64 && FACT == 3), "the per-stage reference runs on one instance per wavefront, compact stage blocks");
+    static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
     const int nact = MASKED ? p.n_obst : NOBST;
 #define ROW_OFF(j) (MASKED && (j) >= nact)
 #define OBST_IN(j) (MASKED ? ((j) < nact ? (j) : nact - 1) : (j))
@@ -2147,7 +2176,11 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
                                                                                               // (with ten obstacles these four registers are the difference between 28 and 0 B of scratch)
     // REF: this lane's stage reference, read once and held in vector registers through the interior point (the predictor re-forms the gradient every iteration)
     double yr[REF ? 6 : 1];
-    if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
+    if constexpr (IPAR) load_ref_or_goal<IPAR>(p.yref, p.ref_off, p.ref_T, inst, act ? i : N, has_u, gl, yr);
+    else if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
+    // IPAR: the squared radius of obstacle row j, the same in every lane (one instance per wavefront): a scalar load wherever a row's h is formed
+    IpConst *const ipr2 = IPAR ? ip_const(p.ip_r2, (size_t)inst * nact) : nullptr;
+#define ROW_R2(j) (IPAR ? ipr2[OBST_IN(j)] : p.r2)
     double *Xg = p.X + (size_t)inst * (N + 1) * 5, *Ug = p.U + (size_t)inst * N * 2;
     // episode already finished (goal reached): the instance idles, nothing of it is touched
     const bool ep_done = (p.fused & kFuseMetrics) && p.ep_flags && (p.ep_flags[inst] & 1);
@@ -2365,7 +2398,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
         ObstView v;
         if constexpr (LEAN) {
             const double ex = (xi[0] + zero) - pos_x(j), ey = (xi[1] + zero) - pos_y(j);
-            v.hh = ex * ex + ey * ey - p.r2; v.ax = 2 * ex; v.ay = 2 * ey;
+            v.hh = ex * ex + ey * ey - ROW_R2(j); v.ax = 2 * ex; v.ay = 2 * ey;
             v.rt1 = rcp_nr(t1[j] + zero); v.rt2 = rcp_nr(t2[j] + zero);
         } else { v.hh = hh[j]; v.ax = ax[j]; v.ay = ay[j]; v.rt1 = rt1[j]; v.rt2 = rt2[j]; }
         return v;
@@ -2373,7 +2406,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 #pragma unroll
     for (int j = 0; j < NOBST; j++) {
         const double ex = xi[0] - pos_x(j), ey = xi[1] - pos_y(j);
-        const double h0 = ex * ex + ey * ey - p.r2;
+        const double h0 = ex * ex + ey * ey - ROW_R2(j);
         if (soft) {
             sv[j] = (h0 < 0 ? -h0 : 0.0) + p.thr0;
             t1[j] = fmax(h0 + sv[j], p.thr0);
@@ -2491,6 +2524,18 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
         // scalar copy first -- written as if / else on the argument arrays, the optimiser selects the ADDRESS and issues five
         // per-lane global loads from the kernel-argument segment inside the iteration loop
         double hs[7], ht[5], wg[6], we[4];
+        if constexpr (IPAR) {      // this instance's row of the derived table: scalar loads, like the kernel arguments they replace
+            IpConst *pw = ip_const(p.ip_w, (size_t)inst * kIpW);
+            asm volatile("" : "+s"(pw));
+#pragma unroll
+            for (int c = 0; c < 7; c++) hs[c] = pw[kIpHs + c];
+#pragma unroll
+            for (int c = 0; c < 5; c++) ht[c] = pw[kIpHt + c];
+#pragma unroll
+            for (int c = 0; c < 6; c++) wg[c] = pw[kIpWg + c];
+#pragma unroll
+            for (int c = 0; c < 4; c++) we[c] = pw[kIpWe + c];
+        } else {
 #ifdef MPC_NO_RELOAD
 #pragma unroll
         for (int c = 0; c < 7; c++) { hs[c] = p.Hd_stage[c]; asm volatile("" : "+s"(hs[c])); }
@@ -2512,6 +2557,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 #pragma unroll
         for (int c = 0; c < 4; c++) we[c] = pk->Weg[c];
 #endif
+        }
         Hd[0] = has_u ? hs[0] : 0.0; Hd[1] = has_u ? hs[1] : 0.0;
 #pragma unroll
         for (int c = 0; c < 5; c++) Hd[2 + c] = has_u ? hs[2 + c] : ht[c];
@@ -3366,6 +3412,8 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     int32_t *const t_iters_acc = pt->iters_acc;
     int32_t *const t_status_acc = pt->status_acc;
     const double t_Wg[6] = {pt->Wg[0], pt->Wg[1], pt->Wg[2], pt->Wg[3], pt->Wg[4], pt->Wg[5]}, t_Weg[4] = {pt->Weg[0], pt->Weg[1], pt->Weg[2], pt->Weg[3]};
+    IpConst *const t_ipr2 = IPAR ? ip_const(pt->ip_r2, (size_t)inst * nact) : nullptr;      // (IPAR: the tail's own reads of the per-instance tables)
+    const double *const t_ip_rhit = IPAR ? pt->ip_rhit : nullptr;
     // ---- full step on the iterate; status 4 leaves it unchanged ----
     const bool store = valid && !ep_done;
     status = ipm_finite_step<G>(status, z, lane);
@@ -3419,7 +3467,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
                 if (store && t_obst_rw) { double *w = t_obst_rw + ((size_t)inst * nact + i) * 4; w[0] = ox; w[1] = oy; w[2] = ovx; w[3] = ovy; }
             }
             const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
-            margin = sqrt(ddx * ddx + ddy * ddy) - t_r_hit;  // :222-228
+            margin = sqrt(ddx * ddx + ddy * ddy) - (IPAR ? t_ip_rhit[(size_t)inst * nact + i] : t_r_hit);  // :222-228
         }
         if (t_fused & kFuseMetrics) {
             margin = -seg_max<G>(-margin, lane);
@@ -3441,14 +3489,23 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     if (t_cost) {
         double J = 0.0;
         if (REF && act) {
+            if constexpr (IPAR) {
+                double r[6];
+                load_ref_or_goal<IPAR>(pt->yref, pt->ref_off, pt->ref_T, inst, i, has_u, gl, r);
+                IpConst *pw = ip_const(pt->ip_w, (size_t)inst * kIpW);
+                const double wg[6] = {pw[kIpWg], pw[kIpWg + 1], pw[kIpWg + 2], pw[kIpWg + 3], pw[kIpWg + 4], pw[kIpWg + 5]};
+                const double we[4] = {pw[kIpWe], pw[kIpWe + 1], pw[kIpWe + 2], pw[kIpWe + 3]};
+                J = ls_cost_ref(wg, we, xi, ui, r, has_u);
+            } else {
             const double *row = ref_row(pt->yref, pt->ref_off, pt->ref_T, inst, i);
             const double r[6] = {row[0], row[1], row[2], row[3], has_u ? row[4] : 0.0, has_u ? row[5] : 0.0};
             J = ls_cost_ref(t_Wg, t_Weg, xi, ui, r, has_u);
+            }
 #pragma unroll
             for (int j = 0; j < NOBST; j++) {
                 if (ROW_OFF(j)) continue;
                 const double dx = xi[0] - pos_x(j), dy = xi[1] - pos_y(j);
-                const double hv = dx * dx + dy * dy - t_r2;
+                const double hv = dx * dx + dy * dy - (IPAR ? t_ipr2[OBST_IN(j)] : t_r2);
                 const double v = hv < 0 ? -hv : 0.0;
                 J += zpen * (v + 0.5 * v * v);
             }
@@ -3481,5 +3538,6 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 }
 #undef ROW_OFF
 #undef OBST_IN
+#undef ROW_R2
 
 }  // namespace mpc

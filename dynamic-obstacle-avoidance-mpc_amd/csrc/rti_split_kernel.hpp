@@ -57,10 +57,13 @@ __device__ __forceinline__ double nth_of_six(double a0, double a1, double a2, do
 // MASKED: fewer obstacles than row pairs (p.n_obst < NOBST, see rti_solve_kernel): a template flag, because with the count known at compile time
 // the per-slot row flags fold into the stage flags (measured: the run-time count costs 1 % at C2)
 // BLK2: the stage recursions run on PAIRS of stages (Blk2Lds / rowpar_factor2, rti_kernel.hpp): even horizons, dense blocks, one wavefront per SIMD
-template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false>
+// IPAR: per-instance cost constants and per-obstacle radii (KParams::ip_w, ip_r2, ip_rhit; mpc_set_instance_params) in place of the kernel-argument
+// constants Hd_stage, Hd_term, Wg, Weg, r2, r_hit.  Built on the REF code (load_ref_or_goal), so one family serves solves with and without a reference
+template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false>
 __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 {
     static_assert(!REF || !BLK2, "the per-stage reference is not built for the block-2 recursions");
+    static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
     static_assert(LPS == 2 || LPS == 3, "two or three lanes per horizon stage");
     static_assert(!BLK2 || !W2, "the block-2 recursions exist on the dense layout only");
     using SL = SplitLds<LPS, NOBST, W2, BLK2>;
@@ -307,7 +310,13 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     double ll[NBL], tl[NBL], lh[NBL], th[NBL], rtl[NBL], rth[NBL], zs[NBL];
     // REF: this lane's stage reference, needed only here (gc0 carries it through the interior point); the cost at the end reads it again
     double yr[REF ? 6 : 1];
-    if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
+    if constexpr (IPAR) load_ref_or_goal<IPAR>(p.yref, p.ref_off, p.ref_T, inst, act ? i : N, has_u, gl, yr);
+    else if constexpr (REF) load_ref(p, inst, act ? i : N, has_u, yr);
+    // IPAR: this instance's row of the derived cost table, the same in every lane (scalar loads)
+    IpConst *const ipw = IPAR ? ip_const(p.ip_w, (size_t)__builtin_amdgcn_readfirstlane(inst) * kIpW) : nullptr;
+    // ... and the squared radius of the obstacle of row slot s (rows beyond the count replicate the last obstacle, as their positions do): read where it is
+    // used, here and in the cost at the end, not carried in between
+#define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + ((s) * LPS + h < nact ? (s) * LPS + h : nact - 1)] : p.r2)
     {
         auto slot_init = [&](auto sc) {     // slot index as a compile-time constant
             constexpr int s = decltype(sc)::value;
@@ -316,11 +325,22 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             const double hi = part_of(sc, p.bu_hi[0], p.bu_hi[1], p.bx_hi[0], p.bx_hi[1], p.bx_hi[2], p.bx_hi[3]);
             const bool is_u = part_of(sc, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0) != 0.0;
             bp[s] = act && (is_u ? has_u : xb);
-            hd[s] = part_of(sc, has_u ? p.Hd_stage[0] : 0.0, has_u ? p.Hd_stage[1] : 0.0, has_u ? p.Hd_stage[2] : p.Hd_term[0],
-                            has_u ? p.Hd_stage[3] : p.Hd_term[1], has_u ? p.Hd_stage[5] : p.Hd_term[3], has_u ? p.Hd_stage[6] : p.Hd_term[4]);
+            // (IPAR in branches of their own, statement for statement: wrapped in one expression with the kernel arguments, or in another order, the arguments'
+            // arm compiles to differently scheduled code in the instantiations that were there before)
+            if constexpr (IPAR)
+                hd[s] = part_of(sc, has_u ? ipw[kIpHs + 0] : 0.0, has_u ? ipw[kIpHs + 1] : 0.0, has_u ? ipw[kIpHs + 2] : ipw[kIpHt + 0],
+                                has_u ? ipw[kIpHs + 3] : ipw[kIpHt + 1], has_u ? ipw[kIpHs + 5] : ipw[kIpHt + 3], has_u ? ipw[kIpHs + 6] : ipw[kIpHt + 4]);
+            else
+                hd[s] = part_of(sc, has_u ? p.Hd_stage[0] : 0.0, has_u ? p.Hd_stage[1] : 0.0, has_u ? p.Hd_stage[2] : p.Hd_term[0],
+                                has_u ? p.Hd_stage[3] : p.Hd_term[1], has_u ? p.Hd_stage[5] : p.Hd_term[3], has_u ? p.Hd_stage[6] : p.Hd_term[4]);
             hq[s] = (is_u && !has_u) ? 1.0 : hd[s];       // the terminal stage has no inputs: unit block keeps Muu regular
-            const double wg = part_of(sc, has_u ? p.Wg[4] : 0.0, has_u ? p.Wg[5] : 0.0, has_u ? p.Wg[0] : p.Weg[0], has_u ? p.Wg[1] : p.Weg[1],
-                                      has_u ? p.Wg[2] : p.Weg[2], has_u ? p.Wg[3] : p.Weg[3]);
+            double wg;
+            if constexpr (IPAR)
+                wg = part_of(sc, has_u ? ipw[kIpWg + 4] : 0.0, has_u ? ipw[kIpWg + 5] : 0.0, has_u ? ipw[kIpWg + 0] : ipw[kIpWe + 0], has_u ? ipw[kIpWg + 1] : ipw[kIpWe + 1],
+                             has_u ? ipw[kIpWg + 2] : ipw[kIpWe + 2], has_u ? ipw[kIpWg + 3] : ipw[kIpWe + 3]);
+            else
+                wg = part_of(sc, has_u ? p.Wg[4] : 0.0, has_u ? p.Wg[5] : 0.0, has_u ? p.Wg[0] : p.Weg[0], has_u ? p.Wg[1] : p.Weg[1],
+                             has_u ? p.Wg[2] : p.Weg[2], has_u ? p.Wg[3] : p.Weg[3]);
             if constexpr (REF) gc0[s] = wg * (val - part_of(sc, yr[4], yr[5], yr[0], yr[1], yr[2], yr[3]));
             else gc0[s] = wg * (val - part_of(sc, 0.0, 0.0, gl[0], gl[1], 0.0, 0.0));
             cl0[s] = val - lo; ch0[s] = hi - val;
@@ -334,7 +354,10 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         slot_init(std::integral_constant<int, 1>{});
         if constexpr (NBL > 2) slot_init(std::integral_constant<int, 2>{});
     }
-    const double hd_psi = has_u ? p.Hd_stage[4] : p.Hd_term[2];
+    double hd_psi_;
+    if constexpr (IPAR) hd_psi_ = has_u ? ipw[kIpHs + 4] : ipw[kIpHt + 2];
+    else hd_psi_ = has_u ? p.Hd_stage[4] : p.Hd_term[2];
+    const double hd_psi = hd_psi_;
     // ---- this lane's obstacle rows (slot s <-> obstacle j = s * LPS + part): rho1 = h + a'dx + s >= 0 (lam1, t1), rho2 = s >= 0
     //      (lam2, t2); robot_model.py:60-65 ----
     bool sp[NSL];
@@ -343,7 +366,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     for (int s = 0; s < NSL; s++) {
         sp[s] = vs && (s * LPS + h < nact);
         const double ex = xi[0] - pxy[s][0], ey = xi[1] - pxy[s][1];
-        hh[s] = ex * ex + ey * ey - p.r2; ax[s] = 2 * ex; ay[s] = 2 * ey;
+        hh[s] = ex * ex + ey * ey - ROW_R2(s); ax[s] = 2 * ex; ay[s] = 2 * ey;
         if (soft) {
             sv[s] = (hh[s] < 0 ? -hh[s] : 0.0) + p.thr0;
             t1[s] = fmax(hh[s] + sv[s], p.thr0);
@@ -1102,7 +1125,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
                 if (store && p.obst_rw) { double *w = p.obst_rw + ((size_t)inst * nact + lane) * 4; w[0] = ox; w[1] = oy; w[2] = ovx; w[3] = ovy; }
             }
             const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
-            margin = sqrt(ddx * ddx + ddy * ddy) - p.r_hit;  // :222-228
+            margin = sqrt(ddx * ddx + ddy * ddy) - (IPAR ? p.ip_rhit[(size_t)inst * nact + lane] : p.r_hit);  // :222-228
         }
         if (p.fused & kFuseMetrics) {
             margin = -seg_max<64>(-margin, lane);
@@ -1124,7 +1147,13 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     if (p.cost) {
         double J = 0.0;
         if (act) {
-            if (REF && own) {
+            if (IPAR && own) {
+                double r[6];
+                load_ref_or_goal<IPAR>(p.yref, p.ref_off, p.ref_T, inst, i, has_u, gl, r);
+                const double wg[6] = {ipw[kIpWg], ipw[kIpWg + 1], ipw[kIpWg + 2], ipw[kIpWg + 3], ipw[kIpWg + 4], ipw[kIpWg + 5]};      // (read again: not carried)
+                const double we[4] = {ipw[kIpWe], ipw[kIpWe + 1], ipw[kIpWe + 2], ipw[kIpWe + 3]};
+                J = ls_cost_ref(wg, we, xi, ui, r, has_u);
+            } else if (REF && own) {
                 const double *row = ref_row(p.yref, p.ref_off, p.ref_T, inst, i);
                 const double r[6] = {row[0], row[1], row[2], row[3], has_u ? row[4] : 0.0, has_u ? row[5] : 0.0};
                 J = ls_cost_ref(p.Wg, p.Weg, xi, ui, r, has_u);
@@ -1137,7 +1166,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 #pragma unroll
             for (int s = 0; s < NSL; s++) if (s * LPS + h < nact) {
                 const double dx = xi[0] - pxy[s][0], dy = xi[1] - pxy[s][1];
-                const double hv = dx * dx + dy * dy - p.r2;
+                const double hv = dx * dx + dy * dy - ROW_R2(s);
                 const double v = hv < 0 ? -hv : 0.0;
                 J += zpen * (v + 0.5 * v * v);
             }
@@ -1160,5 +1189,6 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     if (p.trace && lane == 0) { for (int k = 0; k < 16; k++) p.trace[((size_t)inst * p.iter_max) * 4 + k] = (double)tacc_[k]; }
 #endif
 }
+#undef ROW_R2
 
 }  // namespace mpc

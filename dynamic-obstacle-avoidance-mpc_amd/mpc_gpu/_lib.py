@@ -66,6 +66,8 @@ SYMBOLS = {
     "mpc_set_slack_schedule_dev": (C.c_int, [_vp, _vp]),
     "mpc_set_reference": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "mpc_set_reference_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "mpc_set_instance_params": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "mpc_set_instance_params_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mpc_plant_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "mpc_predict": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "mpc_solve_dev": (C.c_int, [_vp, C.c_int] + [_vp] * 10),

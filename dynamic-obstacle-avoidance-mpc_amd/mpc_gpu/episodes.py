@@ -18,7 +18,7 @@ from .solver import BatchedMpc
 
 def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, init_guess_when_error=True,
                  bug_compat_alias=True, seed=0, device=0, solver=None, n_obst=5, first_seed=0, record=False, noise=None,
-                 interpolate_init=False, status_log=False, compact_from=4096, **cfg):
+                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, **cfg):
     """x0 (B,5), goal (B,2), obst (B,n_obst,4) -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): instance s then starts
     from the reference generator's draw for np.random.seed(first_seed + s), produced on the device (experiments.py:26-29).
     record=True also returns simX (steps+1,B,5), obst_traj (steps+1,B,n_obst,4) and pred (steps,B,N+1,5): what the reference keeps
@@ -37,6 +37,9 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     have finished, their results are parked and the live ones move together (device-side gathers, one host read of the count).  Each episode's arithmetic is
     its own: results are those of the uncompacted run, bit for bit where an instance's result does not depend on its wavefront neighbours (one instance
     per wavefront) and to the rounding of the wavefront sums otherwise (three per wavefront).  Off with record / status_log; None: never.
+    r_safe, r_hit: optional per-instance radii, (B, n_obst) or (B,) (BatchedMpc.set_instance_params): obstacle j of episode b keeps the robot
+    r_safe[b, j] away and counts as hit within r_hit[b, j] (default r_safe[b, j] - (cfg.r_safe - 1.2)).  The scenario generators draw no radii (they
+    are pinned to the reference's streams): drawing them is the caller's business.  Episodes with radii of their own are not compacted.
     Returns dict(table (B,6), x_last (B,5), steps_run, solves)."""
     import torch
     x0 = np.ascontiguousarray(x0, dtype=np.float64); B = x0.shape[0]
@@ -57,6 +60,9 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     goal = np.ascontiguousarray(np.broadcast_to(goal, (B, 2)), dtype=np.float64)
     dev = torch.device("cuda", device)
     m = solver or BatchedMpc(N, n_obst, Tf, max_batch=B, device=device, **cfg)
+    own_radii = r_safe is not None or r_hit is not None
+    if own_radii:
+        m.set_instance_params(r_safe=r_safe, r_hit=r_hit)
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
         t = lambda a: torch.from_numpy(a.copy()).to(dev)
@@ -96,7 +102,7 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             dnoise = torch.from_numpy(noise).to(dev)
         k = 0
         # compaction of finished episodes (compact_from): results of parked episodes live in full-size arrays, `ids` maps the live batch to them
-        compact = compact_from is not None and B >= compact_from and not record and not status_log
+        compact = compact_from is not None and B >= compact_from and not record and not status_log and not own_radii
         B0 = B
         if compact:
             ids = torch.arange(B, device=dev)
@@ -160,6 +166,8 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             extra.update(status2=n2.cpu().numpy(), status4=n4.cpu().numpy(), first_bad=first_bad.cpu().numpy())
     if solver is None:
         m.close()
+    elif own_radii:
+        m.set_instance_params()      # (a caller's solver leaves as it came)
     return dict(table=table, x_last=xl, steps_run=k, solves=int(steps.sum().item()) + int((fl_h & 1).sum()), **extra)
 
 

@@ -95,6 +95,12 @@ class PipelinedMpc:
         for lo, hi, m, _ in self.parts:
             m.set_reference(None if yref is None else yref[lo:hi], None if yref is None else self._sl(offset, lo, hi))
 
+    def set_instance_params_dev(self, W=None, We=None, r_safe=None, r_hit=None):
+        """per-instance weights and per-obstacle radii (BatchedMpc.set_instance_params) from device tensors (max_batch, 6), (max_batch, 4),
+        (max_batch, n_obst), (max_batch, n_obst): every sub-handle gets its contiguous slice, used in place; all None switches the feature off"""
+        for lo, hi, m, _ in self.parts:
+            m.set_instance_params(self._sl(W, lo, hi), self._sl(We, lo, hi), self._sl(r_safe, lo, hi), self._sl(r_hit, lo, hi))
+
     # ------------------------------------------------------------------ the cost exchange lives on the first sub-batch's handle (include/mpc_gpu.h mpc_comm_*)
     def comm_init(self, rank, world, unique_id):
         self.parts[0][2].comm_init(rank, world, unique_id)

@@ -160,6 +160,46 @@ class BatchedMpc:
                 raise ValueError(f"device offsets must be a contiguous int32 tensor ({self.max_batch},)")
             _lib.check(_lib.lib().mpc_set_reference_dev(self._h, int(yref.shape[1]), _ptr(yref), _ptr(offset)))
 
+    def _instance_arrays(self, W, We, r_safe, r_hit):
+        """host arrays of set_instance_params in the C layout: (B, 6), (B, 4), (B, n_obst), (B, n_obst); r_safe / r_hit of shape (B,) mean one radius
+        per instance (every obstacle of it); all of one batch size.  None stays None."""
+        out, B = [], None
+        for name, a, cols in (("W", W, 6), ("We", We, 4), ("r_safe", r_safe, self.n_obst), ("r_hit", r_hit, self.n_obst)):
+            if a is not None:
+                a = np.asarray(a, dtype=np.float64)
+                if a.ndim == 1 and name in ("r_safe", "r_hit"):
+                    a = np.repeat(a[:, None], self.n_obst, axis=1)
+                a = _f64(a)
+                if a.ndim != 2 or a.shape[1] != cols:
+                    raise ValueError(f"{name} must be (B, {cols})" + (" or (B,)" if name in ("r_safe", "r_hit") else "") + f", got {a.shape}")
+                if B is not None and a.shape[0] != B:
+                    raise ValueError(f"{name} has {a.shape[0]} rows, the arrays before it {B}")
+                B = a.shape[0]
+            out.append(a)
+        return out, B
+
+    def set_instance_params(self, W=None, We=None, r_safe=None, r_hit=None):
+        """Per-instance cost weights and per-obstacle radii (include/mpc_gpu.h mpc_set_instance_params): instance b solves with W[b] (6,) and We[b] (4,)
+        in the order of mpc_config.W / .We, obstacle j of it with the safety radius r_safe[b, j] and, in the fused step's bookkeeping, the hit radius
+        r_hit[b, j] (default r_safe[b, j] - (cfg.r_safe - 1.2)).  A group left None keeps the handle's value; all None switches the feature off.
+        numpy arrays (B, 6), (B, 4), (B, n_obst) -- r_safe and r_hit also (B,), one radius per instance -- are validated and copied; device tensors
+        (max_batch, ...) of exactly the C shapes are used in place (the values they hold when a solve is launched).  Not both kinds in one call."""
+        given = [a for a in (W, We, r_safe, r_hit) if a is not None]
+        if not given:
+            _lib.check(_lib.lib().mpc_set_instance_params(self._h, 0, None, None, None, None))
+            return
+        host = [isinstance(a, (np.ndarray, list, tuple)) for a in given]
+        if all(host):
+            (W, We, r_safe, r_hit), B = self._instance_arrays(W, We, r_safe, r_hit)
+            _lib.check(_lib.lib().mpc_set_instance_params(self._h, B, _ptr(W), _ptr(We), _ptr(r_safe), _ptr(r_hit)))
+        elif not any(host):
+            for name, a, cols in (("W", W, 6), ("We", We, 4), ("r_safe", r_safe, self.n_obst), ("r_hit", r_hit, self.n_obst)):
+                if a is not None and (tuple(a.shape) != (self.max_batch, cols) or str(a.dtype) != "torch.float64" or not a.is_contiguous()):
+                    raise ValueError(f"a device {name} must be a contiguous float64 tensor ({self.max_batch}, {cols})")
+            _lib.check(_lib.lib().mpc_set_instance_params_dev(self._h, _ptr(W), _ptr(We), _ptr(r_safe), _ptr(r_hit)))
+        else:
+            raise ValueError("per-instance parameters: host arrays or device tensors, not both in one call")
+
     def plant_step(self, x, u):
         """ocp_integrator set/solve/get, robot_ocp_problem.py:207-212."""
         x = _f64(np.atleast_2d(x)); u = _f64(np.atleast_2d(u), (x.shape[0], 2))

@@ -172,6 +172,24 @@ int mpc_set_slack_schedule_dev(mpc_handle *h, const double *d_alpha);
 int mpc_set_reference(mpc_handle *h, int batch, int T, const double *yref, const int32_t *offset);
 int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d_offset);
 
+/* Per-instance cost weights and per-obstacle radii: W[batch][6] and We[batch][4] in the order of mpc_config.W / .We, r_safe[batch][n_obst] and
+ * r_hit[batch][n_obst].  Any pointer may be NULL: that group keeps the handle's mpc_config value; all four NULL switch the feature off and the handle
+ * runs the kernels it ran before.  Instance b then solves with its own weights (gradient, Hessian diagonal, reported cost, stationarity residual,
+ * q of mpc_linearize_dev), obstacle row j of every stage of instance b reads h = |p - o_j|^2 - r_safe[b][j]^2 (hval of mpc_linearize_dev, the penalty
+ * in the reported cost), and the episode bookkeeping of mpc_closed_loop_step_dev (margin, hit flag) uses r_hit[b][j] for obstacle j in place of its
+ * constant 1.2.  With r_safe given and r_hit NULL, r_hit[b][j] = r_safe[b][j] - (cfg.r_safe - 1.2): the handle's margin between the two radii is kept.
+ * The Levenberg-Marquardt term, cost_scale_dt / lm_scaled, bounds, slack schedule and tolerances stay per handle.
+ * Host arrays, validated (finite, weights >= 0, radii > 0, batch in [1, max_batch]; MPC_ERR_ARG otherwise) and copied; applies to every following
+ * solve (mpc_solve, mpc_solve_obst, mpc_solve_dev, mpc_closed_loop_step_dev, mpc_linearize_dev) of the first `batch` instances until replaced.
+ * Works together with mpc_set_reference, with explicit P, with the in-kernel look-ahead and with every flag of the fused step.
+ * _dev: device arrays of max_batch rows, used in place and not validated: the values they hold when a solve is launched are the ones it uses (a small
+ * kernel in front of each solve, on the solve's stream, forms the derived constants with the host's rounding).
+ * The mappings are those of a per-stage reference: the stage-split kernel for N <= 31 at every batch size, one instance per wavefront on compact
+ * stage blocks beyond, the multi-wavefront kernel for more than 10 obstacles; with mpc_set_matrix_cores(1), mpc_set_row_parallel(0),
+ * mpc_set_block_riccati(1) or lanes per instance 16, 21 or 32 a solve returns MPC_ERR_ARG while the feature is on. */
+int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const double *We, const double *r_safe, const double *r_hit);
+int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *d_We, const double *d_r_safe, const double *d_r_hit);
+
 /* Plant integrator, ocp_integrator.set/solve/get, robot_ocp_problem.py:207-212 (same IRK as the OCP) */
 int mpc_plant_step(mpc_handle *h, int batch, const double *x, const double *u, double *x_next);
 /* Obstacle look-ahead only: obst[B][n_obst][4] -> P[B][N+1][n_obst][2] (visualization.py:62-79) */

@@ -3,8 +3,8 @@
 Usage: python scripts/compare_listings.py OLD.s NEW.s
 Every kernel present in both listings must have the same instructions once label numbers, comments and directives that only name
 sections or sizes are ignored.  Kernels only in NEW (new instantiations) are listed; kernels only in OLD are an error.  Exit 1 on any difference.
-A kernel that gained a trailing `bool` template parameter whose default (false) keeps the old code -- the REF parameter of the per-stage reference --
-is matched to its old name: rti_*_kernel<..., false> and linearize_kernel<false>.
+A kernel that gained a trailing `bool` template parameter whose default (false) keeps the old code -- the REF parameter of the per-stage reference,
+the IPAR parameter of the per-instance parameters -- is matched to its old name: rti_*_kernel<..., false> and linearize_kernel<..., false>.
 """
 import re
 import sys
@@ -50,8 +50,8 @@ def new_name(k, b):
     """the NEW symbol of OLD kernel k: itself, or its instantiation with one more template argument `false`"""
     if k in b:
         return k
-    if k.endswith("EEEvNS_7KParamsE"):                  # rti_*_kernel<...>(KParams) -> rti_*_kernel<..., false>
-        c = k[:-len("EEEvNS_7KParamsE")] + "ELb0EEEvNS_7KParamsE"
+    if "EEEvNS_7KParamsE" in k:                         # rti_*_kernel<...>(KParams), linearize_kernel<...>(KParams, ...) -> the same with <..., false>
+        c = k.replace("EEEvNS_7KParamsE", "ELb0EEEvNS_7KParamsE", 1)
         if c in b:
             return c
     m = re.match(r"^(_ZN3mpc\d+\w+?)E(NS_7KParamsE.*)$", k)   # a non-template kernel that became a template: match on the base name
