@@ -91,6 +91,11 @@ struct mpc_handle {
     int ip_batch;                     // ... the instances they cover (a solve of more is refused)
     double *d_ip_w, *d_ip_r2, *d_ip_rhit;   // ... the derived tables the IPAR kernels read (KParams::ip_w, ip_r2, ip_rhit), max_batch rows, allocated on first use
     const double *ip_dev[4];          // ... mode 2: the caller's W, We, r_safe, r_hit (null = the handle's value)
+    bool ip_default;                  // ... the tables hold the handle's own mpc_config values in all max_batch rows (what an obstacle mask without instance parameters reads)
+    int om_mode;                      // per-instance obstacle masks (mpc_set_obstacle_mask[_dev]): 0 off, 1 host words (copied to d_omask_own), 2 device words (used in place)
+    int om_batch;                     // ... the instances they cover (a solve of more is refused)
+    const uint32_t *d_omask;          // ... the words the OSEL kernels read (KParams::omask)
+    uint32_t *d_omask_own;            // ... handle-owned copy of host words, max_batch, allocated on first use
 };
 
 namespace {
@@ -158,7 +163,8 @@ hipStream_t pick(mpc_handle *h, void *stream) { return stream ? (hipStream_t)str
 // Lanes per instance of the one-lane-per-stage mapping: the smallest of {16, 32, 64} with N + 1 < G (an idle lane separates instances that
 // share a wavefront), or 21 -- three instances per wavefront on compact LDS blocks -- for 16 <= N <= 20 once pick_split hands a large batch
 // to this mapping; unless overridden.  Packing instances into one wavefront multiplies throughput for large batches.
-bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst; }
+// (an obstacle mask is a run-time row count by nature: with one set, a handle whose count fills its capacity runs the run-time-count variants too)
+bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || h->om_mode != 0; }
 
 int pick_lanes(mpc_handle *h, int batch)
 {
@@ -230,7 +236,7 @@ int grant_lds(K kernel, int (&granted)[kMaxDevices], int device, size_t lds)
 // Block-2 (partially condensed) stage recursions: the stage-split mapping on dense blocks, even horizons, all rows of the kernel's capacity in use
 bool use_block2(const mpc_handle *h, bool w2, bool masked) { return h->block2 && !w2 && !masked && (h->cfg.N % 2 == 0) && h->cfg.N >= 4; }
 
-template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false>
+template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false>
 int launch_split_w(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
     if constexpr (!BLK2 && !W2 && !MASKED && !REF) {
@@ -238,8 +244,8 @@ int launch_split_w(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
     }
     static int granted[kMaxDevices] = {};
     const size_t lds = (size_t)mpc::SplitLds<LPS, NO, W2, BLK2>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR>), dim3(p.batch), dim3(64), lds, s, p);
+    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR, OSEL>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR, OSEL>), dim3(p.batch), dim3(64), lds, s, p);
     return MPC_OK;
 }
 
@@ -251,13 +257,13 @@ int launch_split(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 }
 
 // 11 .. 32 obstacles: one instance per workgroup of WideShape<CAP>::W wavefronts
-template <int CAP, bool MASKED, bool REF = false, bool IPAR = false>
+template <int CAP, bool MASKED, bool REF = false, bool IPAR = false, bool OSEL = false>
 int launch_wide(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
 {
     static int granted[kMaxDevices] = {};
     const size_t lds = (size_t)mpc::WideLds<CAP>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
+    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR, OSEL>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR, OSEL>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
     return MPC_OK;
 }
 
@@ -271,12 +277,12 @@ int check_wide(const mpc_handle *h)
     return MPC_OK;
 }
 
-template <int NO, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false>
+template <int NO, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false>
 int launch_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 grid, size_t lds)
 {
     static int granted[kMaxDevices] = {};
-    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR>), grid, dim3(64), lds, s, p);
+    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR, OSEL>, granted, h->device, lds); if (rc) return rc;
+    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR, OSEL>), grid, dim3(64), lds, s, p);
     return MPC_OK;
 }
 
@@ -294,10 +300,13 @@ bool ref_active(const mpc_handle *h) { return h->d_yref != nullptr; }
 // Per-instance parameters (mpc_set_instance_params): the IPAR instantiations are the REF ones with one more flag, with or without a reference -- the
 // same mappings, the same plan (plan_solve_ref), the same refusals
 bool ip_active(const mpc_handle *h) { return h->ip_mode != 0; }
+// Per-instance obstacle masks (mpc_set_obstacle_mask): the OSEL instantiations are the IPAR ones with a run-time row count and one more flag -- again the
+// same mappings, plan and refusals; without instance parameters the tables they read hold the handle's own values
+bool om_active(const mpc_handle *h) { return h->om_mode != 0; }
 
 int check_ref_mapping(const mpc_handle *h)
 {
-    const char *what = ip_active(h) ? "per-instance parameters" : "a per-stage reference";
+    const char *what = om_active(h) ? "an obstacle mask" : (ip_active(h) ? "per-instance parameters" : "a per-stage reference");
     if (h->use_mfma) return fail(MPC_ERR_ARG, "%s: no build for the matrix-core factorisation (mpc_set_matrix_cores)", what);
     if (!h->row_parallel) return fail(MPC_ERR_ARG, "%s: no build for the systolic sweeps (mpc_set_row_parallel(0))", what);
     if (h->block2) return fail(MPC_ERR_ARG, "%s: no build for the block-2 recursions (mpc_set_block_riccati)", what);
@@ -322,7 +331,7 @@ SolvePlan plan_solve_ref(mpc_handle *h, int batch)
 
 SolvePlan plan_solve(mpc_handle *h, int batch, bool lookahead)
 {
-    if (ref_active(h) || ip_active(h)) return plan_solve_ref(h, batch);
+    if (ref_active(h) || ip_active(h) || om_active(h)) return plan_solve_ref(h, batch);
     SolvePlan q = {1, 1, 64, 2, 0};
     const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
     q.lps = pick_split(h, batch);
@@ -410,9 +419,43 @@ int dispatch_solve_ref(mpc_handle *h, const mpc::KParams &p, hipStream_t s, cons
     return MPC_OK;
 }
 
+// the OSEL instantiations (plan_solve_ref): the run-time-count variant of every family
+int dispatch_solve_osel(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
+{
+    int rc = MPC_OK;
+    if (wide_rows(h->cfg.n_obst)) {
+        rc = check_wide(h); if (rc) return rc;
+        if (row_capacity(h->cfg.n_obst) == 20) rc = launch_wide<20, true, true, true, true>(h, p, s);
+        else rc = launch_wide<32, true, true, true, true>(h, p, s);
+    } else if ((rc = check_ref_mapping(h)) != MPC_OK) {
+        return rc;
+    } else if (q.lps > 1) {
+        switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
+        case 32: rc = launch_split_w<3, 2, false, true, false, true, true, true>(h, p, s); break;
+        case 33: rc = launch_split_w<3, 3, false, true, false, true, true, true>(h, p, s); break;
+        case 52: rc = launch_split_w<5, 2, false, true, false, true, true, true>(h, p, s); break;
+        case 53: rc = launch_split_w<5, 3, false, true, false, true, true, true>(h, p, s); break;
+        case 102: rc = launch_split_w<10, 2, false, true, false, true, true, true>(h, p, s); break;
+        case 103: rc = launch_split_w<10, 3, false, true, false, true, true, true>(h, p, s); break;
+        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
+        }
+    } else {
+        switch (row_capacity(h->cfg.n_obst)) {
+        case 3: rc = launch_one_lane<3, 64, 3, true, true, true, true>(h, p, s, dim3(p.batch), q.lds); break;
+        case 5: rc = launch_one_lane<5, 64, 3, true, true, true, true>(h, p, s, dim3(p.batch), q.lds); break;
+        case 10: rc = launch_one_lane<10, 64, 3, true, true, true, true>(h, p, s, dim3(p.batch), q.lds); break;
+        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
+        }
+    }
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 // launches the variant the plan names; no event handling here
 int dispatch_solve(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
 {
+    if (p.omask) return dispatch_solve_osel(h, p, s, q);
     if (p.ip_w) return dispatch_solve_ref<true>(h, p, s, q);
     if (p.yref) return dispatch_solve_ref<false>(h, p, s, q);
     int rc = MPC_OK;
@@ -515,6 +558,39 @@ int alloc_instance_tables(mpc_handle *h)
     return MPC_OK;
 }
 
+// the handle's own values in every row of the tables: what a solve with an obstacle mask and without instance parameters reads.  A host call (it
+// waits for the handle's stream); made where the mask is set and where instance parameters are switched off under a mask, never in front of a solve
+int fill_default_instance_tables(mpc_handle *h)
+{
+    if (h->ip_default) return MPC_OK;
+    int rc = alloc_instance_tables(h); if (rc) return rc;
+    const size_t B = (size_t)h->max_batch, no = (size_t)h->cfg.n_obst;
+    const mpc::IpDefaults d = ip_defaults(h->cfg);
+    std::vector<double> tw(B * mpc::kIpW), t2(B * no), th(B * no);
+    for (int b = 0; b < h->max_batch; b++)
+        mpc::derive_instance_params(d, b, (int)no, nullptr, nullptr, nullptr, nullptr, tw.data(), t2.data(), th.data());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ip_w, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ip_r2, t2.data(), t2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ip_rhit, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->ip_default = true;
+    return MPC_OK;
+}
+
+// in front of a solve: the obstacle mask's coverage check and kernel argument (with it, the tables are attached whether or not instance parameters are set)
+int attach_obstacle_mask(mpc_handle *h, mpc::KParams &p)
+{
+    if (!h->om_mode) return MPC_OK;
+    if (p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
+    if (!h->ip_mode) {
+        if (!h->ip_default) return fail(MPC_ERR_ARG, "internal: the default instance tables of the obstacle mask are not filled");
+        p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
+    }
+    p.omask = h->d_omask;
+    return MPC_OK;
+}
+
 // in front of a launch that reads the tables: the coverage check, the derivation from device arrays (mode 2), the kernel arguments
 int attach_instance_params(mpc_handle *h, mpc::KParams &p, hipStream_t s)
 {
@@ -538,6 +614,7 @@ int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
     if ((p.fused & MPC_STEP_ADVANCE_REF) && (!h->d_yref || !h->d_ref_off))
         return fail(MPC_ERR_ARG, "MPC_STEP_ADVANCE_REF needs a per-stage reference with offsets (mpc_set_reference[_dev])");
     int rc_ip = attach_instance_params(h, p, s); if (rc_ip) return rc_ip;
+    rc_ip = attach_obstacle_mask(h, p); if (rc_ip) return rc_ip;
     // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
     if (h->d_alpha && h->d_alpha == h->d_alpha_own && p.batch > h->alpha_batch)
         return fail(MPC_ERR_ARG, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
@@ -657,7 +734,7 @@ int mpc_destroy(mpc_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
                     h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own,
-                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit};
+                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->h_pack) (void)hipHostFree(h->h_pack);
@@ -1253,7 +1330,11 @@ int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d
 int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const double *We, const double *r_safe, const double *r_hit)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!W && !We && !r_safe && !r_hit) { h->ip_mode = 0; h->ip_batch = 0; return MPC_OK; }
+    if (!W && !We && !r_safe && !r_hit) {
+        h->ip_mode = 0; h->ip_batch = 0;
+        if (h->om_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
+        return MPC_OK;
+    }
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "per-instance parameters need batch in [1, max_batch]");
     const size_t B = (size_t)batch, no = (size_t)h->cfg.n_obst;
     auto all_in = [](const double *v, size_t n, double lo, bool open) {      // finite and >= lo (open: > lo); NaN fails every comparison
@@ -1271,6 +1352,7 @@ int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const dou
     for (int b = 0; b < batch; b++)
         mpc::derive_instance_params(d, b, (int)no, W, We, r_safe, r_hit, tw.data(), t2.data(), th.data());
     HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the tables)
+    h->ip_default = false;
     HIPCHK(hipMemcpyAsync(h->d_ip_w, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_ip_r2, t2.data(), t2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_ip_rhit, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1282,11 +1364,47 @@ int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const dou
 int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *d_We, const double *d_r_safe, const double *d_r_hit)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!d_W && !d_We && !d_r_safe && !d_r_hit) { h->ip_mode = 0; h->ip_batch = 0; return MPC_OK; }
+    if (!d_W && !d_We && !d_r_safe && !d_r_hit) {
+        h->ip_mode = 0; h->ip_batch = 0;
+        if (h->om_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
+        return MPC_OK;
+    }
     HIPCHK(hipSetDevice(h->device));
     int rc = alloc_instance_tables(h); if (rc) return rc;
+    h->ip_default = false;
     h->ip_dev[0] = d_W; h->ip_dev[1] = d_We; h->ip_dev[2] = d_r_safe; h->ip_dev[3] = d_r_hit;
     h->ip_mode = 2; h->ip_batch = h->max_batch;
+    return MPC_OK;
+}
+
+/* ---------------------------------------------- per-instance obstacle masks ---------------------------------------------- */
+
+int mpc_set_obstacle_mask(mpc_handle *h, int batch, const uint32_t *mask)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!mask) { h->om_mode = 0; h->om_batch = 0; h->d_omask = nullptr; return MPC_OK; }
+    if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "an obstacle mask needs batch in [1, max_batch]");
+    const int no = h->cfg.n_obst;
+    const uint32_t legal = no >= 32 ? 0xffffffffu : ((1u << no) - 1u);
+    for (int b = 0; b < batch; b++)
+        if (mask[b] & ~legal) return fail(MPC_ERR_ARG, "an obstacle mask word has a bit at or above n_obst");
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->d_omask_own) HIPCHK(hipMalloc(&h->d_omask_own, (size_t)h->max_batch * sizeof(uint32_t)));
+    if (!h->ip_mode) { int rc = fill_default_instance_tables(h); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the words)
+    HIPCHK(hipMemcpyAsync(h->d_omask_own, mask, (size_t)batch * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->d_omask = h->d_omask_own; h->om_mode = 1; h->om_batch = batch;
+    return MPC_OK;
+}
+
+int mpc_set_obstacle_mask_dev(mpc_handle *h, const uint32_t *d_mask)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!d_mask) { h->om_mode = 0; h->om_batch = 0; h->d_omask = nullptr; return MPC_OK; }
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->ip_mode) { int rc = fill_default_instance_tables(h); if (rc) return rc; }
+    h->d_omask = d_mask; h->om_mode = 2; h->om_batch = h->max_batch;
     return MPC_OK;
 }
 
@@ -1425,11 +1543,12 @@ int mpc_get_kernel_name(mpc_handle *h, int batch, int lookahead, char *buf, int 
     const char *masked = partial_rows(h) ? "true" : "false";      // (all template arguments, as rocprofv3 prints the instantiation)
     if (wide_rows(h->cfg.n_obst)) {
         const int rc = check_wide(h); if (rc) return rc;
-        snprintf(buf, (size_t)len, ip_active(h) ? "rti_wide_kernel<%d, 2, %s, true, true>" : (ref_active(h) ? "rti_wide_kernel<%d, 2, %s, true>" : "rti_wide_kernel<%d, 2, %s>"), cap, masked);
+        snprintf(buf, (size_t)len, om_active(h) ? "rti_wide_kernel<%d, 2, %s, true, true, true>" :
+                 (ip_active(h) ? "rti_wide_kernel<%d, 2, %s, true, true>" : (ref_active(h) ? "rti_wide_kernel<%d, 2, %s, true>" : "rti_wide_kernel<%d, 2, %s>")), cap, masked);
     }
-    else if (ref_active(h) || ip_active(h)) {      // (the REF instantiations carry one more template argument, the IPAR ones two)
+    else if (ref_active(h) || ip_active(h) || om_active(h)) {      // (the REF instantiations carry one more template argument, the IPAR ones two, the OSEL ones three)
         const int rc = check_ref_mapping(h); if (rc) return rc;
-        const char *ip = ip_active(h) ? ", true" : "";
+        const char *ip = om_active(h) ? ", true, true" : (ip_active(h) ? ", true" : "");
         if (q.lps > 1) snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, false, true%s>", cap, q.lps, q.waves == 2 && !partial_rows(h) ? "true" : "false", masked, ip);
         else snprintf(buf, (size_t)len, "rti_solve_kernel<%d, 64, 3, %s, true%s>", cap, masked, ip);
     }

@@ -55,7 +55,8 @@ enum : int {
     kFuseAliasBug = 16,    // ... which in the reference also zeroes the plant's v, omega (defect D2, :301-302)
     kFuseMetrics = 32,     // episode bookkeeping of RobotOcpProblem.step (:213-250)
     kFuseInterpGuess = 64, // ... and that set_initial_guess() is the straight-line variant the reference keeps commented out (:293-300, interp_guess below)
-    kFuseAdvanceRef = 128  // per-stage reference: offset[inst] += 1 for every instance that stepped (mpc_set_reference; REF instantiations only)
+    kFuseAdvanceRef = 128, // per-stage reference: offset[inst] += 1 for every instance that stepped (mpc_set_reference; REF instantiations only)
+    kFuseMarginAll = 256   // obstacle masks: the margin and the hit flag count every obstacle, absent ones included (mpc_set_obstacle_mask; OSEL instantiations only)
 };
 
 struct KParams {
@@ -104,6 +105,8 @@ struct KParams {
     const double *ip_w;       // [B][kIpW]: the derived cost constants of an instance in the order Hd_stage[7], Hd_term[5], Wg[6], Weg[4], rounded as make_params rounds them
     const double *ip_r2;      // [B][n_obst]: r_safe^2 of obstacle row j (every stage of the instance)
     const double *ip_rhit;    // [B][n_obst]: hit radius of obstacle j in the fused step's bookkeeping (margin, hit flag)
+    // ---- per-instance obstacle masks (mpc_set_obstacle_mask; read only by the OSEL instantiations) ----
+    const uint32_t *omask;    // [B]: bit j set = obstacle j of the instance exists (bits at and above n_obst are ignored)
 };
 
 // Layout of one row of KParams::ip_w
@@ -112,6 +115,13 @@ enum : int { kIpHs = 0, kIpHt = 7, kIpWg = 12, kIpWe = 18, kIpW = 22 };
 // instance per wavefront or per workgroup in every IPAR mapping) is a handful of scalar loads and the values stay in scalar registers
 typedef const __attribute__((address_space(4))) double IpConst;
 __device__ __forceinline__ IpConst *ip_const(const double *tab, size_t off) { return (IpConst *)(tab + off); }
+// The obstacle mask of an instance (KParams::omask), read the same way: `inst` is wave-uniform in every OSEL mapping, so this is one scalar load.  Bits at
+// and above the obstacle count are dropped here (the device form of the setter is not validated: no index formed from the word leaves the arrays)
+__device__ __forceinline__ uint32_t omask_word(const uint32_t *tab, int inst, int nact)
+{
+    const uint32_t w = ((const __attribute__((address_space(4))) uint32_t *)tab)[inst];
+    return nact >= 32 ? w : (w & ((1u << nact) - 1u));
+}
 
 // Row of the per-stage reference that stage i of instance inst uses: min(off + i, T - 1), floored at 0 (device offsets are not validated; a negative one
 // reads row 0 instead of memory in front of the array)
@@ -2128,14 +2138,22 @@ __device__ __forceinline__ void systolic_rollout(int stage, int N, const StageLi
 // that everything computed from them stays finite.  Instantiated for one instance per wavefront only; the stage-split kernel takes any count.
 // IPAR: per-instance cost constants and per-obstacle radii (KParams::ip_w, ip_r2, ip_rhit; mpc_set_instance_params) in place of the kernel-argument
 // constants Hd_stage, Hd_term, Wg, Weg, r2, r_hit.  Built on the REF code (load_ref_or_goal), so one family serves solves with and without a reference
-template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false>
+// OSEL: per-instance obstacle masks (KParams::omask; mpc_set_obstacle_mask): the rows of obstacle j exist iff bit j of the instance's word is set; an absent
+// slot replicates the highest present obstacle (zero with an empty word), as the slots beyond the count replicate the last one.  Built on the MASKED IPAR code
+template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false>
 __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 {
     static_assert(!REF || (G == 64 && FACT == 3), "the per-stage reference runs on one instance per wavefront, compact stage blocks");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
+    static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
     const int nact = MASKED ? p.n_obst : NOBST;
-#define ROW_OFF(j) (MASKED && (j) >= nact)
-#define OBST_IN(j) (MASKED ? ((j) < nact ? (j) : nact - 1) : (j))
+    // OSEL: the instance's word and the obstacle an absent slot reads in its place (set below, once the instance is known); OSEL_POS: a position read
+    // through OBST_IN, the origin with an empty word (there is no obstacle to stand in)
+    uint32_t omask = 0u;
+    int osub = 0;
+#define ROW_OFF(j) (OSEL ? (((omask >> (j)) & 1u) == 0u) : (MASKED && (j) >= nact))
+#define OBST_IN(j) (OSEL ? ((((omask >> (j)) & 1u) != 0u) ? (j) : osub) : (MASKED ? ((j) < nact ? (j) : nact - 1) : (j)))
+#define OSEL_POS(v) ((OSEL && omask == 0u) ? 0.0 : (v))
     constexpr bool USE_MFMA = FACT == 1, ROWPAR = FACT >= 2, COMPACT = FACT == 3;
     // five and more obstacle pairs: recomputable row state is not carried (see obst_view below).  Measured per obstacle count (scripts/ab_workload.py,
     // 65536 random scenarios): 3 obstacles -4.6 % (their state fits the registers: recomputing only adds instructions), 5 obstacles +8 % at N = 20 and
@@ -2160,6 +2178,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     // the exec restore of an if / else join (scripts/isa_audit.py rule P1) -- scalar spills (v_writelane) ignore EXEC
     if constexpr (G == 64) inst_ = __builtin_amdgcn_readfirstlane(inst_);
     const int inst = inst_;
+    if constexpr (OSEL) { omask = omask_word(p.omask, inst, nact); osub = 31 - __builtin_clz(omask | 1u); }
     const int N = p.N;
     const int i = lane - slot * G;            // this lane's stage
     const bool act = (i <= N);
@@ -2209,13 +2228,13 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
             if (act) {
                 const double *Pg = p.P + ((size_t)inst * (N + 1) + i) * nact * 2;
 #pragma unroll
-                for (int e = 0; e < 2 * NOBST; e++) Pl[i * NOBST * 2 + e] = Pg[2 * OBST_IN(e >> 1) + (e & 1)];
+                for (int e = 0; e < 2 * NOBST; e++) Pl[i * NOBST * 2 + e] = OSEL_POS(Pg[2 * OBST_IN(e >> 1) + (e & 1)]);
             }
         } else if (2 * NOBST <= G) {
             if (i < 2 * NOBST) {   // lane i walks coordinate i & 1 of obstacle i >> 1 through the horizon (Obstacle.predict_trajectory, visualization.py:62-79)
                 const int j = OBST_IN(i >> 1), c = i & 1;
                 const double *o = p.obst + ((size_t)inst * nact + j) * 4;
-                double q = o[c], v = (c == 0 && !p.world.bug_compat_predict) ? o[2] : o[3];      // defect D1: vx = self.vy (:69)
+                double q = OSEL_POS(o[c]), v = OSEL_POS((c == 0 && !p.world.bug_compat_predict) ? o[2] : o[3]);      // defect D1: vx = self.vy (:69)
                 const double lo = c ? p.world.ymin : p.world.xmin, hi = c ? p.world.ymax : p.world.xmax;
                 Pl[i] = q;
                 for (int k = 1; k <= N; k++) {
@@ -2225,8 +2244,8 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
             }
         } else if (i < NOBST) {       // lane j = i walks obstacle j through the horizon
             const double *o = p.obst + ((size_t)inst * nact + OBST_IN(i)) * 4;
-            double ox = o[0], oy = o[1], ovy = o[3];
-            double ovx = p.world.bug_compat_predict ? o[3] : o[2];
+            double ox = OSEL_POS(o[0]), oy = OSEL_POS(o[1]), ovy = OSEL_POS(o[3]);
+            double ovx = OSEL_POS(p.world.bug_compat_predict ? o[3] : o[2]);
             Pl[i * 2] = ox; Pl[i * 2 + 1] = oy;
             for (int k = 1; k <= N; k++) {
                 obstacle_advance(p.world, dt, ox, ovx, oy, ovy);
@@ -2242,7 +2261,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     } else {
         const double *Pg = p.P + ((size_t)inst * (N + 1) + (act ? i : 0)) * nact * 2;
 #pragma unroll
-        for (int j = 0; j < NOBST; j++) { pxy[j][0] = act ? Pg[2 * OBST_IN(j)] : 0.0; pxy[j][1] = act ? Pg[2 * OBST_IN(j) + 1] : 0.0; }
+        for (int j = 0; j < NOBST; j++) { pxy[j][0] = act ? OSEL_POS(Pg[2 * OBST_IN(j)]) : 0.0; pxy[j][1] = act ? OSEL_POS(Pg[2 * OBST_IN(j) + 1]) : 0.0; }
     }
     // position of obstacle j at this lane's stage
     auto pos_x = [&](int j) { if constexpr (PLDS) return myP[2 * j]; else return pxy[j][0]; };
@@ -2422,7 +2441,8 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     int n_items_lane = 0;
 #pragma unroll
     for (int k = 0; k < NB; k++) n_items_lane += ((k < 2) ? vbu : vbx) ? 2 : 0;
-    n_items_lane += vs ? (soft ? 2 * nact : nact) : 0;
+    if constexpr (OSEL) n_items_lane += vs ? (soft ? 2 * __builtin_popcount(omask) : __builtin_popcount(omask)) : 0;
+    else n_items_lane += vs ? (soft ? 2 * nact : nact) : 0;
     const double n_items = seg_sum<G>((double)n_items_lane, lane);
     double inv_items = n_items > 0 ? 1.0 / n_items : 0.0;
     if constexpr (G == 64) inv_items = wave_uniform(inv_items);
@@ -3468,6 +3488,9 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
             }
             const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
             margin = sqrt(ddx * ddx + ddy * ddy) - (IPAR ? t_ip_rhit[(size_t)inst * nact + i] : t_r_hit);  // :222-228
+            if constexpr (OSEL) {       // an absent obstacle moves, but is not counted (kFuseMarginAll: it is)
+                if (ROW_OFF(i) && !(t_fused & kFuseMarginAll)) margin = INFINITY;
+            }
         }
         if (t_fused & kFuseMetrics) {
             margin = -seg_max<G>(-margin, lane);
@@ -3538,6 +3561,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 }
 #undef ROW_OFF
 #undef OBST_IN
+#undef OSEL_POS
 #undef ROW_R2
 
 }  // namespace mpc

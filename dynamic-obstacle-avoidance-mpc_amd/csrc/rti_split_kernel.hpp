@@ -59,9 +59,13 @@ __device__ __forceinline__ double nth_of_six(double a0, double a1, double a2, do
 // BLK2: the stage recursions run on PAIRS of stages (Blk2Lds / rowpar_factor2, rti_kernel.hpp): even horizons, dense blocks, one wavefront per SIMD
 // IPAR: per-instance cost constants and per-obstacle radii (KParams::ip_w, ip_r2, ip_rhit; mpc_set_instance_params) in place of the kernel-argument
 // constants Hd_stage, Hd_term, Wg, Weg, r2, r_hit.  Built on the REF code (load_ref_or_goal), so one family serves solves with and without a reference
-template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false>
+// OSEL: per-instance obstacle masks (KParams::omask; mpc_set_obstacle_mask): obstacle j of the instance exists iff bit j of its word is set.  "j < nact"
+// becomes the bit test wherever a row, a cost term or a margin depends on it; the position and radius of an absent slot are those of the highest present
+// obstacle (zero with an empty word), so nothing an absent entry of P / obst holds is ever read into the row state.  Built on the MASKED IPAR code
+template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false>
 __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 {
+    static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
     static_assert(!REF || !BLK2, "the per-stage reference is not built for the block-2 recursions");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
     static_assert(LPS == 2 || LPS == 3, "two or three lanes per horizon stage");
@@ -77,6 +81,13 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     const int i = lane / LPS;                 // this lane's stage
     const int h = lane - i * LPS;             // ... and its part of the stage's rows
     const bool own = (h == 0);                // the part that stages the stage's blocks in LDS and stores the iterate
+    // OSEL: this instance's word, the same in every lane (a scalar load), and the obstacle an absent slot reads in its place
+    uint32_t omask = 0u;
+    if constexpr (OSEL) omask = omask_word(p.omask, __builtin_amdgcn_readfirstlane(inst), nact);
+    const int osub = OSEL ? 31 - __builtin_clz(omask | 1u) : 0;
+    // obstacle j exists for this instance / the obstacle whose position and radius row slot j reads
+#define OBST_ON(j) (OSEL ? (((omask >> (j)) & 1u) != 0u) : ((j) < nact))
+#define OBST_IN(j) (OSEL ? ((((omask >> (j)) & 1u) != 0u) ? (j) : osub) : ((j) < nact ? (j) : nact - 1))
     const bool act = (i <= N);
     const bool has_u = (i < N);
     const bool xb = (i >= 1) && (i < N || (i == N && p.bx_terminal));
@@ -173,16 +184,22 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     if (p.obst) {       // (two branches, not a select between an LDS and a global pointer: that would be a flat load)
 #pragma unroll
         for (int s = 0; s < NSL; s++) {
-            const int j = s * LPS + h, jj = j < nact ? j : nact - 1;
+            const int j = s * LPS + h, jj = OBST_IN(j);
             const double *src = lds_P + ((act ? i : 0) * NOBST + jj) * 2;
             pxy[s][0] = src[0]; pxy[s][1] = src[1];
         }
     } else {
 #pragma unroll
         for (int s = 0; s < NSL; s++) {
-            const int j = s * LPS + h, jj = j < nact ? j : nact - 1;
+            const int j = s * LPS + h, jj = OBST_IN(j);
             const double *src = p.P + (((size_t)inst * (N + 1) + (act ? i : 0)) * nact + jj) * 2;
             pxy[s][0] = src[0]; pxy[s][1] = src[1];
+        }
+    }
+    if constexpr (OSEL) {       // an empty word: no obstacle to stand in, the slots read as the origin
+        if (omask == 0u) {
+#pragma unroll
+            for (int s = 0; s < NSL; s++) { pxy[s][0] = 0.0; pxy[s][1] = 0.0; }
         }
     }
     const bool ep_done = (ep_word & 1) != 0;
@@ -316,7 +333,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     IpConst *const ipw = IPAR ? ip_const(p.ip_w, (size_t)__builtin_amdgcn_readfirstlane(inst) * kIpW) : nullptr;
     // ... and the squared radius of the obstacle of row slot s (rows beyond the count replicate the last obstacle, as their positions do): read where it is
     // used, here and in the cost at the end, not carried in between
-#define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + ((s) * LPS + h < nact ? (s) * LPS + h : nact - 1)] : p.r2)
+#define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + (OSEL ? OBST_IN((s) * LPS + h) : ((s) * LPS + h < nact ? (s) * LPS + h : nact - 1))] : p.r2)
     {
         auto slot_init = [&](auto sc) {     // slot index as a compile-time constant
             constexpr int s = decltype(sc)::value;
@@ -364,7 +381,8 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     double hh[NSL], ax[NSL], ay[NSL], sv[NSL], l1[NSL], t1[NSL], l2[NSL], t2[NSL], rt1[NSL], rt2[NSL];
 #pragma unroll
     for (int s = 0; s < NSL; s++) {
-        sp[s] = vs && (s * LPS + h < nact);
+        if constexpr (OSEL) sp[s] = vs && OBST_ON(s * LPS + h);
+        else sp[s] = vs && (s * LPS + h < nact);
         const double ex = xi[0] - pxy[s][0], ey = xi[1] - pxy[s][1];
         hh[s] = ex * ex + ey * ey - ROW_R2(s); ax[s] = 2 * ex; ay[s] = 2 * ey;
         if (soft) {
@@ -1126,6 +1144,9 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             }
             const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
             margin = sqrt(ddx * ddx + ddy * ddy) - (IPAR ? p.ip_rhit[(size_t)inst * nact + lane] : p.r_hit);  // :222-228
+            if constexpr (OSEL) {       // an absent obstacle moves, but is not counted (kFuseMarginAll: it is)
+                if (!OBST_ON(lane) && !(p.fused & kFuseMarginAll)) margin = INFINITY;
+            }
         }
         if (p.fused & kFuseMetrics) {
             margin = -seg_max<64>(-margin, lane);
@@ -1164,7 +1185,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
                 else J = 0.5 * (p.Weg[0] * ex * ex + p.Weg[1] * ey * ey + p.Weg[2] * xi[3] * xi[3] + p.Weg[3] * xi[4] * xi[4]);
             }
 #pragma unroll
-            for (int s = 0; s < NSL; s++) if (s * LPS + h < nact) {
+            for (int s = 0; s < NSL; s++) if (OBST_ON(s * LPS + h)) {
                 const double dx = xi[0] - pxy[s][0], dy = xi[1] - pxy[s][1];
                 const double hv = dx * dx + dy * dy - ROW_R2(s);
                 const double v = hv < 0 ? -hv : 0.0;
@@ -1190,5 +1211,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 #endif
 }
 #undef ROW_R2
+#undef OBST_ON
+#undef OBST_IN
 
 }  // namespace mpc

@@ -60,9 +60,11 @@ __device__ __forceinline__ void group_sync()
 
 // MASKED: fewer obstacles than row pairs (p.n_obst < CAP): the run-time count, as in rti_split_kernel
 // IPAR: per-instance cost constants and per-obstacle radii, as in rti_split_kernel (built on the REF code)
-template <int CAP, int LPS, bool MASKED = false, bool REF = false, bool IPAR = false>
+// OSEL: per-instance obstacle masks, as in rti_split_kernel (the word is the same in every wavefront of the workgroup)
+template <int CAP, int LPS, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false>
 __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(const KParams p)
 {
+    static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
     static_assert(LPS == 2, "two lanes per horizon stage (N <= 31)");
     constexpr int W = WideShape<CAP>::W, KW = WideShape<CAP>::K;
@@ -79,6 +81,12 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     const int i = lane / LPS;
     const int h = lane - i * LPS;
     const bool own = (h == 0);
+    // OSEL: this instance's word (a scalar load) and the obstacle an absent slot reads in its place
+    uint32_t omask = 0u;
+    if constexpr (OSEL) omask = omask_word(p.omask, __builtin_amdgcn_readfirstlane(inst), nact);
+    const int osub = OSEL ? 31 - __builtin_clz(omask | 1u) : 0;
+#define OBST_ON(j) (OSEL ? (((omask >> (j)) & 1u) != 0u) : ((j) < nact))
+#define OBST_IN(j) (OSEL ? ((((omask >> (j)) & 1u) != 0u) ? (j) : osub) : ((j) < nact ? (j) : nact - 1))
     const bool act = (i <= N);
     const bool has_u = (i < N);
     const bool xb = (i >= 1) && (i < N || (i == N && p.bx_terminal));
@@ -160,16 +168,22 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     if (p.obst) {
 #pragma unroll
         for (int s = 0; s < NSL; s++) {
-            const int j = wv * KW + s * LPS + h, jj = j < nact ? j : nact - 1;
+            const int j = wv * KW + s * LPS + h, jj = OBST_IN(j);
             const double *src = lds_P + ((act ? i : 0) * CAP + jj) * 2;
             pxy[s][0] = src[0]; pxy[s][1] = src[1];
         }
     } else {
 #pragma unroll
         for (int s = 0; s < NSL; s++) {
-            const int j = wv * KW + s * LPS + h, jj = j < nact ? j : nact - 1;
+            const int j = wv * KW + s * LPS + h, jj = OBST_IN(j);
             const double *src = p.P + (((size_t)inst * (N + 1) + (act ? i : 0)) * nact + jj) * 2;
             pxy[s][0] = src[0]; pxy[s][1] = src[1];
+        }
+    }
+    if constexpr (OSEL) {       // an empty word: no obstacle to stand in, the slots read as the origin
+        if (omask == 0u) {
+#pragma unroll
+            for (int s = 0; s < NSL; s++) { pxy[s][0] = 0.0; pxy[s][1] = 0.0; }
         }
     }
     const bool ep_done = (ep_word & 1) != 0;
@@ -236,7 +250,7 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     // IPAR: this instance's row of the derived cost table, the same in every lane of the workgroup (scalar loads)
     IpConst *const ipw = IPAR ? ip_const(p.ip_w, (size_t)__builtin_amdgcn_readfirstlane(inst) * kIpW) : nullptr;
     // ... and the squared radius of the obstacle of row slot s of this wavefront (rows beyond the count replicate the last obstacle, as their positions do)
-#define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + (wv * KW + (s) * LPS + h < nact ? wv * KW + (s) * LPS + h : nact - 1)] : p.r2)
+#define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + (OSEL ? OBST_IN(wv * KW + (s) * LPS + h) : (wv * KW + (s) * LPS + h < nact ? wv * KW + (s) * LPS + h : nact - 1))] : p.r2)
     {
         auto slot_init = [&](auto sc) {
             constexpr int s = decltype(sc)::value;
@@ -283,7 +297,8 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     double hh[NSL], ax[NSL], ay[NSL], sv[NSL], l1[NSL], t1[NSL], l2[NSL], t2[NSL], rt1[NSL], rt2[NSL];
 #pragma unroll
     for (int s = 0; s < NSL; s++) {
-        sp[s] = vs && (wv * KW + s * LPS + h < nact);
+        if constexpr (OSEL) sp[s] = vs && OBST_ON(wv * KW + s * LPS + h);
+        else sp[s] = vs && (wv * KW + s * LPS + h < nact);
         const double ex = xi[0] - pxy[s][0], ey = xi[1] - pxy[s][1];
         hh[s] = ex * ex + ey * ey - ROW_R2(s); ax[s] = 2 * ex; ay[s] = 2 * ey;
         if (soft) {
@@ -823,7 +838,7 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
                 else J = 0.5 * (p.Weg[0] * ex * ex + p.Weg[1] * ey * ey + p.Weg[2] * xi[3] * xi[3] + p.Weg[3] * xi[4] * xi[4]);
             }
 #pragma unroll
-            for (int s = 0; s < NSL; s++) if (wv * KW + s * LPS + h < nact) {
+            for (int s = 0; s < NSL; s++) if (OBST_ON(wv * KW + s * LPS + h)) {
                 const double dx = xi[0] - pxy[s][0], dy = xi[1] - pxy[s][1];
                 const double hv = dx * dx + dy * dy - ROW_R2(s);
                 const double v = hv < 0 ? -hv : 0.0;
@@ -857,6 +872,9 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
             }
             const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
             margin = sqrt(ddx * ddx + ddy * ddy) - (IPAR ? p.ip_rhit[(size_t)inst * nact + lane] : p.r_hit);
+            if constexpr (OSEL) {       // an absent obstacle moves, but is not counted (kFuseMarginAll: it is)
+                if (!OBST_ON(lane) && !(p.fused & kFuseMarginAll)) margin = INFINITY;
+            }
         }
         if (p.fused & kFuseMetrics) {
             margin = -seg_max<64>(-margin, lane);
@@ -885,5 +903,7 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     }
 }
 #undef ROW_R2
+#undef OBST_ON
+#undef OBST_IN
 
 }  // namespace mpc

@@ -19,6 +19,7 @@ REPO_ROOT = os.path.dirname(PKG_ROOT)
 MPC_OK, MPC_ERR_ARG, MPC_ERR_HIP, MPC_ERR_NODEVICE = 0, -1, -2, -3
 STEP_SHIFT, STEP_PLANT, STEP_OBSTACLES, STEP_RESET_ON_FAIL, STEP_ALIAS_BUG, STEP_METRICS, STEP_INTERP_GUESS = 1, 2, 4, 8, 16, 32, 64
 STEP_ADVANCE_REF = 128
+STEP_MARGIN_ALL = 256
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
 
@@ -68,6 +69,8 @@ SYMBOLS = {
     "mpc_set_reference_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "mpc_set_instance_params": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_set_instance_params_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mpc_set_obstacle_mask": (C.c_int, [_vp, C.c_int, _vp]),
+    "mpc_set_obstacle_mask_dev": (C.c_int, [_vp, _vp]),
     "mpc_plant_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "mpc_predict": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "mpc_solve_dev": (C.c_int, [_vp, C.c_int] + [_vp] * 10),

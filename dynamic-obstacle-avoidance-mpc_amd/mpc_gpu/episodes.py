@@ -18,7 +18,7 @@ from .solver import BatchedMpc
 
 def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, init_guess_when_error=True,
                  bug_compat_alias=True, seed=0, device=0, solver=None, n_obst=5, first_seed=0, record=False, noise=None,
-                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, **cfg):
+                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, active=None, margin_all=False, **cfg):
     """x0 (B,5), goal (B,2), obst (B,n_obst,4) -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): instance s then starts
     from the reference generator's draw for np.random.seed(first_seed + s), produced on the device (experiments.py:26-29).
     record=True also returns simX (steps+1,B,5), obst_traj (steps+1,B,n_obst,4) and pred (steps,B,N+1,5): what the reference keeps
@@ -40,6 +40,9 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     r_safe, r_hit: optional per-instance radii, (B, n_obst) or (B,) (BatchedMpc.set_instance_params): obstacle j of episode b keeps the robot
     r_safe[b, j] away and counts as hit within r_hit[b, j] (default r_safe[b, j] - (cfg.r_safe - 1.2)).  The scenario generators draw no radii (they
     are pinned to the reference's streams): drawing them is the caller's business.  Episodes with radii of their own are not compacted.
+    active: optional bool (B, n_obst) (BatchedMpc.set_obstacle_mask): obstacle j exists for episode b only where active[b, j]; the absent ones still
+    move (and draw their noise) but are neither solved against nor, unless margin_all, counted in the margin and the hit flag.  Masked episodes are
+    not compacted.
     Returns dict(table (B,6), x_last (B,5), steps_run, solves)."""
     import torch
     x0 = np.ascontiguousarray(x0, dtype=np.float64); B = x0.shape[0]
@@ -63,6 +66,9 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     own_radii = r_safe is not None or r_hit is not None
     if own_radii:
         m.set_instance_params(r_safe=r_safe, r_hit=r_hit)
+    own_mask = active is not None
+    if own_mask:
+        m.set_obstacle_mask(np.asarray(active))
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
         t = lambda a: torch.from_numpy(a.copy()).to(dev)
@@ -81,6 +87,8 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
         fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS
         if init_guess_when_error:
             fl |= _lib.STEP_RESET_ON_FAIL | (_lib.STEP_ALIAS_BUG if bug_compat_alias else 0) | (_lib.STEP_INTERP_GUESS if interpolate_init else 0)
+        if own_mask and margin_all:
+            fl |= _lib.STEP_MARGIN_ALL
         if status_log:
             n2 = torch.zeros(B, dtype=torch.int32, device=dev); n4 = torch.zeros(B, dtype=torch.int32, device=dev)
             first_bad = torch.full((B,), -1, dtype=torch.int32, device=dev)
@@ -102,7 +110,7 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             dnoise = torch.from_numpy(noise).to(dev)
         k = 0
         # compaction of finished episodes (compact_from): results of parked episodes live in full-size arrays, `ids` maps the live batch to them
-        compact = compact_from is not None and B >= compact_from and not record and not status_log and not own_radii
+        compact = compact_from is not None and B >= compact_from and not record and not status_log and not own_radii and not own_mask
         B0 = B
         if compact:
             ids = torch.arange(B, device=dev)
@@ -166,8 +174,11 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             extra.update(status2=n2.cpu().numpy(), status4=n4.cpu().numpy(), first_bad=first_bad.cpu().numpy())
     if solver is None:
         m.close()
-    elif own_radii:
-        m.set_instance_params()      # (a caller's solver leaves as it came)
+    else:                            # (a caller's solver leaves as it came)
+        if own_radii:
+            m.set_instance_params()
+        if own_mask:
+            m.set_obstacle_mask(None)
     return dict(table=table, x_last=xl, steps_run=k, solves=int(steps.sum().item()) + int((fl_h & 1).sum()), **extra)
 
 

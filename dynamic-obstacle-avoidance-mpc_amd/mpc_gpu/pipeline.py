@@ -101,6 +101,12 @@ class PipelinedMpc:
         for lo, hi, m, _ in self.parts:
             m.set_instance_params(self._sl(W, lo, hi), self._sl(We, lo, hi), self._sl(r_safe, lo, hi), self._sl(r_hit, lo, hi))
 
+    def set_obstacle_mask_dev(self, mask=None):
+        """per-instance obstacle masks (BatchedMpc.set_obstacle_mask) from ONE device tensor (max_batch,) of int32 / uint32 words: every sub-handle gets
+        its contiguous slice, used in place (rewrite the words on the device at will); None switches the feature off"""
+        for lo, hi, m, _ in self.parts:
+            m.set_obstacle_mask(self._sl(mask, lo, hi))
+
     # ------------------------------------------------------------------ the cost exchange lives on the first sub-batch's handle (include/mpc_gpu.h mpc_comm_*)
     def comm_init(self, rank, world, unique_id):
         self.parts[0][2].comm_init(rank, world, unique_id)

@@ -28,6 +28,25 @@ def _ptr(a):
     return C.c_void_p(a.data_ptr())      # torch tensor (device or host)
 
 
+def pack_obstacle_mask(active):
+    """bool (B, n_obst) -> np.uint32 (B,): bit j of word b set iff active[b, j] (the words of mpc_set_obstacle_mask; n_obst <= 32)"""
+    a = np.asarray(active)
+    if a.ndim != 2 or a.shape[1] < 1 or a.shape[1] > 32:
+        raise ValueError(f"active must be a bool array (B, n_obst) with 1 <= n_obst <= 32, got shape {a.shape}")
+    if a.dtype != np.bool_:
+        if not np.isin(a, (0, 1)).all():
+            raise ValueError("active must hold booleans (or 0 / 1)")
+        a = a.astype(np.bool_)
+    w = (a.astype(np.uint64) << np.arange(a.shape[1], dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+    return np.ascontiguousarray(w.astype(np.uint32))
+
+
+def unpack_obstacle_mask(words, n_obst):
+    """np.uint32 (B,) -> bool (B, n_obst): the inverse of pack_obstacle_mask"""
+    w = np.asarray(words, dtype=np.uint32).astype(np.uint64)
+    return ((w[:, None] >> np.arange(int(n_obst), dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
+
+
 class BatchedMpc:
     # lanes per horizon stage / wavefronts per SIMD / lanes per instance applied to every new handle (0 = automatic); test / tuning hooks,
     # also settable from the environment for profiling runs of unmodified programs (MPC_LANES_PER_STAGE, MPC_WAVES_PER_SIMD, MPC_LANES_PER_INSTANCE)
@@ -200,6 +219,26 @@ class BatchedMpc:
         else:
             raise ValueError("per-instance parameters: host arrays or device tensors, not both in one call")
 
+    def set_obstacle_mask(self, active=None):
+        """Per-instance obstacle masks (include/mpc_gpu.h mpc_set_obstacle_mask): active[b, j] says whether obstacle j exists for instance b.  An absent
+        obstacle has no rows at any stage, no penalty in the reported cost and (unless STEP_MARGIN_ALL) no part in the fused step's margin; its entries
+        in P / obst may hold anything.  A bool array (B, n_obst) is packed (pack_obstacle_mask), validated and copied; a device tensor (max_batch,) of
+        int32 / uint32 words is used in place (the words it holds when a solve is launched; rewrite them on the device at will); None switches off."""
+        if active is None:
+            _lib.check(_lib.lib().mpc_set_obstacle_mask(self._h, 0, None))
+        elif isinstance(active, (np.ndarray, list, tuple)):
+            a = np.asarray(active)
+            if a.ndim != 2 or a.shape[1] != self.n_obst:
+                raise ValueError(f"active must be (B, {self.n_obst}), got {a.shape}")
+            if a.shape[0] < 1 or a.shape[0] > self.max_batch:
+                raise ValueError(f"active has {a.shape[0]} rows, the handle holds 1 .. {self.max_batch} instances")
+            words = pack_obstacle_mask(a)
+            _lib.check(_lib.lib().mpc_set_obstacle_mask(self._h, int(words.shape[0]), _ptr(words)))
+        else:
+            if tuple(active.shape) != (self.max_batch,) or str(active.dtype) not in ("torch.int32", "torch.uint32") or not active.is_contiguous():
+                raise ValueError(f"a device obstacle mask must be a contiguous int32 / uint32 tensor ({self.max_batch},)")
+            _lib.check(_lib.lib().mpc_set_obstacle_mask_dev(self._h, _ptr(active)))
+
     def plant_step(self, x, u):
         """ocp_integrator set/solve/get, robot_ocp_problem.py:207-212."""
         x = _f64(np.atleast_2d(x)); u = _f64(np.atleast_2d(u), (x.shape[0], 2))
@@ -301,7 +340,8 @@ class BatchedMpc:
     def closed_loop_step_dev(self, batch, x0, obst, goal, X, U, u0=None, cost=None, status=None, iters=None, noise=None,
                              randomness=0.1, vmax=2.0, flags=_lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES,
                              min_margin=None, ep_flags=None, ep_steps=None, stream=None):
-        """One whole control step (look-ahead, solve, plant, obstacle motion, bookkeeping, shift) in one launch.  flags | STEP_ADVANCE_REF moves
+        """One whole control step (look-ahead, solve, plant, obstacle motion, bookkeeping, shift) in one launch.  flags | STEP_MARGIN_ALL lets the margin and
+        the hit flag count obstacles that set_obstacle_mask masks off; flags | STEP_ADVANCE_REF moves
         the per-stage reference window (set_reference with offsets) one row on for every instance that stepped."""
         _lib.check(_lib.lib().mpc_closed_loop_step_dev(self._h, batch, _ptr(x0), _ptr(obst), _ptr(goal), _ptr(X), _ptr(U), _ptr(u0),
                                                        _ptr(cost), _ptr(status), _ptr(iters), _ptr(noise), randomness, vmax, flags,

@@ -190,6 +190,25 @@ int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d
 int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const double *We, const double *r_safe, const double *r_hit);
 int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *d_We, const double *d_r_safe, const double *d_r_hit);
 
+/* Per-instance obstacle masks: bit j of mask[b] set means obstacle j exists for instance b; one batch then holds problems with different obstacle sets
+ * (sweeps over the obstacle count, obstacles that enter and leave an instance's view).  NULL switches the feature off and the handle runs the kernels
+ * it ran before.  An absent obstacle has no row at any stage: no inequality pairs, no entries in the item count behind mu, no part in the cold start,
+ * the complementarity and polish tests or the slack equations of the stationarity residual, no penalty term in the reported cost -- the solve is the
+ * one of a handle built for the present obstacles only.  Its entries in P / obst may hold anything, NaN and Inf included: they reach no output and
+ * not the non-finite-input test (status 4).  A word of 0 is valid: that instance solves the problem without obstacle rows.
+ * Host words, validated (batch in [1, max_batch], no bit at or above n_obst; MPC_ERR_ARG otherwise) and copied; applies to every following solve
+ * (mpc_solve, mpc_solve_obst, mpc_solve_dev, mpc_closed_loop_step_dev) of the first `batch` instances until replaced.
+ * _dev: max_batch device words, used in place and not validated (bits at and above n_obst are ignored): a solve reads them when it is launched, so
+ * a caller may rewrite them on the device between steps with no host call.
+ * mpc_closed_loop_step_dev: every obstacle still moves and still consumes its noise pair (the noise stream and a later re-activation stay consistent);
+ * absent obstacles do not enter the margin or the hit flag unless MPC_STEP_MARGIN_ALL is given ("not sensed, but it is there": the solve sees the
+ * masked set, the bookkeeping every obstacle).
+ * Works together with mpc_set_reference, mpc_set_instance_params, explicit P, the in-kernel look-ahead and every flag of the fused step; thr0 and all
+ * other mpc_config fields stay per handle.  mpc_linearize_dev is NOT masked: hval / dh are geometry and keep reporting every obstacle.
+ * Mappings and refusals are those of mpc_set_instance_params (above), always on the run-time-row-count kernels (also when n_obst fills the row capacity). */
+int mpc_set_obstacle_mask(mpc_handle *h, int batch, const uint32_t *mask);
+int mpc_set_obstacle_mask_dev(mpc_handle *h, const uint32_t *d_mask);
+
 /* Plant integrator, ocp_integrator.set/solve/get, robot_ocp_problem.py:207-212 (same IRK as the OCP) */
 int mpc_plant_step(mpc_handle *h, int batch, const double *x, const double *u, double *x_next);
 /* Obstacle look-ahead only: obst[B][n_obst][4] -> P[B][N+1][n_obst][2] (visualization.py:62-79) */
@@ -216,6 +235,7 @@ int mpc_predict_dev(mpc_handle *h, int batch, const double *d_obst, double *d_P,
 #define MPC_STEP_METRICS 32
 #define MPC_STEP_INTERP_GUESS 64   /* with MPC_STEP_RESET_ON_FAIL: the reset writes the straight-line guess of mpc_reset_guess_interp */
 #define MPC_STEP_ADVANCE_REF 128   /* behind the step, offset[b] += 1 of the per-stage reference for every instance that stepped (idle ones do not); needs offsets */
+#define MPC_STEP_MARGIN_ALL 256    /* with an obstacle mask: margin and hit flag count every obstacle, absent ones included (without a mask they all count anyway) */
 int mpc_closed_loop_step_dev(mpc_handle *h, int batch, double *d_x0, double *d_obst, const double *d_goal, double *d_X, double *d_U,
                              double *d_u0, double *d_cost, int32_t *d_status, int32_t *d_iters, const double *d_noise,
                              double randomness, double vmax, int flags, double *d_min_margin, int32_t *d_ep_flags,

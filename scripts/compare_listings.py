@@ -4,7 +4,7 @@ Usage: python scripts/compare_listings.py OLD.s NEW.s
 Every kernel present in both listings must have the same instructions once label numbers, comments and directives that only name
 sections or sizes are ignored.  Kernels only in NEW (new instantiations) are listed; kernels only in OLD are an error.  Exit 1 on any difference.
 A kernel that gained a trailing `bool` template parameter whose default (false) keeps the old code -- the REF parameter of the per-stage reference,
-the IPAR parameter of the per-instance parameters -- is matched to its old name: rti_*_kernel<..., false> and linearize_kernel<..., false>.
+the IPAR parameter of the per-instance parameters, the OSEL parameter of the obstacle masks -- is matched to its old name: rti_*_kernel<..., false> and linearize_kernel<..., false>.
 """
 import re
 import sys
