@@ -5,6 +5,7 @@
 #include "rti_kernel.hpp"
 #include "rti_split_kernel.hpp"
 #include "rti_wide_kernel.hpp"
+#include "solve_dispatch.hpp"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -160,6 +161,17 @@ int check_batch(mpc_handle *h, int batch)
 
 hipStream_t pick(mpc_handle *h, void *stream) { return stream ? (hipStream_t)stream : h->stream; }
 
+// the kernel arguments of a solve: its inputs (the look-ahead P, or the obstacle states it is computed from inside the kernel) and outputs
+mpc::KParams solve_params(mpc_handle *h, int batch, const double *x0, const double *P, const double *obst, const double *goal, double *X, double *U,
+                          double *u0, double *cost, int32_t *status, int32_t *iters)
+{
+    mpc::KParams p = make_params(h->cfg, batch);
+    p.x0 = x0; p.P = P; p.obst = obst; p.goal = goal; p.X = X; p.U = U;
+    p.u0 = u0; p.cost = cost; p.status = status; p.iters = iters; p.trace = h->d_trace;
+    if (obst) p.world = make_world(h->cfg);
+    return p;
+}
+
 // Lanes per instance of the one-lane-per-stage mapping: the smallest of {16, 32, 64} with N + 1 < G (an idle lane separates instances that
 // share a wavefront), or 21 -- three instances per wavefront on compact LDS blocks -- for 16 <= N <= 20 once pick_split hands a large batch
 // to this mapping; unless overridden.  Packing instances into one wavefront multiplies throughput for large batches.
@@ -220,52 +232,22 @@ int pick_waves(mpc_handle *h, int batch)
 }
 
 // More than 64 KB of dynamic LDS has to be granted per kernel function and device; the grant is remembered (largest size so far per
-// kernel and device) instead of being re-issued on every launch.
+// kernel and device, beside the kernel's table row) instead of being re-issued on every launch.
 constexpr int kMaxDevices = 64;
-template <typename K>
-int grant_lds(K kernel, int (&granted)[kMaxDevices], int device, size_t lds)
+int g_granted[mpc::kSolveKernelCount][kMaxDevices];
+int grant_lds(const mpc::KernelRow &row, int device, size_t lds)
 {
     if (lds <= 65536) return MPC_OK;
+    int (&granted)[kMaxDevices] = g_granted[&row - mpc::kSolveKernels];
     const int d = device < kMaxDevices ? device : kMaxDevices - 1;
     if (device < kMaxDevices && granted[d] >= (int)lds) return MPC_OK;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(row.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     granted[d] = (int)lds;
     return MPC_OK;
 }
 
 // Block-2 (partially condensed) stage recursions: the stage-split mapping on dense blocks, even horizons, all rows of the kernel's capacity in use
 bool use_block2(const mpc_handle *h, bool w2, bool masked) { return h->block2 && !w2 && !masked && (h->cfg.N % 2 == 0) && h->cfg.N >= 4; }
-
-template <int NO, int LPS, bool W2, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false>
-int launch_split_w(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
-{
-    if constexpr (!BLK2 && !W2 && !MASKED && !REF) {
-        if (use_block2(h, W2, MASKED)) return launch_split_w<NO, LPS, W2, MASKED, true>(h, p, s);
-    }
-    static int granted[kMaxDevices] = {};
-    const size_t lds = (size_t)mpc::SplitLds<LPS, NO, W2, BLK2>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR, OSEL>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_split_kernel<NO, LPS, W2, MASKED, BLK2, REF, IPAR, OSEL>), dim3(p.batch), dim3(64), lds, s, p);
-    return MPC_OK;
-}
-
-template <int NO, int LPS, bool REF = false, bool IPAR = false>
-int launch_split(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
-{
-    if (p.n_obst != NO) return launch_split_w<NO, LPS, false, true, false, REF, IPAR>(h, p, s);      // fewer obstacles than rows: the run-time-count variant
-    return pick_waves(h, p.batch) == 2 ? launch_split_w<NO, LPS, true, false, false, REF, IPAR>(h, p, s) : launch_split_w<NO, LPS, false, false, false, REF, IPAR>(h, p, s);
-}
-
-// 11 .. 32 obstacles: one instance per workgroup of WideShape<CAP>::W wavefronts
-template <int CAP, bool MASKED, bool REF = false, bool IPAR = false, bool OSEL = false>
-int launch_wide(mpc_handle *h, const mpc::KParams &p, hipStream_t s)
-{
-    static int granted[kMaxDevices] = {};
-    const size_t lds = (size_t)mpc::WideLds<CAP>::total(p.N, p.obst != nullptr) * sizeof(double);
-    int rc = grant_lds(&mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR, OSEL>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_wide_kernel<CAP, 2, MASKED, REF, IPAR, OSEL>), dim3(p.batch), dim3(64 * mpc::WideShape<CAP>::W), lds, s, p);
-    return MPC_OK;
-}
 
 // what rti_wide_kernel cannot run: horizons beyond two lanes per stage, and the mapping overrides that name a layout it does not have
 int check_wide(const mpc_handle *h)
@@ -277,213 +259,80 @@ int check_wide(const mpc_handle *h)
     return MPC_OK;
 }
 
-template <int NO, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false>
-int launch_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 grid, size_t lds)
-{
-    static int granted[kMaxDevices] = {};
-    int rc = grant_lds(&mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR, OSEL>, granted, h->device, lds); if (rc) return rc;
-    hipLaunchKernelGGL((mpc::rti_solve_kernel<NO, G, FACT, MASKED, REF, IPAR, OSEL>), grid, dim3(64), lds, s, p);
-    return MPC_OK;
-}
-
-// The lane mapping, kernel variant and dynamic-LDS size a batch runs with (one place: launches and mpc_get_kernel_name read it)
-struct SolvePlan {
-    int lps, waves;        // stage-split mapping: lanes per stage (> 1) and wavefronts per SIMD
-    int G, fact;           // one lane per stage: lanes per instance, sweep variant (0 systolic, 1 matrix cores, 2 row-parallel dense, 3 compact)
-    size_t lds;
-};
-
-// Per-stage reference (mpc_set_reference): the REF instantiations exist for the stage-split kernel (every horizon up to 31, at every batch size --
-// where the goal path would pack 3 or 4 instances into a wavefront the reference path stays on the split mapping), the multi-wavefront kernel,
+// Per-stage reference (mpc_set_reference), feature level 1: the REF instantiations exist for the stage-split kernel (every horizon up to 31, at every batch
+// size -- where the goal path would pack 3 or 4 instances into a wavefront the reference path stays on the split mapping), the multi-wavefront kernel,
 // and one instance per wavefront on compact stage blocks (N > 31, or one lane per stage asked for).  The evidence mappings have none.
-bool ref_active(const mpc_handle *h) { return h->d_yref != nullptr; }
-// Per-instance parameters (mpc_set_instance_params): the IPAR instantiations are the REF ones with one more flag, with or without a reference -- the
-// same mappings, the same plan (plan_solve_ref), the same refusals
-bool ip_active(const mpc_handle *h) { return h->ip_mode != 0; }
-// Per-instance obstacle masks (mpc_set_obstacle_mask): the OSEL instantiations are the IPAR ones with a run-time row count and one more flag -- again the
-// same mappings, plan and refusals; without instance parameters the tables they read hold the handle's own values
-bool om_active(const mpc_handle *h) { return h->om_mode != 0; }
+// Per-instance parameters (mpc_set_instance_params), level 2: the REF instantiations with one more flag, with or without a reference -- the same mappings,
+// the same plan, the same refusals.
+// Per-instance obstacle masks (mpc_set_obstacle_mask), level 3: the IPAR instantiations with a run-time row count and one more flag -- again the same
+// mappings, plan and refusals; without instance parameters the tables they read hold the handle's own values
+int feature_level(const mpc_handle *h) { return h->om_mode != 0 ? 3 : (h->ip_mode != 0 ? 2 : (h->d_yref != nullptr ? 1 : 0)); }
 
-int check_ref_mapping(const mpc_handle *h)
+int check_feature_mapping(const mpc_handle *h)
 {
-    const char *what = om_active(h) ? "an obstacle mask" : (ip_active(h) ? "per-instance parameters" : "a per-stage reference");
-    if (h->use_mfma) return fail(MPC_ERR_ARG, "%s: no build for the matrix-core factorisation (mpc_set_matrix_cores)", what);
-    if (!h->row_parallel) return fail(MPC_ERR_ARG, "%s: no build for the systolic sweeps (mpc_set_row_parallel(0))", what);
-    if (h->block2) return fail(MPC_ERR_ARG, "%s: no build for the block-2 recursions (mpc_set_block_riccati)", what);
-    if (h->lanes_override != 0 && h->lanes_override != 64) return fail(MPC_ERR_ARG, "%s: one instance per wavefront only (mpc_set_lanes_per_instance 0 or 64)", what);
+    const char *what[] = {"", "a per-stage reference", "per-instance parameters", "an obstacle mask"};
+    const char *w = what[feature_level(h)];
+    if (h->use_mfma) return fail(MPC_ERR_ARG, "%s: no build for the matrix-core factorisation (mpc_set_matrix_cores)", w);
+    if (!h->row_parallel) return fail(MPC_ERR_ARG, "%s: no build for the systolic sweeps (mpc_set_row_parallel(0))", w);
+    if (h->block2) return fail(MPC_ERR_ARG, "%s: no build for the block-2 recursions (mpc_set_block_riccati)", w);
+    if (h->lanes_override != 0 && h->lanes_override != 64) return fail(MPC_ERR_ARG, "%s: one instance per wavefront only (mpc_set_lanes_per_instance 0 or 64)", w);
     return MPC_OK;
 }
 
-SolvePlan plan_solve_ref(mpc_handle *h, int batch)
+// The lane mapping, kernel variant, launch geometry and dynamic-LDS size a batch runs with: the one place that decides them (launch_plan and
+// mpc_get_kernel_name read it)
+mpc::SolvePlan plan_solve(mpc_handle *h, int batch, bool lookahead)
 {
-    SolvePlan q = {1, 1, 64, 3, 0};
-    const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
-    const int fit = N <= 20 ? 3 : (N <= 31 ? 2 : 1);
+    mpc::SolvePlan q = {};
+    const int N = h->cfg.N, fit = N <= 20 ? 3 : (N <= 31 ? 2 : 1);
+    q.cap = row_capacity(h->cfg.n_obst);
+    q.masked = partial_rows(h);
+    q.level = feature_level(h);
     q.lps = pick_split(h, batch);
-    if (q.lps == 1 && fit > 1 && h->split_override != 1 && h->lanes_override != 64) q.lps = fit;
-    if (q.lps > 1) {
-        q.waves = pick_waves(h, batch);
-        return q;
+    q.G = 64; q.fact = 3;
+    q.grid = (unsigned)batch;
+    // (the feature levels stay on the split mapping wherever the horizon fits it, unless one lane per stage is asked for)
+    if (q.level && q.lps == 1 && fit > 1 && h->split_override != 1 && h->lanes_override != 64) q.lps = fit;
+    if (wide_rows(h->cfg.n_obst)) {
+        q.family = mpc::kWide;
+    } else if (q.lps > 1) {
+        q.family = mpc::kSplit;
+        q.w2 = pick_waves(h, batch) == 2 && !q.masked;
+        q.blk2 = !q.level && use_block2(h, q.w2, q.masked);
+    } else if (!q.level) {
+        q.G = pick_lanes(h, batch);
+        const bool use_mfma = (q.G == 64) && h->use_mfma && !q.masked;
+        const bool rowpar = (!use_mfma && h->row_parallel) || q.masked;
+        // Compact stage blocks (look-ahead staged inside them): always with three instances per wavefront (13.5 KB per instance at N = 20:
+        // four wavefronts of three per CU), and for long horizons on 64 lanes whenever the dense blocks would leave a CU fewer than the four
+        // wavefronts its SIMDs can hold (N = 50, 10 obstacles: 51 KB -> 3 per CU dense, 32 KB -> 4 compact)
+        const bool compact = rowpar && (q.G == 21 || (q.G == 64 && (mpc::one_lane_lds(q.cap, q.G, 2, N, lookahead) > 40960 || q.cap >= 10)));     // (ten row pairs: the compact kernel keeps its positions in LDS and has no scratch)
+        q.fact = use_mfma ? 1 : (rowpar ? (compact ? 3 : 2) : 0);
+        q.grid = (unsigned)((batch + 64 / q.G - 1) / (64 / q.G));
     }
-    q.lds = (size_t)(no >= 10 ? mpc::RowLdsC::total_with_positions(N, 1, no) : mpc::RowLdsC::total(N, 1)) * sizeof(double);
+    q.row = mpc::find_solve_kernel(q.key());
+    if (q.row) { q.block = (unsigned)q.row->block; q.lds = q.row->lds(N, lookahead); }
     return q;
 }
 
-SolvePlan plan_solve(mpc_handle *h, int batch, bool lookahead)
+// What a plan's mapping refuses, decided here for the launch and for mpc_get_kernel_name alike
+int check_plan(const mpc_handle *h, const mpc::SolvePlan &q)
 {
-    if (ref_active(h) || ip_active(h) || om_active(h)) return plan_solve_ref(h, batch);
-    SolvePlan q = {1, 1, 64, 2, 0};
-    const int N = h->cfg.N, no = row_capacity(h->cfg.n_obst);
-    q.lps = pick_split(h, batch);
-    if (q.lps > 1) {
-        q.waves = pick_waves(h, batch);
-        return q;          // (the LDS size of a split launch is a compile-time function of the kernel's template arguments: launch_split_w)
-    }
-    q.G = pick_lanes(h, batch);
-    const bool use_mfma = (q.G == 64) && h->use_mfma && !partial_rows(h);
-    const bool rowpar = (!use_mfma && h->row_parallel) || partial_rows(h);
-    const int ipw = 64 / q.G;
-    const size_t dense = ((lookahead ? (size_t)ipw * (N + 1) * no * 2 : 0) + (use_mfma ? (size_t)mpc::MfmaLds::doubles(N) : 0) +
-                          (rowpar ? (size_t)mpc::RowLds::total(N, ipw) : 0)) * sizeof(double);
-    // Compact stage blocks (look-ahead staged inside them): always with three instances per wavefront (13.5 KB per instance at N = 20:
-    // four wavefronts of three per CU), and for long horizons on 64 lanes whenever the dense blocks would leave a CU fewer than the four
-    // wavefronts its SIMDs can hold (N = 50, 10 obstacles: 51 KB -> 3 per CU dense, 32 KB -> 4 compact)
-    const bool compact = rowpar && (q.G == 21 || (q.G == 64 && (dense > 40960 || no >= 10)));     // (ten row pairs: the compact kernel keeps its positions in LDS and has no scratch)
-    q.fact = use_mfma ? 1 : (rowpar ? (compact ? 3 : 2) : 0);
-    // (compact blocks with 10 obstacles: the look-ahead positions stay resident behind the blocks, rti_kernel.hpp PLDS)
-    q.lds = compact ? (size_t)(no >= 10 ? mpc::RowLdsC::total_with_positions(N, ipw, no) : mpc::RowLdsC::total(N, ipw)) * sizeof(double) : dense;
-    return q;
-}
-
-template <int NO>
-int launch_one_lane_g(mpc_handle *h, const mpc::KParams &p, hipStream_t s, dim3 grid, const SolvePlan &q)
-{
-    if (p.n_obst != NO) {        // fewer obstacles than rows: the run-time-count variants (one instance per wavefront, row-parallel sweeps)
-        if (q.G == 64 && q.fact == 2) return launch_one_lane<NO, 64, 2, true>(h, p, s, grid, q.lds);
-        if (q.G == 64 && q.fact == 3) return launch_one_lane<NO, 64, 3, true>(h, p, s, grid, q.lds);
-        return fail(MPC_ERR_ARG, "no kernel variant for this lane mapping with n_obst outside {3, 5, 10}");
-    }
-    switch (q.G * 10 + q.fact) {
-    case 213: return launch_one_lane<NO, 21, 3>(h, p, s, grid, q.lds);
-    case 162: return launch_one_lane<NO, 16, 2>(h, p, s, grid, q.lds);
-    case 160: return launch_one_lane<NO, 16, 0>(h, p, s, grid, q.lds);
-    case 322: return launch_one_lane<NO, 32, 2>(h, p, s, grid, q.lds);
-    case 320: return launch_one_lane<NO, 32, 0>(h, p, s, grid, q.lds);
-    case 641: return launch_one_lane<NO, 64, 1>(h, p, s, grid, q.lds);
-    case 642: return launch_one_lane<NO, 64, 2>(h, p, s, grid, q.lds);
-    case 643: return launch_one_lane<NO, 64, 3>(h, p, s, grid, q.lds);
-    case 640: return launch_one_lane<NO, 64, 0>(h, p, s, grid, q.lds);
-    }
-    return fail(MPC_ERR_ARG, "no kernel variant for this lane mapping (three instances per wavefront need the row-parallel sweeps)");
-}
-
-// the REF instantiations (plan_solve_ref), and the IPAR ones built on them
-template <int NO, bool IPAR>
-int launch_ref_one_lane(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
-{
-    if (p.n_obst != NO) return launch_one_lane<NO, 64, 3, true, true, IPAR>(h, p, s, dim3(p.batch), q.lds);
-    return launch_one_lane<NO, 64, 3, false, true, IPAR>(h, p, s, dim3(p.batch), q.lds);
-}
-
-template <bool IPAR>
-int dispatch_solve_ref(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
-{
-    int rc = MPC_OK;
-    if (wide_rows(h->cfg.n_obst)) {
-        rc = check_wide(h); if (rc) return rc;
-        const bool masked = partial_rows(h);
-        if (row_capacity(h->cfg.n_obst) == 20) rc = masked ? launch_wide<20, true, true, IPAR>(h, p, s) : launch_wide<20, false, true, IPAR>(h, p, s);
-        else rc = masked ? launch_wide<32, true, true, IPAR>(h, p, s) : launch_wide<32, false, true, IPAR>(h, p, s);
-    } else if ((rc = check_ref_mapping(h)) != MPC_OK) {
-        return rc;
-    } else if (q.lps > 1) {
-        switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
-        case 32: rc = launch_split<3, 2, true, IPAR>(h, p, s); break;
-        case 33: rc = launch_split<3, 3, true, IPAR>(h, p, s); break;
-        case 52: rc = launch_split<5, 2, true, IPAR>(h, p, s); break;
-        case 53: rc = launch_split<5, 3, true, IPAR>(h, p, s); break;
-        case 102: rc = launch_split<10, 2, true, IPAR>(h, p, s); break;
-        case 103: rc = launch_split<10, 3, true, IPAR>(h, p, s); break;
-        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
-        }
-    } else {
-        switch (row_capacity(h->cfg.n_obst)) {
-        case 3: rc = launch_ref_one_lane<3, IPAR>(h, p, s, q); break;
-        case 5: rc = launch_ref_one_lane<5, IPAR>(h, p, s, q); break;
-        case 10: rc = launch_ref_one_lane<10, IPAR>(h, p, s, q); break;
-        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
-        }
-    }
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    return MPC_OK;
-}
-
-// the OSEL instantiations (plan_solve_ref): the run-time-count variant of every family
-int dispatch_solve_osel(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
-{
-    int rc = MPC_OK;
-    if (wide_rows(h->cfg.n_obst)) {
-        rc = check_wide(h); if (rc) return rc;
-        if (row_capacity(h->cfg.n_obst) == 20) rc = launch_wide<20, true, true, true, true>(h, p, s);
-        else rc = launch_wide<32, true, true, true, true>(h, p, s);
-    } else if ((rc = check_ref_mapping(h)) != MPC_OK) {
-        return rc;
-    } else if (q.lps > 1) {
-        switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
-        case 32: rc = launch_split_w<3, 2, false, true, false, true, true, true>(h, p, s); break;
-        case 33: rc = launch_split_w<3, 3, false, true, false, true, true, true>(h, p, s); break;
-        case 52: rc = launch_split_w<5, 2, false, true, false, true, true, true>(h, p, s); break;
-        case 53: rc = launch_split_w<5, 3, false, true, false, true, true, true>(h, p, s); break;
-        case 102: rc = launch_split_w<10, 2, false, true, false, true, true, true>(h, p, s); break;
-        case 103: rc = launch_split_w<10, 3, false, true, false, true, true, true>(h, p, s); break;
-        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
-        }
-    } else {
-        switch (row_capacity(h->cfg.n_obst)) {
-        case 3: rc = launch_one_lane<3, 64, 3, true, true, true, true>(h, p, s, dim3(p.batch), q.lds); break;
-        case 5: rc = launch_one_lane<5, 64, 3, true, true, true, true>(h, p, s, dim3(p.batch), q.lds); break;
-        case 10: rc = launch_one_lane<10, 64, 3, true, true, true, true>(h, p, s, dim3(p.batch), q.lds); break;
-        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
-        }
-    }
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    return MPC_OK;
+    if (q.family == mpc::kWide) return check_wide(h);
+    return q.level ? check_feature_mapping(h) : MPC_OK;
 }
 
 // launches the variant the plan names; no event handling here
-int dispatch_solve(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const SolvePlan &q)
+int launch_plan(mpc_handle *h, const mpc::KParams &p, hipStream_t s, const mpc::SolvePlan &q)
 {
-    if (p.omask) return dispatch_solve_osel(h, p, s, q);
-    if (p.ip_w) return dispatch_solve_ref<true>(h, p, s, q);
-    if (p.yref) return dispatch_solve_ref<false>(h, p, s, q);
-    int rc = MPC_OK;
-    if (wide_rows(h->cfg.n_obst)) {
-        rc = check_wide(h); if (rc) return rc;
-        const bool masked = partial_rows(h);
-        if (row_capacity(h->cfg.n_obst) == 20) rc = masked ? launch_wide<20, true>(h, p, s) : launch_wide<20, false>(h, p, s);
-        else rc = masked ? launch_wide<32, true>(h, p, s) : launch_wide<32, false>(h, p, s);
-    } else if (q.lps > 1) {
-        switch (row_capacity(h->cfg.n_obst) * 10 + q.lps) {
-        case 32: rc = launch_split<3, 2>(h, p, s); break;
-        case 33: rc = launch_split<3, 3>(h, p, s); break;
-        case 52: rc = launch_split<5, 2>(h, p, s); break;
-        case 53: rc = launch_split<5, 3>(h, p, s); break;
-        case 102: rc = launch_split<10, 2>(h, p, s); break;
-        case 103: rc = launch_split<10, 3>(h, p, s); break;
-        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
-        }
-    } else {
-        const dim3 grid((p.batch + 64 / q.G - 1) / (64 / q.G));
-        switch (row_capacity(h->cfg.n_obst)) {
-        case 3: rc = launch_one_lane_g<3>(h, p, s, grid, q); break;
-        case 5: rc = launch_one_lane_g<5>(h, p, s, grid, q); break;
-        case 10: rc = launch_one_lane_g<10>(h, p, s, grid, q); break;
-        default: return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
-        }
+    int rc = check_plan(h, q); if (rc) return rc;
+    if (!q.row) {
+        if (q.family != mpc::kOneLane) return fail(MPC_ERR_ARG, "n_obst must be in [1, 10]");
+        if (q.masked) return fail(MPC_ERR_ARG, "no kernel variant for this lane mapping with n_obst outside {3, 5, 10}");
+        return fail(MPC_ERR_ARG, "no kernel variant for this lane mapping (three instances per wavefront need the row-parallel sweeps)");
     }
-    if (rc) return rc;
+    rc = grant_lds(*q.row, h->device, q.lds); if (rc) return rc;
+    hipLaunchKernelGGL(q.row->fn, dim3(q.grid), dim3(q.block), q.lds, s, p);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -578,47 +427,46 @@ int fill_default_instance_tables(mpc_handle *h)
     return MPC_OK;
 }
 
-// in front of a solve: the obstacle mask's coverage check and kernel argument (with it, the tables are attached whether or not instance parameters are set)
-int attach_obstacle_mask(mpc_handle *h, mpc::KParams &p)
+// In front of a launch that reads them: the coverage checks and kernel arguments of the per-stage reference, the per-instance tables (derived here from
+// device arrays, mode 2) and, for a solve, the obstacle mask (with it the tables are attached whether or not instance parameters are set) and the slack schedule
+enum AttachFor { kForSolve, kForLinearize };
+int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
 {
-    if (!h->om_mode) return MPC_OK;
-    if (p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
-    if (!h->ip_mode) {
-        if (!h->ip_default) return fail(MPC_ERR_ARG, "internal: the default instance tables of the obstacle mask are not filled");
+    p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
+    if (h->d_yref && p.batch > h->ref_batch)
+        return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this %s", what == kForSolve ? "solve" : "call");
+    if ((p.fused & MPC_STEP_ADVANCE_REF) && (!h->d_yref || !h->d_ref_off))
+        return fail(MPC_ERR_ARG, "MPC_STEP_ADVANCE_REF needs a per-stage reference with offsets (mpc_set_reference[_dev])");
+    if (h->ip_mode) {
+        if (p.batch > h->ip_batch) return fail(MPC_ERR_ARG, "the per-instance parameters set by mpc_set_instance_params cover fewer instances than this solve");
+        if (h->ip_mode == 2) {
+            hipLaunchKernelGGL(mpc::instance_params_kernel, dim3((p.batch + 127) / 128), dim3(128), 0, s, ip_defaults(h->cfg), p.batch, h->cfg.n_obst,
+                               h->ip_dev[0], h->ip_dev[1], h->ip_dev[2], h->ip_dev[3], h->d_ip_w, h->d_ip_r2, h->d_ip_rhit);
+            HIPCHK(hipGetLastError());
+        }
         p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
     }
-    p.omask = h->d_omask;
-    return MPC_OK;
-}
-
-// in front of a launch that reads the tables: the coverage check, the derivation from device arrays (mode 2), the kernel arguments
-int attach_instance_params(mpc_handle *h, mpc::KParams &p, hipStream_t s)
-{
-    if (!h->ip_mode) return MPC_OK;
-    if (p.batch > h->ip_batch) return fail(MPC_ERR_ARG, "the per-instance parameters set by mpc_set_instance_params cover fewer instances than this solve");
-    if (h->ip_mode == 2) {
-        hipLaunchKernelGGL(mpc::instance_params_kernel, dim3((p.batch + 127) / 128), dim3(128), 0, s, ip_defaults(h->cfg), p.batch, h->cfg.n_obst,
-                           h->ip_dev[0], h->ip_dev[1], h->ip_dev[2], h->ip_dev[3], h->d_ip_w, h->d_ip_r2, h->d_ip_rhit);
-        HIPCHK(hipGetLastError());
+    if (what != kForSolve) return MPC_OK;
+    if (h->om_mode) {
+        if (p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
+        if (!h->ip_mode) {
+            if (!h->ip_default) return fail(MPC_ERR_ARG, "internal: the default instance tables of the obstacle mask are not filled");
+            p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
+        }
+        p.omask = h->d_omask;
     }
-    p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
+    // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
+    p.alpha = h->d_alpha;
+    if (h->d_alpha && h->d_alpha == h->d_alpha_own && p.batch > h->alpha_batch)
+        return fail(MPC_ERR_ARG, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
     return MPC_OK;
 }
 
 int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
 {
     p.iters_acc = h->d_iters_acc; p.status_acc = h->d_status_acc;
-    p.alpha = h->d_alpha;
-    p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
-    if (h->d_yref && p.batch > h->ref_batch) return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this solve");
-    if ((p.fused & MPC_STEP_ADVANCE_REF) && (!h->d_yref || !h->d_ref_off))
-        return fail(MPC_ERR_ARG, "MPC_STEP_ADVANCE_REF needs a per-stage reference with offsets (mpc_set_reference[_dev])");
-    int rc_ip = attach_instance_params(h, p, s); if (rc_ip) return rc_ip;
-    rc_ip = attach_obstacle_mask(h, p); if (rc_ip) return rc_ip;
-    // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
-    if (h->d_alpha && h->d_alpha == h->d_alpha_own && p.batch > h->alpha_batch)
-        return fail(MPC_ERR_ARG, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
-    const SolvePlan q = plan_solve(h, p.batch, p.obst != nullptr);
+    int rc_in = attach_inputs(h, p, s, kForSolve); if (rc_in) return rc_in;
+    const mpc::SolvePlan q = plan_solve(h, p.batch, p.obst != nullptr);
     // Instance scheduling (aux_kernels.hpp::schedule_kernel): wavefront slots are dealt the instances in the order of their iteration counts
     // in this handle's previous launch of the same batch size, longest first -- instances that share a wavefront then stop together, and
     // the rare 50-iteration instance starts in the first round of wavefronts instead of stretching the last one; the order for the NEXT
@@ -633,7 +481,7 @@ int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
     // counts only when both records and the launch between them succeeded
     const bool timed = h->profiling && (h->launch_count++ % h->profiling) == 0 && h->ev_used < (int)h->ev_start.size();
     if (timed) HIPCHK(hipEventRecord(h->ev_start[h->ev_used], s));
-    int rc = dispatch_solve(h, p, s, q);
+    int rc = launch_plan(h, p, s, q);
     if (rc) return rc;
     if (timed) {
         HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], s));
@@ -767,9 +615,7 @@ int mpc_solve_dev(mpc_handle *h, int batch, const double *d_x0, const double *d_
     if (batch == 0) return MPC_OK;
     if (!d_x0 || !d_P || !d_goal || !d_X || !d_U) return fail(MPC_ERR_ARG, "null device pointer");
     HIPCHK(hipSetDevice(h->device));
-    mpc::KParams p = make_params(h->cfg, batch);
-    p.x0 = d_x0; p.P = d_P; p.goal = d_goal; p.X = d_X; p.U = d_U;
-    p.u0 = d_u0; p.cost = d_cost; p.status = d_status; p.iters = d_iters; p.trace = h->d_trace;
+    mpc::KParams p = solve_params(h, batch, d_x0, d_P, nullptr, d_goal, d_X, d_U, d_u0, d_cost, d_status, d_iters);
     return launch_solve(h, p, pick(h, stream));
 }
 
@@ -783,14 +629,11 @@ int mpc_closed_loop_step_dev(mpc_handle *h, int batch, double *d_x0, double *d_o
     if (!d_x0 || !d_obst || !d_goal || !d_X || !d_U) return fail(MPC_ERR_ARG, "null device pointer");
     if ((flags & MPC_STEP_METRICS) && (!d_min_margin || !d_ep_flags || !d_ep_steps)) return fail(MPC_ERR_ARG, "metrics requested without buffers");
     HIPCHK(hipSetDevice(h->device));
-    mpc::KParams p = make_params(h->cfg, batch);
-    p.x0 = d_x0; p.P = nullptr; p.goal = d_goal; p.X = d_X; p.U = d_U;
-    p.u0 = d_u0; p.cost = d_cost; p.status = d_status; p.iters = d_iters; p.trace = h->d_trace;
-    p.obst = d_obst; p.x0_rw = d_x0; p.obst_rw = d_obst; p.noise = d_noise;
+    mpc::KParams p = solve_params(h, batch, d_x0, nullptr, d_obst, d_goal, d_X, d_U, d_u0, d_cost, d_status, d_iters);
+    p.x0_rw = d_x0; p.obst_rw = d_obst; p.noise = d_noise;
     p.randomness = randomness; p.vmax = vmax;
     p.tol_goal = 0.15;               // TOL, src/models/world_specification.py:45
     p.r_hit = 1.0 + 0.2;             // o.r + R_ROBOT, robot_ocp_problem.py:224
-    p.world = make_world(h->cfg);
     p.fused = flags;
     p.ep_min_margin = d_min_margin; p.ep_flags = d_ep_flags; p.ep_steps = d_ep_steps;
     return launch_solve(h, p, pick(h, stream));
@@ -893,12 +736,10 @@ int mpc_linearize_dev(mpc_handle *h, int batch, const double *d_x0, const double
     if (batch == 0) return MPC_OK;
     if (!d_x0 || !d_P || !d_goal || !d_X || !d_U || !d_A || !d_B || !d_b || !d_q || !d_hval || !d_dh) return fail(MPC_ERR_ARG, "null device pointer");
     HIPCHK(hipSetDevice(h->device));
-    if (h->d_yref && batch > h->ref_batch) return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this call");
     mpc::KParams p = make_params(h->cfg, batch);
     p.x0 = d_x0; p.P = d_P; p.goal = d_goal;
-    p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
     const int count = batch * (h->cfg.N + 1);
-    rc = attach_instance_params(h, p, pick(h, stream)); if (rc) return rc;
+    rc = attach_inputs(h, p, pick(h, stream), kForLinearize); if (rc) return rc;
     if (p.ip_w)
         hipLaunchKernelGGL((mpc::linearize_kernel<true, true>), dim3((count + 127) / 128), dim3(128), 0, pick(h, stream), p, h->cfg.n_obst, d_X, d_U,
                            d_A, d_B, d_b, d_q, d_hval, d_dh);
@@ -1010,11 +851,8 @@ static int solve_common(mpc_handle *h, int batch, const double *x0, const double
         memcpy(hin, x0, 5 * B * sizeof(double)); memcpy(hin + 5 * B, goal, 2 * B * sizeof(double));
         memcpy(hin + 7 * B, P ? P : obst, (nin - 7 * B) * sizeof(double));
         HIPCHK(hipMemcpyAsync(din, hin, nin * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        mpc::KParams p = make_params(h->cfg, batch);
-        p.x0 = din; p.goal = din + 5 * B; p.X = h->dX; p.U = h->dU;
-        if (P) p.P = din + 7 * B; else p.obst = din + 7 * B;
-        p.u0 = dout; p.cost = dout + 2 * B; p.status = (int32_t *)(dout + 3 * B); p.iters = p.status + B; p.trace = h->d_trace;
-        if (!P) p.world = make_world(h->cfg);
+        int32_t *dstat = (int32_t *)(dout + 3 * B);
+        mpc::KParams p = solve_params(h, batch, din, P ? din + 7 * B : nullptr, P ? nullptr : din + 7 * B, din + 5 * B, h->dX, h->dU, dout, dout + 2 * B, dstat, dstat + B);
         rc = launch_solve(h, p, h->stream); if (rc) return rc;
         HIPCHK(hipMemcpyAsync(hout, dout, 4 * B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1031,9 +869,7 @@ static int solve_common(mpc_handle *h, int batch, const double *x0, const double
         rc = mpc_solve_dev(h, batch, h->d_x0, h->d_P, h->d_goal, h->dX, h->dU, h->d_u0, h->d_cost, h->d_status, h->d_iters, nullptr);
     } else {        // obstacle states in: the look-ahead is computed inside the solve kernel (no P in HBM at all)
         HIPCHK(hipMemcpyAsync(h->d_obst, obst, (size_t)batch * no * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        mpc::KParams p = make_params(h->cfg, batch);
-        p.x0 = h->d_x0; p.obst = h->d_obst; p.goal = h->d_goal; p.X = h->dX; p.U = h->dU; p.world = make_world(h->cfg);
-        p.u0 = h->d_u0; p.cost = h->d_cost; p.status = h->d_status; p.iters = h->d_iters; p.trace = h->d_trace;
+        mpc::KParams p = solve_params(h, batch, h->d_x0, nullptr, h->d_obst, h->d_goal, h->dX, h->dU, h->d_u0, h->d_cost, h->d_status, h->d_iters);
         rc = launch_solve(h, p, h->stream);
     }
     if (rc) return rc;
@@ -1538,25 +1374,9 @@ int mpc_get_instance_order(mpc_handle *h, int batch, int32_t *order)
 int mpc_get_kernel_name(mpc_handle *h, int batch, int lookahead, char *buf, int len)
 {
     if (!h || !buf || len < 1) return fail(MPC_ERR_ARG, "null argument");
-    const SolvePlan q = plan_solve(h, batch, lookahead != 0);
-    const int cap = row_capacity(h->cfg.n_obst);
-    const char *masked = partial_rows(h) ? "true" : "false";      // (all template arguments, as rocprofv3 prints the instantiation)
-    if (wide_rows(h->cfg.n_obst)) {
-        const int rc = check_wide(h); if (rc) return rc;
-        snprintf(buf, (size_t)len, om_active(h) ? "rti_wide_kernel<%d, 2, %s, true, true, true>" :
-                 (ip_active(h) ? "rti_wide_kernel<%d, 2, %s, true, true>" : (ref_active(h) ? "rti_wide_kernel<%d, 2, %s, true>" : "rti_wide_kernel<%d, 2, %s>")), cap, masked);
-    }
-    else if (ref_active(h) || ip_active(h) || om_active(h)) {      // (the REF instantiations carry one more template argument, the IPAR ones two, the OSEL ones three)
-        const int rc = check_ref_mapping(h); if (rc) return rc;
-        const char *ip = om_active(h) ? ", true, true" : (ip_active(h) ? ", true" : "");
-        if (q.lps > 1) snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, false, true%s>", cap, q.lps, q.waves == 2 && !partial_rows(h) ? "true" : "false", masked, ip);
-        else snprintf(buf, (size_t)len, "rti_solve_kernel<%d, 64, 3, %s, true%s>", cap, masked, ip);
-    }
-    else if (q.lps > 1) {
-        const bool w2 = q.waves == 2 && !partial_rows(h);
-        snprintf(buf, (size_t)len, "rti_split_kernel<%d, %d, %s, %s, %s>", cap, q.lps, w2 ? "true" : "false", masked, use_block2(h, w2, partial_rows(h)) ? "true" : "false");
-    }
-    else snprintf(buf, (size_t)len, "rti_solve_kernel<%d, %d, %d, %s>", cap, q.G, q.fact, masked);
+    const mpc::SolvePlan q = plan_solve(h, batch, lookahead != 0);
+    const int rc = check_plan(h, q); if (rc) return rc;
+    mpc::format_kernel_name(q, buf, (size_t)len);      // (a name also where the table has no such row: the launch then refuses)
     return MPC_OK;
 }
 
