@@ -246,6 +246,27 @@ __device__ __forceinline__ void coord_advance(double lo, double hi, double dt, d
     if (hit) { const double a = v * t_hit, b = v * (dt - t_hit); x = x + (a - b); v = -v; }
     else { const double a = v * dt; x = x + a; }
 }
+// Four steps of coord_advance without a branch, for the stretch of a walk that stays clear of the walls: out[j] is the coordinate after step j + 1.  Returns
+// whether every one of the four steps takes coord_advance's plain arm (v == 0, or n > |v| dt (1 + 2^-50) at the coordinate the step starts from); then v keeps
+// its value, v * dt and the threshold are the same rounded products in every step, and each out[j] = RN(out[j - 1] + RN(v * dt)) is coord_advance's result bit
+// for bit.  On `false` the caller discards out[] and walks the four steps with coord_advance.  The coordinate is a chain of four additions; the distances and
+// comparisons hang off it and do not lengthen it (one exit test per four steps instead of one per step).
+__device__ __forceinline__ bool coord_advance4_clear(double lo, double hi, double dt, double x, double v, double out[4])
+{
+#pragma clang fp contract(off)
+    const double av = fabs(v);
+    const double thr = av * dt * (1.0 + 0x1p-50), a = v * dt;
+    const bool neg = v < 0, still = !(v != 0);
+    bool clear = true;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double n = neg ? x - lo : hi - x;
+        clear = clear && (still || n > thr);
+        x = x + a;
+        out[j] = x;
+    }
+    return clear;
+}
 __device__ __forceinline__ void obstacle_advance(const World w, double dt, double &x, double &vx, double &y, double &vy)
 {
     coord_advance(w.xmin, w.xmax, dt, x, vx);

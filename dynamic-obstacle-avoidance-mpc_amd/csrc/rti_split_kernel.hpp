@@ -163,6 +163,25 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     // what part q of this lane's stage holds in the variable v: from_right shifts the whole wavefront by one lane, so the owner
     // (part 0) sees its neighbours' values; only the owner's result is meaningful
     auto of_part = [&](double v, int q) { return q == 0 ? v : (q == 1 ? from_right(v) : from_right(from_right(v))); };
+    // FX: the work around the interior-point loop in the order that takes it off the wavefront's critical path -- the look-ahead walked four stages per exit
+    // test, the obstacle motion of the fused step in front of the loop, the epilogue's loads and stores grouped.  The ground-truth motion of obstacle j = lane
+    // consumes nothing the solve produces: its state is requested here, next to the iterate, advanced once the positions have been read, and waits in four words
+    // of the look-ahead's staging region per obstacle for the epilogue's stores -- no trip to global memory behind the interior point.  Not built for
+    //   W2, which stages the look-ahead inside the H~aug region (the interior point overwrites it) and already spills at 256 registers;
+    //   LPS = 2 with more than five obstacles, which sits at 256 + 256 registers with scratch: the reordered epilogue adds 8 B of scratch to one of them;
+    //   BLK2, an evidence path.
+    // These keep the order they had (same arithmetic either way: the outputs are bit for bit the same, tests/test_gpu_parity.py, test_gpu_split_fixed_cost.py).
+    constexpr bool FX = !W2 && !BLK2 && !(LPS == 2 && NOBST > 5);
+    const bool obst_step = p.obst && (p.fused & (kFusePlant | kFuseObstacles | kFuseMetrics)) && lane < nact;
+    double og[4] = {0, 0, 0, 0}, onz[2] = {0, 0};
+    if constexpr (FX) {
+        if (obst_step) {
+            const double *o = p.obst + ((size_t)inst * nact + lane) * 4;
+#pragma unroll
+            for (int c = 0; c < 4; c++) og[c] = o[c];
+            if ((p.fused & kFuseObstacles) && p.noise) { onz[0] = p.noise[((size_t)inst * nact + lane) * 2]; onz[1] = p.noise[((size_t)inst * nact + lane) * 2 + 1]; }
+        }
+    }
     // obstacle positions of this lane's obstacle rows at its stage: explicit P (parameterize_model, robot_ocp_problem.py:154-166)
     // or the look-ahead computed here (Obstacle.predict_trajectory, src/utils/visualization.py:62-79)
     double pxy[NSL][2];
@@ -173,7 +192,22 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             double q = o[c], v = (c == 0 && !p.world.bug_compat_predict) ? o[2] : o[3];      // defect D1: vx = self.vy (visualization.py:69)
             const double lo = c ? p.world.ymin : p.world.xmin, hi = c ? p.world.ymax : p.world.xmax;
             lds_P[lane] = q;
-            for (int k = 1; k <= N; k++) {
+            // four stages at a time while no walking lane comes near a wall (coord_advance4_clear: one dependent addition per stage and one exit test per
+            // four); a block in which one does is walked stage by stage, like the remainder of a horizon that is no multiple of four
+            int k = 1;
+            if constexpr (FX) {
+                for (; k + 3 <= N; k += 4) {
+                    double q4[4];
+                    if (coord_advance4_clear(lo, hi, dt, q, v, q4)) q = q4[3];
+                    else {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) { coord_advance(lo, hi, dt, q, v); q4[j] = q; }
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j++) lds_P[(k + j) * NOBST * 2 + lane] = q4[j];
+                }
+            }
+            for (; k <= N; k++) {
                 coord_advance(lo, hi, dt, q, v);
                 lds_P[k * NOBST * 2 + lane] = q;
             }
@@ -200,6 +234,18 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         if (omask == 0u) {
 #pragma unroll
             for (int s = 0; s < NSL; s++) { pxy[s][0] = 0.0; pxy[s][1] = 0.0; }
+        }
+    }
+    if constexpr (FX) {
+        if (p.obst) wave_sync();        // every lane has read its positions: words of the staging region may be written again
+        if (obst_step) {                // ground-truth motion of obstacle j = lane (Obstacle.step(), visualization.py:28-59), parked for the epilogue
+            if (p.fused & kFuseObstacles) {
+                if (p.noise) obstacle_noise(p.randomness, p.vmax, onz[0], onz[1], og[2], og[3]);
+                obstacle_advance(p.world, dt, og[0], og[2], og[1], og[3]);
+            }
+            double *w = lds_P + 4 * lane;       // 4 nact <= 2 (N + 1) NOBST words
+#pragma unroll
+            for (int c = 0; c < 4; c++) w[c] = og[c];
         }
     }
     const bool ep_done = (ep_word & 1) != 0;
@@ -1090,6 +1136,142 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         for (int c = 0; c < 5; c++) x0v[c] = xg[c];
         gl[0] = gg[0]; gl[1] = gg[1];
     }
+    if constexpr (FX) {
+        // ---- epilogue: what it reads from memory is requested first, in one group (the plant state and the goal above, the obstacle states, the accumulators, the
+        //      episode words); then the arithmetic; every store comes last, in one group, so that no wait for a load stands behind the acknowledgement of a store ----
+        const bool store = !ep_done;
+        const bool lane0s = (lane == 0) && store;
+        double ox = 0.0, oy = 0.0, ovx = 0.0, ovy = 0.0;
+        if (obst_step) {
+            const double *w = lds_P + 4 * lane;       // advanced in the prologue
+            ox = w[0]; oy = w[1]; ovx = w[2]; ovy = w[3];
+        }
+        int acc_it = 0, acc_st = 0, ep_fl = 0, ep_inc = 0;
+        double ep_mm = 0.0;
+        if (lane0s) {
+            if (p.iters_acc) acc_it = p.iters_acc[inst];
+            if (p.status_acc) acc_st = p.status_acc[inst];
+            if (p.fused & kFuseMetrics) { ep_fl = p.ep_flags[inst]; ep_mm = p.ep_min_margin[inst]; }
+        }
+        // ---- full step on the iterate; status 4 leaves it unchanged ----
+        status = ipm_finite_step<64>(status, z, lane);
+        if (status != 4) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) xi[c] += z[2 + c];
+            ui[0] += z[0]; ui[1] += z[1];
+        }
+        const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0]
+        if ((p.fused & kFuseResetOnFail) && status == 4) {      // set_initial_guess(), robot_ocp_problem.py:203-205,286-306
+            xi[0] = x0v[0]; xi[1] = x0v[1]; xi[2] = x0v[2]; xi[3] = 0.0; xi[4] = 0.0; ui[0] = ui[1] = 0.0;
+            if (p.fused & kFuseInterpGuess) interp_guess(x0v, gl[1], i <= N ? i : N, N, xi);
+        }
+        // ---- plant, obstacles, episode bookkeeping (fused closed-loop step) ----
+        const bool fused_step = (p.fused & (kFusePlant | kFuseObstacles | kFuseMetrics)) != 0;
+        double xnew[5] = {x0v[0], x0v[1], x0v[2], x0v[3], x0v[4]};
+        if (fused_step) {
+            double xp[5] = {x0v[0], x0v[1], x0v[2], x0v[3], x0v[4]};
+            if ((p.fused & kFuseAliasBug) && (p.fused & kFuseResetOnFail) && status == 4) { xp[3] = 0.0; xp[4] = 0.0; }
+#pragma unroll
+            for (int c = 0; c < 5; c++) xnew[c] = xp[c];
+            if (p.fused & kFusePlant) dyn_step<false>(xp, u_apply, dt, xnew, nullptr, nullptr);     // every lane, same value
+            double margin = INFINITY;
+            if (obst_step) {                                     // obstacle j = lane, where the prologue moved it
+                const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
+                margin = sqrt(ddx * ddx + ddy * ddy) - (IPAR ? p.ip_rhit[(size_t)inst * nact + lane] : p.r_hit);  // :222-228
+                if constexpr (OSEL) {       // an absent obstacle moves, but is not counted (kFuseMarginAll: it is)
+                    if (!OBST_ON(lane) && !(p.fused & kFuseMarginAll)) margin = INFINITY;
+                }
+            }
+            if (p.fused & kFuseMetrics) {
+                margin = -seg_max<64>(-margin, lane);
+                if (lane0s) {
+                    if (xnew[0] < p.world.xmin || xnew[0] > p.world.xmax || xnew[1] < p.world.ymin || xnew[1] > p.world.ymax) ep_fl |= 2;   // :213-214
+                    ep_mm = fmin(ep_mm, margin);
+                    if (ep_mm <= 0.0) ep_fl |= 4;
+                    const double gx_ = xnew[0] - gl[0], gy_ = xnew[1] - gl[1];
+                    if (sqrt(gx_ * gx_ + gy_ * gy_) <= p.tol_goal) ep_fl |= 1;      // :247-250: reached, the loop breaks before i += 1
+                    else ep_inc = 1;
+                }
+            }
+        }
+        // NLP objective at the returned iterate: LS cost (the stage's owner) + exact penalty of the obstacle violation (the rows' lanes)
+        double J = 0.0;
+        if (p.cost) {
+            if (act) {
+                if (IPAR && own) {
+                    double r[6];
+                    load_ref_or_goal<IPAR>(p.yref, p.ref_off, p.ref_T, inst, i, has_u, gl, r);
+                    const double wg[6] = {ipw[kIpWg], ipw[kIpWg + 1], ipw[kIpWg + 2], ipw[kIpWg + 3], ipw[kIpWg + 4], ipw[kIpWg + 5]};      // (read again: not carried)
+                    const double we[4] = {ipw[kIpWe], ipw[kIpWe + 1], ipw[kIpWe + 2], ipw[kIpWe + 3]};
+                    J = ls_cost_ref(wg, we, xi, ui, r, has_u);
+                } else if (REF && own) {
+                    const double *row = ref_row(p.yref, p.ref_off, p.ref_T, inst, i);
+                    const double r[6] = {row[0], row[1], row[2], row[3], has_u ? row[4] : 0.0, has_u ? row[5] : 0.0};
+                    J = ls_cost_ref(p.Wg, p.Weg, xi, ui, r, has_u);
+                } else if (own) {
+                    const double ex = xi[0] - gl[0], ey = xi[1] - gl[1];
+                    if (has_u) J = 0.5 * (p.Wg[0] * ex * ex + p.Wg[1] * ey * ey + p.Wg[2] * xi[3] * xi[3] + p.Wg[3] * xi[4] * xi[4]
+                                          + p.Wg[4] * ui[0] * ui[0] + p.Wg[5] * ui[1] * ui[1]);
+                    else J = 0.5 * (p.Weg[0] * ex * ex + p.Weg[1] * ey * ey + p.Weg[2] * xi[3] * xi[3] + p.Weg[3] * xi[4] * xi[4]);
+                }
+#pragma unroll
+                for (int s = 0; s < NSL; s++) if (OBST_ON(s * LPS + h)) {
+                    const double dx = xi[0] - pxy[s][0], dy = xi[1] - pxy[s][1];
+                    const double hv = dx * dx + dy * dy - ROW_R2(s);
+                    const double v = hv < 0 ? -hv : 0.0;
+                    J += zpen * (v + 0.5 * v * v);
+                }
+            }
+            J = seg_sum<64>(J, lane);
+        }
+        // ---- stores: iterate (shifted), plant state, obstacle states, episode words, u0, cost, accumulators, status, iterations ----
+        if (store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) {
+            if (p.fused & kFuseShift) {                          // X[j] <- X[j+1], U[j] <- U[j+1], U[N-1] <- 0, X[N] kept (:253-258)
+                if (act && i >= 1) {
+#pragma unroll
+                    for (int c = 0; c < 5; c++) Xg[(i - 1) * 5 + c] = xi[c];
+                }
+                if (i == N) {
+#pragma unroll
+                    for (int c = 0; c < 5; c++) Xg[N * 5 + c] = xi[c];
+                }
+                if (has_u && i >= 1) { Ug[(i - 1) * 2] = ui[0]; Ug[(i - 1) * 2 + 1] = ui[1]; }
+                if (i == 0) { Ug[(N - 1) * 2] = 0.0; Ug[(N - 1) * 2 + 1] = 0.0; }
+            } else {
+                if (act) {
+#pragma unroll
+                    for (int c = 0; c < 5; c++) Xg[i * 5 + c] = xi[c];
+                }
+                if (has_u) { Ug[i * 2] = ui[0]; Ug[i * 2 + 1] = ui[1]; }
+            }
+        }
+        if (fused_step) {
+            if ((p.fused & kFusePlant) && lane0s && p.x0_rw) {
+#pragma unroll
+                for (int c = 0; c < 5; c++) p.x0_rw[(size_t)inst * 5 + c] = xnew[c];
+            }
+            if (obst_step && (p.fused & kFuseObstacles) && store && p.obst_rw) {
+                double *w = p.obst_rw + ((size_t)inst * nact + lane) * 4;
+                w[0] = ox; w[1] = oy; w[2] = ovx; w[3] = ovy;
+            }
+            if ((p.fused & kFuseMetrics) && lane0s) {
+                p.ep_min_margin[inst] = ep_mm;
+                if (ep_inc) p.ep_steps[inst] += 1;
+                p.ep_flags[inst] = ep_fl;
+            }
+        }
+        if (lane0s) {
+            if (p.u0) { p.u0[(size_t)inst * 2] = u_apply[0]; p.u0[(size_t)inst * 2 + 1] = u_apply[1]; }
+            if (p.cost) p.cost[inst] = J;
+            if (p.iters_acc) p.iters_acc[inst] = acc_it + it_done;
+            if (p.status_acc) p.status_acc[inst] = acc_st + (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
+            if (p.status) p.status[inst] = status;
+            if (p.iters) p.iters[inst] = it_done;
+        }
+        if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
+            if ((p.fused & kFuseAdvanceRef) && lane0s && p.ref_off) p.ref_off[inst] += 1;
+        }
+    } else {        // (the order these instantiations had; not indented)
     // ---- full step on the iterate; status 4 leaves it unchanged ----
     const bool store = !ep_done;
     status = ipm_finite_step<64>(status, z, lane);
@@ -1203,6 +1385,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     }
     if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
         if ((p.fused & kFuseAdvanceRef) && lane == 0 && store && p.ref_off) p.ref_off[inst] += 1;
+    }
     }
 #ifdef MPC_PHASE_TIMING
     __builtin_amdgcn_s_waitcnt(0);

@@ -1,6 +1,6 @@
 """Condense the rocprofv3 output of scripts/profile_passes.sh into <tag>_kernel_stats.csv and <tag>_pmc_summary.json (written to
 gpurun_out/; copy them into profiles/).  Per-launch means over the launches of the solve kernel."""
-import csv, glob, json, os, sys
+import csv, glob, json, os, re, sys
 out, tag = sys.argv[1], sys.argv[2]
 root = os.path.dirname(out)
 stats = sorted(glob.glob(os.path.join(out, "stats", "**", "*kernel_stats.csv"), recursive=True))
@@ -61,5 +61,21 @@ if "SQ_INSTS_VALU_MFMA_MOPS_F64" in c and summary.get("kernel_stats"):
     d["mfma_f64_tflops"] = flops / summary["kernel_stats"]["avg_ns"] * 1e-3
     d["mfma_f64_fraction_of_peak_78.6"] = d["mfma_f64_tflops"] / 78.6
 summary["derived"] = d
+
+
+def library_name(name):
+    """the kernel as mpc_get_kernel_name prints it (solve_dispatch.hpp::format_kernel_name): the trailing REF / IPAR / OSEL arguments appear only from the first
+    `true` on, while the profiler prints every template argument -- bench.py looks its kernel up under the library's name"""
+    m = re.search(r"(rti_(split|solve|wide)_kernel)<([^>]*)>", name or "")
+    if not m:
+        return name
+    args, keep = [a.strip() for a in m.group(3).split(",")], {"split": 5, "solve": 4, "wide": 3}[m.group(2)]
+    while len(args) > keep and args[-1] == "false":
+        args.pop()
+    return name[:m.start()] + f"{m.group(1)}<{', '.join(args)}>" + name[m.end():]
+
+
+if summary["kernel"] and library_name(summary["kernel"]) != summary["kernel"]:
+    summary["kernel_profiler"], summary["kernel"] = summary["kernel"], library_name(summary["kernel"])
 json.dump(summary, open(os.path.join(root, f"{tag}_pmc_summary.json"), "w"), indent=1)
 print(json.dumps({"kernel": summary["kernel"], "stats": summary["kernel_stats"], "derived": d, "counters": sorted(c)}, indent=1))
