@@ -97,6 +97,11 @@ struct mpc_handle {
     int om_batch;                     // ... the instances they cover (a solve of more is refused)
     const uint32_t *d_omask;          // ... the words the OSEL kernels read (KParams::omask)
     uint32_t *d_omask_own;            // ... handle-owned copy of host words, max_batch, allocated on first use
+    int bd_mode;                      // per-instance box bounds (mpc_set_instance_bounds[_dev]): 0 off, 1 host arrays (packed into d_ip_b_own), 2 a device table (used in place)
+    int bd_batch;                     // ... the instances they cover (a solve of more is refused)
+    const double *d_ip_b;             // ... the packed table the IBND kernels read (KParams::ip_b), [.][kIpB]
+    double *d_ip_b_own;               // ... handle-owned table of the host form, max_batch rows, allocated on first use
+    uint32_t *d_omask_full;           // ... every obstacle present in max_batch words: what the IBND kernels (built on the masks' code) read without a mask
 };
 
 namespace {
@@ -175,8 +180,9 @@ mpc::KParams solve_params(mpc_handle *h, int batch, const double *x0, const doub
 // Lanes per instance of the one-lane-per-stage mapping: the smallest of {16, 32, 64} with N + 1 < G (an idle lane separates instances that
 // share a wavefront), or 21 -- three instances per wavefront on compact LDS blocks -- for 16 <= N <= 20 once pick_split hands a large batch
 // to this mapping; unless overridden.  Packing instances into one wavefront multiplies throughput for large batches.
-// (an obstacle mask is a run-time row count by nature: with one set, a handle whose count fills its capacity runs the run-time-count variants too)
-bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || h->om_mode != 0; }
+// (an obstacle mask is a run-time row count by nature: with one set, a handle whose count fills its capacity runs the run-time-count variants too;
+// the instance bounds are built on the masks' code, so they do the same)
+bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || h->om_mode != 0 || h->bd_mode != 0; }
 
 int pick_lanes(mpc_handle *h, int batch)
 {
@@ -266,11 +272,13 @@ int check_wide(const mpc_handle *h)
 // the same plan, the same refusals.
 // Per-instance obstacle masks (mpc_set_obstacle_mask), level 3: the IPAR instantiations with a run-time row count and one more flag -- again the same
 // mappings, plan and refusals; without instance parameters the tables they read hold the handle's own values
-int feature_level(const mpc_handle *h) { return h->om_mode != 0 ? 3 : (h->ip_mode != 0 ? 2 : (h->d_yref != nullptr ? 1 : 0)); }
+// Per-instance box bounds (mpc_set_instance_bounds), level 4: the OSEL instantiations with one more flag -- the same mappings, plan and refusals; without a
+// mask they read words of the handle's own that have every obstacle present
+int feature_level(const mpc_handle *h) { return h->bd_mode != 0 ? 4 : (h->om_mode != 0 ? 3 : (h->ip_mode != 0 ? 2 : (h->d_yref != nullptr ? 1 : 0))); }
 
 int check_feature_mapping(const mpc_handle *h)
 {
-    const char *what[] = {"", "a per-stage reference", "per-instance parameters", "an obstacle mask"};
+    const char *what[] = {"", "a per-stage reference", "per-instance parameters", "an obstacle mask", "instance bounds"};
     const char *w = what[feature_level(h)];
     if (h->use_mfma) return fail(MPC_ERR_ARG, "%s: no build for the matrix-core factorisation (mpc_set_matrix_cores)", w);
     if (!h->row_parallel) return fail(MPC_ERR_ARG, "%s: no build for the systolic sweeps (mpc_set_row_parallel(0))", w);
@@ -408,7 +416,8 @@ int alloc_instance_tables(mpc_handle *h)
 }
 
 // the handle's own values in every row of the tables: what a solve with an obstacle mask and without instance parameters reads.  A host call (it
-// waits for the handle's stream); made where the mask is set and where instance parameters are switched off under a mask, never in front of a solve
+// waits for the handle's stream); made where the mask or the instance bounds are set and where instance parameters are switched off under them, never in
+// front of a solve
 int fill_default_instance_tables(mpc_handle *h)
 {
     if (h->ip_default) return MPC_OK;
@@ -428,7 +437,8 @@ int fill_default_instance_tables(mpc_handle *h)
 }
 
 // In front of a launch that reads them: the coverage checks and kernel arguments of the per-stage reference, the per-instance tables (derived here from
-// device arrays, mode 2) and, for a solve, the obstacle mask (with it the tables are attached whether or not instance parameters are set) and the slack schedule
+// device arrays, mode 2) and, for a solve, the obstacle mask (with it the tables are attached whether or not instance parameters are set), the instance bounds
+// (which bring the tables and a mask with them) and the slack schedule
 enum AttachFor { kForSolve, kForLinearize };
 int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
 {
@@ -447,13 +457,17 @@ int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
         p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
     }
     if (what != kForSolve) return MPC_OK;
-    if (h->om_mode) {
-        if (p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
+    if (h->om_mode || h->bd_mode) {
+        if (h->om_mode && p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
         if (!h->ip_mode) {
             if (!h->ip_default) return fail(MPC_ERR_ARG, "internal: the default instance tables of the obstacle mask are not filled");
             p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
         }
-        p.omask = h->d_omask;
+        p.omask = h->om_mode ? h->d_omask : h->d_omask_full;
+    }
+    if (h->bd_mode) {
+        if (p.batch > h->bd_batch) return fail(MPC_ERR_ARG, "the instance bounds set by mpc_set_instance_bounds cover fewer instances than this solve");
+        p.ip_b = h->d_ip_b;
     }
     // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
     p.alpha = h->d_alpha;
@@ -582,7 +596,7 @@ int mpc_destroy(mpc_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
                     h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own,
-                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own};
+                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own, h->d_ip_b_own, h->d_omask_full};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->h_pack) (void)hipHostFree(h->h_pack);
@@ -1168,7 +1182,7 @@ int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const dou
     if (!h) return fail(MPC_ERR_ARG, "null handle");
     if (!W && !We && !r_safe && !r_hit) {
         h->ip_mode = 0; h->ip_batch = 0;
-        if (h->om_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
+        if (h->om_mode || h->bd_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
         return MPC_OK;
     }
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "per-instance parameters need batch in [1, max_batch]");
@@ -1202,7 +1216,7 @@ int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *
     if (!h) return fail(MPC_ERR_ARG, "null handle");
     if (!d_W && !d_We && !d_r_safe && !d_r_hit) {
         h->ip_mode = 0; h->ip_batch = 0;
-        if (h->om_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
+        if (h->om_mode || h->bd_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
         return MPC_OK;
     }
     HIPCHK(hipSetDevice(h->device));
@@ -1241,6 +1255,63 @@ int mpc_set_obstacle_mask_dev(mpc_handle *h, const uint32_t *d_mask)
     HIPCHK(hipSetDevice(h->device));
     if (!h->ip_mode) { int rc = fill_default_instance_tables(h); if (rc) return rc; }
     h->d_omask = d_mask; h->om_mode = 2; h->om_batch = h->max_batch;
+    return MPC_OK;
+}
+
+/* ---------------------------------------------- per-instance box bounds ---------------------------------------------- */
+
+// what the IBND kernels read beside the bounds when the caller has set neither: a mask with every obstacle present and the handle's own values in the
+// instance tables.  Host calls, made where the bounds are set
+static int bounds_companions(mpc_handle *h)
+{
+    if (!h->d_omask_full) {
+        const int no = h->cfg.n_obst;
+        const std::vector<uint32_t> full((size_t)h->max_batch, no >= 32 ? 0xffffffffu : ((1u << no) - 1u));
+        HIPCHK(hipMalloc(&h->d_omask_full, full.size() * sizeof(uint32_t)));
+        HIPCHK(hipMemcpyAsync(h->d_omask_full, full.data(), full.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return h->ip_mode ? MPC_OK : fill_default_instance_tables(h);
+}
+
+int mpc_set_instance_bounds(mpc_handle *h, int batch, const double *bx_lo, const double *bx_hi, const double *bu_lo, const double *bu_hi)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!bx_lo && !bx_hi && !bu_lo && !bu_hi) { h->bd_mode = 0; h->bd_batch = 0; h->d_ip_b = nullptr; return MPC_OK; }
+    if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "instance bounds need batch in [1, max_batch]");
+    struct Group { const char *lo_name, *hi_name; const double *lo, *hi, *cfg_lo, *cfg_hi; int n, lo_at, hi_at; };
+    const Group groups[2] = {{"bu_lo", "bu_hi", bu_lo, bu_hi, h->cfg.bu_lo, h->cfg.bu_hi, 2, mpc::kIpBuLo, mpc::kIpBuHi},
+                             {"bx_lo", "bx_hi", bx_lo, bx_hi, h->cfg.bx_lo, h->cfg.bx_hi, 4, mpc::kIpBxLo, mpc::kIpBxHi}};
+    std::vector<double> tab((size_t)h->max_batch * mpc::kIpB);
+    for (const Group &g : groups) {
+        for (size_t k = 0; k < (size_t)batch * g.n; k++) {
+            if (g.lo && !(g.lo[k] >= -1e300 && g.lo[k] <= 1e300)) return fail(MPC_ERR_ARG, "instance bounds: %s entries must be finite", g.lo_name);
+            if (g.hi && !(g.hi[k] >= -1e300 && g.hi[k] <= 1e300)) return fail(MPC_ERR_ARG, "instance bounds: %s entries must be finite", g.hi_name);
+        }
+        for (int b = 0; b < h->max_batch; b++)
+            for (int k = 0; k < g.n; k++) {      // (rows behind `batch` hold the handle's own values; no solve reads them)
+                const double lo = (g.lo && b < batch) ? g.lo[(size_t)b * g.n + k] : g.cfg_lo[k], hi = (g.hi && b < batch) ? g.hi[(size_t)b * g.n + k] : g.cfg_hi[k];
+                if (b < batch && !(lo < hi)) return fail(MPC_ERR_ARG, "instance bounds: %s must be below %s in every component", g.lo_name, g.hi_name);
+                tab[(size_t)b * mpc::kIpB + g.lo_at + k] = lo; tab[(size_t)b * mpc::kIpB + g.hi_at + k] = hi;
+            }
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->d_ip_b_own) HIPCHK(hipMalloc(&h->d_ip_b_own, tab.size() * sizeof(double)));
+    int rc = bounds_companions(h); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the table)
+    HIPCHK(hipMemcpyAsync(h->d_ip_b_own, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->d_ip_b = h->d_ip_b_own; h->bd_mode = 1; h->bd_batch = batch;
+    return MPC_OK;
+}
+
+int mpc_set_instance_bounds_dev(mpc_handle *h, const double *d_bounds)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!d_bounds) { h->bd_mode = 0; h->bd_batch = 0; h->d_ip_b = nullptr; return MPC_OK; }
+    HIPCHK(hipSetDevice(h->device));
+    int rc = bounds_companions(h); if (rc) return rc;
+    h->d_ip_b = d_bounds; h->bd_mode = 2; h->bd_batch = h->max_batch;
     return MPC_OK;
 }
 

@@ -107,10 +107,14 @@ struct KParams {
     const double *ip_rhit;    // [B][n_obst]: hit radius of obstacle j in the fused step's bookkeeping (margin, hit flag)
     // ---- per-instance obstacle masks (mpc_set_obstacle_mask; read only by the OSEL instantiations) ----
     const uint32_t *omask;    // [B]: bit j set = obstacle j of the instance exists (bits at and above n_obst are ignored)
+    // ---- per-instance box bounds (mpc_set_instance_bounds; read only by the IBND instantiations, which read NONE of bx_lo, bx_hi, bu_lo, bu_hi above) ----
+    const double *ip_b;       // [B][kIpB]: bu_lo[2], bu_hi[2], bx_lo[4], bx_hi[4] of an instance (bx in mpc_config's order x, y, v, om)
 };
 
 // Layout of one row of KParams::ip_w
 enum : int { kIpHs = 0, kIpHt = 7, kIpWg = 12, kIpWe = 18, kIpW = 22 };
+// Layout of one row of KParams::ip_b
+enum : int { kIpBuLo = 0, kIpBuHi = 2, kIpBxLo = 4, kIpBxHi = 8, kIpB = 12 };
 // The per-instance tables are never written by a solve kernel: they are read through the constant address space, so that a wave-uniform row (one
 // instance per wavefront or per workgroup in every IPAR mapping) is a handful of scalar loads and the values stay in scalar registers
 typedef const __attribute__((address_space(4))) double IpConst;
@@ -2161,9 +2165,12 @@ __device__ __forceinline__ void systolic_rollout(int stage, int N, const StageLi
 // constants Hd_stage, Hd_term, Wg, Weg, r2, r_hit.  Built on the REF code (load_ref_or_goal), so one family serves solves with and without a reference
 // OSEL: per-instance obstacle masks (KParams::omask; mpc_set_obstacle_mask): the rows of obstacle j exist iff bit j of the instance's word is set; an absent
 // slot replicates the highest present obstacle (zero with an empty word), as the slots beyond the count replicate the last one.  Built on the MASKED IPAR code
-template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false>
+// IBND: per-instance box bounds (KParams::ip_b; mpc_set_instance_bounds): lo[] / hi[] are the instance's row of the table, at the start and in every
+// reload_bounds(), in place of the kernel-argument bounds.  Built on the OSEL code
+template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false>
 __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 {
+    static_assert(!IBND || OSEL, "the per-instance bounds are built on the obstacle masks' code");
     static_assert(!REF || (G == 64 && FACT == 3), "the per-stage reference runs on one instance per wavefront, compact stage blocks");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
     static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
@@ -2397,6 +2404,14 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     const bool vbu = has_u, vbx = xb;            // input-box rows (k < 2) / state-box rows (k >= 2) present at this stage
     double lo[NB] = {p.bu_lo[0], p.bu_lo[1], p.bx_lo[0], p.bx_lo[1], p.bx_lo[2], p.bx_lo[3]};
     double hi[NB] = {p.bu_hi[0], p.bu_hi[1], p.bx_hi[0], p.bx_hi[1], p.bx_hi[2], p.bx_hi[3]};
+    // IBND: the instance's row of the bounds table instead (one instance per wavefront: scalar loads)
+    if constexpr (IBND) {
+        IpConst *pb = ip_const(p.ip_b, (size_t)inst * kIpB);
+#pragma unroll
+        for (int k = 0; k < 2; k++) { lo[k] = pb[kIpBuLo + k]; hi[k] = pb[kIpBuHi + k]; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) { lo[2 + k] = pb[kIpBxLo + k]; hi[2 + k] = pb[kIpBxHi + k]; }
+    }
     // Inside the interior point the wave-uniform constants of the problem (12 bounds, 22 cost weights: 68 scalar registers) are RE-READ from the
     // kernel-argument segment at the head of every phase that uses them -- three scalar loads -- instead of staying live across the sweeps: held in
     // scalar registers they do not fit next to the lane masks and LDS addresses (102 registers), and every spilled one comes back through a
@@ -2407,6 +2422,15 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 #ifdef MPC_NO_RELOAD      // diagnostic build: the constants stay in (spilled) scalar registers, as in round 2
         return;
 #endif
+        if constexpr (IBND) {      // the instance's row, through an opaque copy of its address per phase: re-read like the arguments, not kept across the sweeps
+            IpConst *pb = ip_const(p.ip_b, (size_t)inst * kIpB);
+            asm volatile("" : "+s"(pb));
+#pragma unroll
+            for (int k = 0; k < 2; k++) { lo[k] = pb[kIpBuLo + k]; hi[k] = pb[kIpBuHi + k]; }
+#pragma unroll
+            for (int k = 0; k < 4; k++) { lo[2 + k] = pb[kIpBxLo + k]; hi[2 + k] = pb[kIpBxHi + k]; }
+            return;
+        }
         KArg *pk = (KArg *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(pk));
         lo[0] = pk->bu_lo[0]; lo[1] = pk->bu_lo[1]; hi[0] = pk->bu_hi[0]; hi[1] = pk->bu_hi[1];

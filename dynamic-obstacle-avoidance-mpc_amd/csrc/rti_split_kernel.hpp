@@ -62,9 +62,12 @@ __device__ __forceinline__ double nth_of_six(double a0, double a1, double a2, do
 // OSEL: per-instance obstacle masks (KParams::omask; mpc_set_obstacle_mask): obstacle j of the instance exists iff bit j of its word is set.  "j < nact"
 // becomes the bit test wherever a row, a cost term or a margin depends on it; the position and radius of an absent slot are those of the highest present
 // obstacle (zero with an empty word), so nothing an absent entry of P / obst holds is ever read into the row state.  Built on the MASKED IPAR code
-template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false>
+// IBND: per-instance box bounds (KParams::ip_b; mpc_set_instance_bounds): the lo / hi of a box row come from the instance's row of the table (scalar loads)
+// in place of the kernel-argument bounds; they are consumed where the rows are initialised and not carried.  Built on the OSEL code
+template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false>
 __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 {
+    static_assert(!IBND || OSEL, "the per-instance bounds are built on the obstacle masks' code");
     static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
     static_assert(!REF || !BLK2, "the per-stage reference is not built for the block-2 recursions");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
@@ -380,12 +383,20 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     // ... and the squared radius of the obstacle of row slot s (rows beyond the count replicate the last obstacle, as their positions do): read where it is
     // used, here and in the cost at the end, not carried in between
 #define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + (OSEL ? OBST_IN((s) * LPS + h) : ((s) * LPS + h < nact ? (s) * LPS + h : nact - 1))] : p.r2)
+    // IBND: this instance's row of the bounds table, read the same way
+    IpConst *const ipb = IBND ? ip_const(p.ip_b, (size_t)__builtin_amdgcn_readfirstlane(inst) * kIpB) : nullptr;
     {
         auto slot_init = [&](auto sc) {     // slot index as a compile-time constant
             constexpr int s = decltype(sc)::value;
             const double val = part_of(sc, ui[0], ui[1], xi[0], xi[1], xi[3], xi[4]);
-            const double lo = part_of(sc, p.bu_lo[0], p.bu_lo[1], p.bx_lo[0], p.bx_lo[1], p.bx_lo[2], p.bx_lo[3]);
-            const double hi = part_of(sc, p.bu_hi[0], p.bu_hi[1], p.bx_hi[0], p.bx_hi[1], p.bx_hi[2], p.bx_hi[3]);
+            double lo, hi;      // (IBND in a branch of its own, like IPAR below)
+            if constexpr (IBND) {
+                lo = part_of(sc, ipb[kIpBuLo + 0], ipb[kIpBuLo + 1], ipb[kIpBxLo + 0], ipb[kIpBxLo + 1], ipb[kIpBxLo + 2], ipb[kIpBxLo + 3]);
+                hi = part_of(sc, ipb[kIpBuHi + 0], ipb[kIpBuHi + 1], ipb[kIpBxHi + 0], ipb[kIpBxHi + 1], ipb[kIpBxHi + 2], ipb[kIpBxHi + 3]);
+            } else {
+                lo = part_of(sc, p.bu_lo[0], p.bu_lo[1], p.bx_lo[0], p.bx_lo[1], p.bx_lo[2], p.bx_lo[3]);
+                hi = part_of(sc, p.bu_hi[0], p.bu_hi[1], p.bx_hi[0], p.bx_hi[1], p.bx_hi[2], p.bx_hi[3]);
+            }
             const bool is_u = part_of(sc, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0) != 0.0;
             bp[s] = act && (is_u ? has_u : xb);
             // (IPAR in branches of their own, statement for statement: wrapped in one expression with the kernel arguments, or in another order, the arguments'

@@ -61,10 +61,12 @@ __device__ __forceinline__ void group_sync()
 // MASKED: fewer obstacles than row pairs (p.n_obst < CAP): the run-time count, as in rti_split_kernel
 // IPAR: per-instance cost constants and per-obstacle radii, as in rti_split_kernel (built on the REF code)
 // OSEL: per-instance obstacle masks, as in rti_split_kernel (the word is the same in every wavefront of the workgroup)
-template <int CAP, int LPS, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false>
+// IBND: per-instance box bounds, as in rti_split_kernel (the row is the same in every wavefront of the workgroup)
+template <int CAP, int LPS, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false>
 __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(const KParams p)
 {
     static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
+    static_assert(!IBND || OSEL, "the per-instance bounds are built on the obstacle masks' code");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
     static_assert(LPS == 2, "two lanes per horizon stage (N <= 31)");
     constexpr int W = WideShape<CAP>::W, KW = WideShape<CAP>::K;
@@ -251,12 +253,20 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     IpConst *const ipw = IPAR ? ip_const(p.ip_w, (size_t)__builtin_amdgcn_readfirstlane(inst) * kIpW) : nullptr;
     // ... and the squared radius of the obstacle of row slot s of this wavefront (rows beyond the count replicate the last obstacle, as their positions do)
 #define ROW_R2(s) (IPAR ? p.ip_r2[(size_t)inst * nact + (OSEL ? OBST_IN(wv * KW + (s) * LPS + h) : (wv * KW + (s) * LPS + h < nact ? wv * KW + (s) * LPS + h : nact - 1))] : p.r2)
+    // IBND: this instance's row of the bounds table, read the same way
+    IpConst *const ipb = IBND ? ip_const(p.ip_b, (size_t)__builtin_amdgcn_readfirstlane(inst) * kIpB) : nullptr;
     {
         auto slot_init = [&](auto sc) {
             constexpr int s = decltype(sc)::value;
             const double val = part_of(sc, ui[0], ui[1], xi[0], xi[1], xi[3], xi[4]);
-            const double lo = part_of(sc, p.bu_lo[0], p.bu_lo[1], p.bx_lo[0], p.bx_lo[1], p.bx_lo[2], p.bx_lo[3]);
-            const double hi = part_of(sc, p.bu_hi[0], p.bu_hi[1], p.bx_hi[0], p.bx_hi[1], p.bx_hi[2], p.bx_hi[3]);
+            double lo, hi;      // (IBND in a branch of its own, like IPAR below)
+            if constexpr (IBND) {
+                lo = part_of(sc, ipb[kIpBuLo + 0], ipb[kIpBuLo + 1], ipb[kIpBxLo + 0], ipb[kIpBxLo + 1], ipb[kIpBxLo + 2], ipb[kIpBxLo + 3]);
+                hi = part_of(sc, ipb[kIpBuHi + 0], ipb[kIpBuHi + 1], ipb[kIpBxHi + 0], ipb[kIpBxHi + 1], ipb[kIpBxHi + 2], ipb[kIpBxHi + 3]);
+            } else {
+                lo = part_of(sc, p.bu_lo[0], p.bu_lo[1], p.bx_lo[0], p.bx_lo[1], p.bx_lo[2], p.bx_lo[3]);
+                hi = part_of(sc, p.bu_hi[0], p.bu_hi[1], p.bx_hi[0], p.bx_hi[1], p.bx_hi[2], p.bx_hi[3]);
+            }
             const bool is_u = part_of(sc, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0) != 0.0;
             bp[s] = w0 && act && (is_u ? has_u : xb);
             // (IPAR in branches of their own, statement for statement: wrapped in one expression with the kernel arguments, or in another order, the arguments'

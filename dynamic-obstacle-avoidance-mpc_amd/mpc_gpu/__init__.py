@@ -5,7 +5,7 @@ C ABI of include/mpc_gpu.h (libmpcgpu.so).  There is no CPU fallback.
 """
 from . import _lib
 from ._lib import MpcConfig, MpcError, build, default_config
-from .solver import BatchedMpc, pack_obstacle_mask, unpack_obstacle_mask
+from .solver import BatchedMpc, pack_instance_bounds, pack_obstacle_mask, unpack_obstacle_mask
 from .api import solve, get_solver
 from .world import Obstacle, generate_random_moving_obstacles, obstacle_states
 from .acados_shim import AcadosOcpSolverShim, AcadosSimSolverShim
@@ -13,6 +13,6 @@ from .closed_loop import RobotOcpProblem
 from .episodes import run_episodes, visualisation_inputs, write_experiment
 from .experiments import run_grid
 
-__all__ = ["MpcConfig", "MpcError", "build", "default_config", "BatchedMpc", "pack_obstacle_mask", "unpack_obstacle_mask", "solve", "get_solver", "Obstacle",
+__all__ = ["MpcConfig", "MpcError", "build", "default_config", "BatchedMpc", "pack_obstacle_mask", "unpack_obstacle_mask", "pack_instance_bounds", "solve", "get_solver", "Obstacle",
            "generate_random_moving_obstacles", "obstacle_states", "AcadosOcpSolverShim", "AcadosSimSolverShim",
            "RobotOcpProblem", "run_episodes", "visualisation_inputs", "write_experiment", "run_grid"]

@@ -71,6 +71,8 @@ SYMBOLS = {
     "mpc_set_instance_params_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mpc_set_obstacle_mask": (C.c_int, [_vp, C.c_int, _vp]),
     "mpc_set_obstacle_mask_dev": (C.c_int, [_vp, _vp]),
+    "mpc_set_instance_bounds": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "mpc_set_instance_bounds_dev": (C.c_int, [_vp, _vp]),
     "mpc_plant_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "mpc_predict": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "mpc_solve_dev": (C.c_int, [_vp, C.c_int] + [_vp] * 10),

@@ -18,7 +18,7 @@ from .solver import BatchedMpc
 
 def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, init_guess_when_error=True,
                  bug_compat_alias=True, seed=0, device=0, solver=None, n_obst=5, first_seed=0, record=False, noise=None,
-                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, active=None, margin_all=False, **cfg):
+                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, active=None, margin_all=False, bounds=None, **cfg):
     """x0 (B,5), goal (B,2), obst (B,n_obst,4) -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): instance s then starts
     from the reference generator's draw for np.random.seed(first_seed + s), produced on the device (experiments.py:26-29).
     record=True also returns simX (steps+1,B,5), obst_traj (steps+1,B,n_obst,4) and pred (steps,B,N+1,5): what the reference keeps
@@ -43,6 +43,8 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     active: optional bool (B, n_obst) (BatchedMpc.set_obstacle_mask): obstacle j exists for episode b only where active[b, j]; the absent ones still
     move (and draw their noise) but are neither solved against nor, unless margin_all, counted in the margin and the hit flag.  Masked episodes are
     not compacted.
+    bounds: optional dict(bx_lo=, bx_hi=, bu_lo=, bu_hi=) of per-instance box bounds, (B, 4) / (B, 2) or one row for all (BatchedMpc.set_instance_bounds):
+    episode b is solved inside its own actuator and speed limits.  Episodes with bounds of their own are not compacted.
     Returns dict(table (B,6), x_last (B,5), steps_run, solves)."""
     import torch
     x0 = np.ascontiguousarray(x0, dtype=np.float64); B = x0.shape[0]
@@ -69,6 +71,9 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     own_mask = active is not None
     if own_mask:
         m.set_obstacle_mask(np.asarray(active))
+    own_bounds = bounds is not None
+    if own_bounds:
+        m.set_instance_bounds(**bounds)
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
         t = lambda a: torch.from_numpy(a.copy()).to(dev)
@@ -110,7 +115,7 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             dnoise = torch.from_numpy(noise).to(dev)
         k = 0
         # compaction of finished episodes (compact_from): results of parked episodes live in full-size arrays, `ids` maps the live batch to them
-        compact = compact_from is not None and B >= compact_from and not record and not status_log and not own_radii and not own_mask
+        compact = compact_from is not None and B >= compact_from and not record and not status_log and not own_radii and not own_mask and not own_bounds
         B0 = B
         if compact:
             ids = torch.arange(B, device=dev)
@@ -179,6 +184,8 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             m.set_instance_params()
         if own_mask:
             m.set_obstacle_mask(None)
+        if own_bounds:
+            m.set_instance_bounds()
     return dict(table=table, x_last=xl, steps_run=k, solves=int(steps.sum().item()) + int((fl_h & 1).sum()), **extra)
 
 

@@ -107,6 +107,20 @@ class PipelinedMpc:
         for lo, hi, m, _ in self.parts:
             m.set_obstacle_mask(self._sl(mask, lo, hi))
 
+    def set_instance_bounds(self, bx_lo=None, bx_hi=None, bu_lo=None, bu_hi=None):
+        """per-instance box bounds (BatchedMpc.set_instance_bounds) from host arrays of max_batch rows, (max_batch, 4) / (max_batch, 2): every sub-handle
+        gets its rows; a single row (4,) / (2,) goes to every sub-handle as it is; all None switches the feature off"""
+        import numpy as np
+        cut = lambda a, lo, hi: a if a is None or np.ndim(a) == 1 else np.asarray(a)[lo:hi]
+        for lo, hi, m, _ in self.parts:
+            m.set_instance_bounds(cut(bx_lo, lo, hi), cut(bx_hi, lo, hi), cut(bu_lo, lo, hi), cut(bu_hi, lo, hi))
+
+    def set_instance_bounds_dev(self, table=None):
+        """per-instance box bounds from ONE packed device tensor (max_batch, 12) (pack_instance_bounds): every sub-handle gets its contiguous slice, used
+        in place (rewrite the rows on the device at will); None switches the feature off"""
+        for lo, hi, m, _ in self.parts:
+            m.set_instance_bounds_dev(self._sl(table, lo, hi))
+
     # ------------------------------------------------------------------ the cost exchange lives on the first sub-batch's handle (include/mpc_gpu.h mpc_comm_*)
     def comm_init(self, rank, world, unique_id):
         self.parts[0][2].comm_init(rank, world, unique_id)

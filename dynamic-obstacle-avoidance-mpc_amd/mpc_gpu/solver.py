@@ -47,6 +47,37 @@ def unpack_obstacle_mask(words, n_obst):
     return ((w[:, None] >> np.arange(int(n_obst), dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
 
 
+# one row of the packed bounds table of mpc_set_instance_bounds_dev: (name, first column, columns)
+BOUNDS_ROW = (("bu_lo", 0, 2), ("bu_hi", 2, 2), ("bx_lo", 4, 4), ("bx_hi", 8, 4))
+BOUNDS_COLS = 12
+
+
+def _bounds_group(name, a, cols, B=None):
+    """one group of instance bounds as a float64 (B, cols) array; a single row (cols,) is broadcast to B rows (B None: stays one row)"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 1:
+        if a.shape != (cols,):
+            raise ValueError(f"{name} must be (B, {cols}) or ({cols},), got {a.shape}")
+        a = np.tile(a[None, :], (1 if B is None else B, 1))
+    if a.ndim != 2 or a.shape[1] != cols:
+        raise ValueError(f"{name} must be (B, {cols}) or ({cols},), got {a.shape}")
+    if B is not None and a.shape[0] != B:
+        raise ValueError(f"{name} has {a.shape[0]} rows, expected {B}")
+    return np.ascontiguousarray(a)
+
+
+def pack_instance_bounds(cfg, B, bx_lo=None, bx_hi=None, bu_lo=None, bu_hi=None):
+    """The packed table of mpc_set_instance_bounds_dev on the host: float64 (B, 12), a row being bu_lo[2], bu_hi[2], bx_lo[4], bx_hi[4] (bx in the
+    order of mpc_config: x, y, v, omega).  Each group is (B, cols) or one row (cols,) for every instance; None takes cfg's value (an MpcConfig)."""
+    B = int(B)
+    given = dict(bx_lo=bx_lo, bx_hi=bx_hi, bu_lo=bu_lo, bu_hi=bu_hi)
+    tab = np.empty((B, BOUNDS_COLS))
+    for name, at, cols in BOUNDS_ROW:
+        a = given[name]
+        tab[:, at:at + cols] = _bounds_group(name, list(getattr(cfg, name)) if a is None else a, cols, B)
+    return tab
+
+
 class BatchedMpc:
     # lanes per horizon stage / wavefronts per SIMD / lanes per instance applied to every new handle (0 = automatic); test / tuning hooks,
     # also settable from the environment for profiling runs of unmodified programs (MPC_LANES_PER_STAGE, MPC_WAVES_PER_SIMD, MPC_LANES_PER_INSTANCE)
@@ -238,6 +269,31 @@ class BatchedMpc:
             if tuple(active.shape) != (self.max_batch,) or str(active.dtype) not in ("torch.int32", "torch.uint32") or not active.is_contiguous():
                 raise ValueError(f"a device obstacle mask must be a contiguous int32 / uint32 tensor ({self.max_batch},)")
             _lib.check(_lib.lib().mpc_set_obstacle_mask_dev(self._h, _ptr(active)))
+
+    def set_instance_bounds(self, bx_lo=None, bx_hi=None, bu_lo=None, bu_hi=None):
+        """Per-instance box bounds (include/mpc_gpu.h mpc_set_instance_bounds): instance b solves with the state box bx_lo[b] .. bx_hi[b] (4,) in the order
+        of mpc_config (x, y, v, omega) and the input box bu_lo[b] .. bu_hi[b] (2,).  numpy arrays (B, 4) / (B, 2), validated and copied; a single row
+        (4,) / (2,) is broadcast to the batch (max_batch when no group has rows of its own).  A group left None keeps the handle's value; all None
+        switches the feature off."""
+        given = dict(bx_lo=bx_lo, bx_hi=bx_hi, bu_lo=bu_lo, bu_hi=bu_hi)
+        if all(a is None for a in given.values()):
+            _lib.check(_lib.lib().mpc_set_instance_bounds(self._h, 0, None, None, None, None))
+            return
+        cols = {name: c for name, _, c in BOUNDS_ROW}
+        rows = [np.asarray(a).shape[0] for a in given.values() if a is not None and np.asarray(a).ndim == 2]
+        B = rows[0] if rows else self.max_batch
+        arr = {name: (None if a is None else _bounds_group(name, a, cols[name], B)) for name, a in given.items()}
+        _lib.check(_lib.lib().mpc_set_instance_bounds(self._h, int(B), _ptr(arr["bx_lo"]), _ptr(arr["bx_hi"]), _ptr(arr["bu_lo"]), _ptr(arr["bu_hi"])))
+
+    def set_instance_bounds_dev(self, table):
+        """The packed device form (mpc_set_instance_bounds_dev): a contiguous float64 device tensor (max_batch, 12) in the layout of pack_instance_bounds,
+        used in place and not validated (the values it holds when a solve is launched; rewrite them on the device at will); None switches off."""
+        if table is None:
+            _lib.check(_lib.lib().mpc_set_instance_bounds_dev(self._h, None))
+            return
+        if tuple(table.shape) != (self.max_batch, BOUNDS_COLS) or str(table.dtype) != "torch.float64" or not table.is_contiguous():
+            raise ValueError(f"a device bounds table must be a contiguous float64 tensor ({self.max_batch}, {BOUNDS_COLS})")
+        _lib.check(_lib.lib().mpc_set_instance_bounds_dev(self._h, _ptr(table)))
 
     def plant_step(self, x, u):
         """ocp_integrator set/solve/get, robot_ocp_problem.py:207-212."""

@@ -209,6 +209,24 @@ int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *
 int mpc_set_obstacle_mask(mpc_handle *h, int batch, const uint32_t *mask);
 int mpc_set_obstacle_mask_dev(mpc_handle *h, const uint32_t *d_mask);
 
+/* Per-instance box bounds: bx_lo[batch][4] and bx_hi[batch][4] in the order of mpc_config.bx_lo / .bx_hi (x, y, v, omega), bu_lo[batch][2] and
+ * bu_hi[batch][2] (u_a, u_alpha); one batch then holds robots with different actuator and speed limits.  Any pointer may be NULL: that group keeps the
+ * handle's mpc_config value for every instance; all four NULL switch the feature off and the handle runs the kernels it ran before.  Instance b then
+ * solves with its own boxes at every place a solve reads one (the input box of stages 0 .. N-1, the state box of stages 1 .. N-1 and, with bx_terminal,
+ * N).  bx_terminal, arena and every other mpc_config field stay per handle; x0 is not boxed, so an instance whose x0 lies outside its own box gets the
+ * status the usual rules give.  The plant step, the bookkeeping of the fused step, the reported cost and mpc_linearize_dev read no bound.
+ * Host arrays, validated (batch in [1, max_batch], every entry finite, lo < hi in every component -- against the handle's value where only one side is
+ * given; MPC_ERR_ARG with the field's name otherwise, and nothing is switched on) and copied; applies to every following solve (mpc_solve,
+ * mpc_solve_obst, mpc_solve_dev, mpc_closed_loop_step_dev) of the first `batch` instances until replaced; a solve of more instances is refused.
+ * _dev: one packed device table d_bounds[max_batch][12], a row being bu_lo[2], bu_hi[2], bx_lo[4], bx_hi[4], used in place and not validated: a solve
+ * reads the values when it is launched (no kernel runs in front of it), so a caller may rewrite them on the device between steps with no host call.
+ * NULL switches the feature off.
+ * Works together with mpc_set_reference, mpc_set_instance_params, mpc_set_obstacle_mask, explicit P, the in-kernel look-ahead and every flag of the
+ * fused step.  Mappings and refusals are those of mpc_set_obstacle_mask (above), on the run-time-row-count kernels; switching the bounds off returns
+ * the handle to the kernels and results it had. */
+int mpc_set_instance_bounds(mpc_handle *h, int batch, const double *bx_lo, const double *bx_hi, const double *bu_lo, const double *bu_hi);
+int mpc_set_instance_bounds_dev(mpc_handle *h, const double *d_bounds);
+
 /* Plant integrator, ocp_integrator.set/solve/get, robot_ocp_problem.py:207-212 (same IRK as the OCP) */
 int mpc_plant_step(mpc_handle *h, int batch, const double *x, const double *u, double *x_next);
 /* Obstacle look-ahead only: obst[B][n_obst][4] -> P[B][N+1][n_obst][2] (visualization.py:62-79) */
