@@ -303,6 +303,55 @@ __device__ __forceinline__ void obstacle_noise(double randomness, double vmax, d
     vy = fmin(fmax(fy * vy, -vmax), vmax);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The solve tail: what every solve kernel does behind its interior-point loop -- the full step on the iterate, the reset of a failed solve, the (shifted)
+// store of the iterate, the fused closed-loop step, the NLP cost, the result stores.  rti_solve_kernel, both orders of rti_split_kernel and rti_wide_kernel
+// string it together in their own order, around their own reductions and with their own idea of "lane 0 of the instance".  The pieces below are the part
+// of it that is written ONCE: a change to one of them is made here (DESIGN.md section 4f says which tail takes which, and why the rest of the tail is
+// still four texts).  They take values and pointers, never KParams: the one-lane kernel hands them the kernel arguments it reads again behind the loop.
+// ------------------------------------------------------------------------------------------------------------------
+// full step on the iterate; status 4 leaves it unchanged
+__device__ __forceinline__ void tail_full_step(int status, const double z[7], double xi[5], double ui[2])
+{
+    if (status != 4) {
+#pragma unroll
+        for (int c = 0; c < 5; c++) xi[c] += z[2 + c];
+        ui[0] += z[0]; ui[1] += z[1];
+    }
+}
+// a failed solve starts over from set_initial_guess(), robot_ocp_problem.py:203-205,286-306 (behind the read of u* = U[0], which is the caller's)
+__device__ __forceinline__ void tail_reset_on_fail(int fused, int status, const double x0v[5], double goal_y, int i, int N, double xi[5], double ui[2])
+{
+    if ((fused & kFuseResetOnFail) && status == 4) {
+        xi[0] = x0v[0]; xi[1] = x0v[1]; xi[2] = x0v[2]; xi[3] = 0.0; xi[4] = 0.0; ui[0] = ui[1] = 0.0;
+        if (fused & kFuseInterpGuess) interp_guess(x0v, goal_y, i <= N ? i : N, N, xi);
+    }
+}
+// one stage's (xi, ui) into the instance's iterate (Xg, Ug), in place or shifted by one stage; the caller decides whether this lane stores its stage
+__device__ __forceinline__ void tail_store_iterate(int fused, int i, int N, bool act, bool has_u, const double xi[5], const double ui[2], double *Xg, double *Ug)
+{
+    if (fused & kFuseShift) {                          // X[j] <- X[j+1], U[j] <- U[j+1], U[N-1] <- 0, X[N] kept (:253-258)
+        if (act && i >= 1) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) Xg[(i - 1) * 5 + c] = xi[c];
+        }
+        if (i == N) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) Xg[N * 5 + c] = xi[c];
+        }
+        if (has_u && i >= 1) { Ug[(i - 1) * 2] = ui[0]; Ug[(i - 1) * 2 + 1] = ui[1]; }
+        if (i == 0) { Ug[(N - 1) * 2] = 0.0; Ug[(N - 1) * 2 + 1] = 0.0; }
+    } else {
+        if (act) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) Xg[i * 5 + c] = xi[c];
+        }
+        if (has_u) { Ug[i * 2] = ui[0]; Ug[i * 2 + 1] = ui[1]; }
+    }
+}
+// what a solve adds to KParams::status_acc
+__device__ __forceinline__ int tail_status_acc_word(int status) { return (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0); }
+
 // Wavefront reductions with DPP (no LDS crossbar, no waits): four row-local butterfly steps, then the four row totals
 // are combined through v_readlane.  The result is wave-uniform.
 template <int CTRL>
@@ -3479,7 +3528,9 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     const double t_Wg[6] = {pt->Wg[0], pt->Wg[1], pt->Wg[2], pt->Wg[3], pt->Wg[4], pt->Wg[5]}, t_Weg[4] = {pt->Weg[0], pt->Weg[1], pt->Weg[2], pt->Weg[3]};
     IpConst *const t_ipr2 = IPAR ? ip_const(pt->ip_r2, (size_t)inst * nact) : nullptr;      // (IPAR: the tail's own reads of the per-instance tables)
     const double *const t_ip_rhit = IPAR ? pt->ip_rhit : nullptr;
-    // ---- full step on the iterate; status 4 leaves it unchanged ----
+    // ---- full step on the iterate; status 4 leaves it unchanged: the solve tail, shared pieces tail_* above ----
+    // (the step and the iterate's store stay written out here: through tail_full_step / tail_store_iterate the compiler commutes one v_add_f64 of the interior
+    // point in 8 resp. 17 instantiations, e.g. rti_solve_kernel<5, 64, 2, true>, listing line 3420 -- same length, same registers, not the same text)
     const bool store = valid && !ep_done;
     status = ipm_finite_step<G>(status, z, lane);
     if (status != 4) {
@@ -3488,10 +3539,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
         ui[0] += z[0]; ui[1] += z[1];
     }
     const double u_apply[2] = {lane_value_seg<G>(ui[0], lane), lane_value_seg<G>(ui[1], lane)};   // u* = U[0] of this instance
-    if ((t_fused & kFuseResetOnFail) && status == 4) {      // set_initial_guess(), robot_ocp_problem.py:203-205,286-306
-        xi[0] = x0v[0]; xi[1] = x0v[1]; xi[2] = x0v[2]; xi[3] = 0.0; xi[4] = 0.0; ui[0] = ui[1] = 0.0;
-        if (t_fused & kFuseInterpGuess) interp_guess(x0v, gl[1], i <= N ? i : N, N, xi);
-    }
+    tail_reset_on_fail(t_fused, status, x0v, gl[1], i, N, xi, ui);
     if (store && (status != 4 || (t_fused & (kFuseResetOnFail | kFuseShift)))) {
         if (t_fused & kFuseShift) {                          // X[j] <- X[j+1], U[j] <- U[j+1], U[N-1] <- 0, X[N] kept (:253-258)
             if (act && i >= 1) {
@@ -3596,7 +3644,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     }
     if (i == 0 && store) {
         if (t_iters_acc) t_iters_acc[inst] += it_done;
-        if (t_status_acc) t_status_acc[inst] += (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
+        if (t_status_acc) t_status_acc[inst] += tail_status_acc_word(status);
         if (t_status) t_status[inst] = status;
         if (t_iters) t_iters[inst] = it_done;
     }

@@ -1164,18 +1164,11 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             if (p.status_acc) acc_st = p.status_acc[inst];
             if (p.fused & kFuseMetrics) { ep_fl = p.ep_flags[inst]; ep_mm = p.ep_min_margin[inst]; }
         }
-        // ---- full step on the iterate; status 4 leaves it unchanged ----
+        // ---- full step on the iterate; status 4 leaves it unchanged: the solve tail, shared pieces tail_* (rti_kernel.hpp) ----
         status = ipm_finite_step<64>(status, z, lane);
-        if (status != 4) {
-#pragma unroll
-            for (int c = 0; c < 5; c++) xi[c] += z[2 + c];
-            ui[0] += z[0]; ui[1] += z[1];
-        }
+        tail_full_step(status, z, xi, ui);
         const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0]
-        if ((p.fused & kFuseResetOnFail) && status == 4) {      // set_initial_guess(), robot_ocp_problem.py:203-205,286-306
-            xi[0] = x0v[0]; xi[1] = x0v[1]; xi[2] = x0v[2]; xi[3] = 0.0; xi[4] = 0.0; ui[0] = ui[1] = 0.0;
-            if (p.fused & kFuseInterpGuess) interp_guess(x0v, gl[1], i <= N ? i : N, N, xi);
-        }
+        tail_reset_on_fail(p.fused, status, x0v, gl[1], i, N, xi, ui);
         // ---- plant, obstacles, episode bookkeeping (fused closed-loop step) ----
         const bool fused_step = (p.fused & (kFusePlant | kFuseObstacles | kFuseMetrics)) != 0;
         double xnew[5] = {x0v[0], x0v[1], x0v[2], x0v[3], x0v[4]};
@@ -1236,26 +1229,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             J = seg_sum<64>(J, lane);
         }
         // ---- stores: iterate (shifted), plant state, obstacle states, episode words, u0, cost, accumulators, status, iterations ----
-        if (store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) {
-            if (p.fused & kFuseShift) {                          // X[j] <- X[j+1], U[j] <- U[j+1], U[N-1] <- 0, X[N] kept (:253-258)
-                if (act && i >= 1) {
-#pragma unroll
-                    for (int c = 0; c < 5; c++) Xg[(i - 1) * 5 + c] = xi[c];
-                }
-                if (i == N) {
-#pragma unroll
-                    for (int c = 0; c < 5; c++) Xg[N * 5 + c] = xi[c];
-                }
-                if (has_u && i >= 1) { Ug[(i - 1) * 2] = ui[0]; Ug[(i - 1) * 2 + 1] = ui[1]; }
-                if (i == 0) { Ug[(N - 1) * 2] = 0.0; Ug[(N - 1) * 2 + 1] = 0.0; }
-            } else {
-                if (act) {
-#pragma unroll
-                    for (int c = 0; c < 5; c++) Xg[i * 5 + c] = xi[c];
-                }
-                if (has_u) { Ug[i * 2] = ui[0]; Ug[i * 2 + 1] = ui[1]; }
-            }
-        }
+        if (store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) tail_store_iterate(p.fused, i, N, act, has_u, xi, ui, Xg, Ug);
         if (fused_step) {
             if ((p.fused & kFusePlant) && lane0s && p.x0_rw) {
 #pragma unroll
@@ -1275,7 +1249,8 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             if (p.u0) { p.u0[(size_t)inst * 2] = u_apply[0]; p.u0[(size_t)inst * 2 + 1] = u_apply[1]; }
             if (p.cost) p.cost[inst] = J;
             if (p.iters_acc) p.iters_acc[inst] = acc_it + it_done;
-            if (p.status_acc) p.status_acc[inst] = acc_st + (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
+            if (p.status_acc) p.status_acc[inst] = acc_st + (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);      // (not tail_status_acc_word: added to acc_st in another order, every
+                                                                                                                   // instantiation of this branch selects the word differently, e.g. <3, 3, false> line 6549)
             if (p.status) p.status[inst] = status;
             if (p.iters) p.iters[inst] = it_done;
         }
@@ -1283,39 +1258,13 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             if ((p.fused & kFuseAdvanceRef) && lane0s && p.ref_off) p.ref_off[inst] += 1;
         }
     } else {        // (the order these instantiations had; not indented)
-    // ---- full step on the iterate; status 4 leaves it unchanged ----
+    // ---- full step on the iterate; status 4 leaves it unchanged: the solve tail, shared pieces tail_* (rti_kernel.hpp) ----
     const bool store = !ep_done;
     status = ipm_finite_step<64>(status, z, lane);
-    if (status != 4) {
-#pragma unroll
-        for (int c = 0; c < 5; c++) xi[c] += z[2 + c];
-        ui[0] += z[0]; ui[1] += z[1];
-    }
+    tail_full_step(status, z, xi, ui);
     const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0]
-    if ((p.fused & kFuseResetOnFail) && status == 4) {      // set_initial_guess(), robot_ocp_problem.py:203-205,286-306
-        xi[0] = x0v[0]; xi[1] = x0v[1]; xi[2] = x0v[2]; xi[3] = 0.0; xi[4] = 0.0; ui[0] = ui[1] = 0.0;
-        if (p.fused & kFuseInterpGuess) interp_guess(x0v, gl[1], i <= N ? i : N, N, xi);
-    }
-    if (store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) {
-        if (p.fused & kFuseShift) {                          // X[j] <- X[j+1], U[j] <- U[j+1], U[N-1] <- 0, X[N] kept (:253-258)
-            if (act && i >= 1) {
-#pragma unroll
-                for (int c = 0; c < 5; c++) Xg[(i - 1) * 5 + c] = xi[c];
-            }
-            if (i == N) {
-#pragma unroll
-                for (int c = 0; c < 5; c++) Xg[N * 5 + c] = xi[c];
-            }
-            if (has_u && i >= 1) { Ug[(i - 1) * 2] = ui[0]; Ug[(i - 1) * 2 + 1] = ui[1]; }
-            if (i == 0) { Ug[(N - 1) * 2] = 0.0; Ug[(N - 1) * 2 + 1] = 0.0; }
-        } else {
-            if (act) {
-#pragma unroll
-                for (int c = 0; c < 5; c++) Xg[i * 5 + c] = xi[c];
-            }
-            if (has_u) { Ug[i * 2] = ui[0]; Ug[i * 2 + 1] = ui[1]; }
-        }
-    }
+    tail_reset_on_fail(p.fused, status, x0v, gl[1], i, N, xi, ui);
+    if (store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) tail_store_iterate(p.fused, i, N, act, has_u, xi, ui, Xg, Ug);
     // ---- plant, obstacles, episode bookkeeping (fused closed-loop step) ----
     if (p.fused & (kFusePlant | kFuseObstacles | kFuseMetrics)) {
         double xp[5] = {x0v[0], x0v[1], x0v[2], x0v[3], x0v[4]};
@@ -1390,7 +1339,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     }
     if (lane == 0 && store) {
         if (p.iters_acc) p.iters_acc[inst] += it_done;
-        if (p.status_acc) p.status_acc[inst] += (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
+        if (p.status_acc) p.status_acc[inst] += tail_status_acc_word(status);
         if (p.status) p.status[inst] = status;
         if (p.iters) p.iters[inst] = it_done;
     }

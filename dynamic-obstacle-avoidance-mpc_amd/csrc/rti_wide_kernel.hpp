@@ -790,43 +790,18 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
         for (int c = 0; c < 5; c++) x0v[c] = xg[c];
         gl[0] = gg[0]; gl[1] = gg[1];
     }
-    // ---- full step on the iterate; status 4 leaves it unchanged.  Wavefront 0 holds every stage's whole step, the others the (x, y) part ----
+    // ---- full step on the iterate; status 4 leaves it unchanged.  Wavefront 0 holds every stage's whole step, the others the (x, y) part.  The solve tail,
+    //      shared pieces tail_* (rti_kernel.hpp) ----
     const bool store = !ep_done;
     {
         double s4 = ipm_finite_step<64>(status, z, lane) == 4 ? 1.0 : 0.0, unused = 0.0;
         group_reduce2(kSiteFin, false, s4, unused);
         if (s4 != 0.0) status = 4;
     }
-    if (status != 4) {
-#pragma unroll
-        for (int c = 0; c < 5; c++) xi[c] += z[2 + c];
-        ui[0] += z[0]; ui[1] += z[1];
-    }
+    tail_full_step(status, z, xi, ui);
     const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0] (wavefront 0)
-    if ((p.fused & kFuseResetOnFail) && status == 4) {
-        xi[0] = x0v[0]; xi[1] = x0v[1]; xi[2] = x0v[2]; xi[3] = 0.0; xi[4] = 0.0; ui[0] = ui[1] = 0.0;
-        if (p.fused & kFuseInterpGuess) interp_guess(x0v, gl[1], i <= N ? i : N, N, xi);
-    }
-    if (w0 && store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) {
-        if (p.fused & kFuseShift) {
-            if (act && i >= 1) {
-#pragma unroll
-                for (int c = 0; c < 5; c++) Xg[(i - 1) * 5 + c] = xi[c];
-            }
-            if (i == N) {
-#pragma unroll
-                for (int c = 0; c < 5; c++) Xg[N * 5 + c] = xi[c];
-            }
-            if (has_u && i >= 1) { Ug[(i - 1) * 2] = ui[0]; Ug[(i - 1) * 2 + 1] = ui[1]; }
-            if (i == 0) { Ug[(N - 1) * 2] = 0.0; Ug[(N - 1) * 2 + 1] = 0.0; }
-        } else {
-            if (act) {
-#pragma unroll
-                for (int c = 0; c < 5; c++) Xg[i * 5 + c] = xi[c];
-            }
-            if (has_u) { Ug[i * 2] = ui[0]; Ug[i * 2 + 1] = ui[1]; }
-        }
-    }
+    tail_reset_on_fail(p.fused, status, x0v, gl[1], i, N, xi, ui);
+    if (w0 && store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) tail_store_iterate(p.fused, i, N, act, has_u, xi, ui, Xg, Ug);
     // NLP objective at the returned iterate: LS cost (wavefront 0's stage owners) + exact penalty of every wavefront's obstacle rows, in wave order
     if (p.cost) {
         double J = 0.0;
@@ -904,7 +879,7 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     if (lane == 0 && p.u0 && store) { p.u0[(size_t)inst * 2] = u_apply[0]; p.u0[(size_t)inst * 2 + 1] = u_apply[1]; }
     if (lane == 0 && store) {
         if (p.iters_acc) p.iters_acc[inst] += it_done;
-        if (p.status_acc) p.status_acc[inst] += (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0);
+        if (p.status_acc) p.status_acc[inst] += tail_status_acc_word(status);
         if (p.status) p.status[inst] = status;
         if (p.iters) p.iters[inst] = it_done;
     }

@@ -15,6 +15,88 @@ def random_batch(B, n_obst, seed=1234, moving=True):
     return x0, goal, obst
 
 
+ARENA = 8.0     # mpc_default_config: the arena is [-8, 8] x [-8, 8]
+
+
+def wall_batch(B, no, seed):
+    """random_batch with obstacles placed so that, at dt = 0.1, coordinates reflect off an arena wall inside a horizon of five stages.  The predictor moves x
+    with vy (defect D1, bug_compat_predict), the ground-truth step moves it with vx: both velocities point at the wall.
+      instance 0, obstacle 0: 0.3 from ymin, moving down at 1.9 -- reflects in the second stage, inside the first block of four;
+      instance 1, obstacle 0: exactly on xmax, moving outwards -- the distance to the wall is zero in the first stage;
+      instance 2, last obstacle: 0.05 from xmin and 0.3 from ymin -- both coordinates reflect, in different stages;
+      instance 0, last obstacle (two or more obstacles): 1.0 from ymax at 1.5 -- reflects in the seventh stage, a later block (horizons of 20 and more)."""
+    x0, goal, obst = random_batch(B, no, seed=seed)
+    obst[0, 0] = [1.0, -ARENA + 0.3, 0.5, -1.9]
+    obst[1, 0] = [ARENA, 2.0, 1.0, 1.0]
+    obst[2, no - 1] = [-ARENA + 0.05, -ARENA + 0.3, -1.5, -1.5]
+    if no >= 2:
+        obst[0, no - 1] = [0.0, ARENA - 1.0, 0.3, 1.5]
+    return x0, goal, obst
+
+
+def fused_step_is_the_separate_calls(mpc_gpu, N, no, x0, goal, obst, noise, configure, flags, steps=3):
+    """`steps` fused control steps (closed_loop_step_dev with `flags`) against solve, plant step, obstacle step and shift through their own entry points, bit
+    for bit.  configure(s) sets the lane mapping of a fresh handle and asserts that it took; noise: [steps][B][no][2] standard normals or None.
+    With STEP_RESET_ON_FAIL in the flags the separate side resets the iterate of an instance whose solve failed (status 4) with reset_guess at the state the
+    solve started from, before the shift; NaN obstacle states compare equal, and the cost of a failed instance is not compared.
+    Returns the per-step records of the fused side."""
+    import torch
+    from mpc_gpu import _lib
+    B = len(x0)
+    reset = bool(flags & _lib.STEP_RESET_ON_FAIL)
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    c = lambda a: a.cpu().numpy()
+
+    def handle():
+        s = mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B)
+        configure(s)
+        s.reset_guess(x0)
+        return s
+
+    fused, apart = [], []
+    with handle() as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        st = torch.cuda.current_stream().cuda_stream
+        dx, dobst, dgoal = t(x0), t(obst), t(goal)
+        u0 = torch.zeros(B, 2, dtype=torch.float64, device=dev); cost = torch.zeros(B, dtype=torch.float64, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev); iters = torch.zeros(B, dtype=torch.int32, device=dev)
+        dX, dU, _ = s.iterate_ptrs()
+        for k in range(steps):
+            s.closed_loop_step_dev(B, dx, dobst, dgoal, dX, dU, u0, cost, status, iters, None if noise is None else t(noise[k]), flags=flags, stream=st)
+            torch.cuda.current_stream().synchronize()
+            X, U = s.get_traj(B)
+            fused.append(dict(X=X, U=U, x=c(dx), obst=c(dobst), u0=c(u0), cost=c(cost), status=c(status), iters=c(iters)))
+    with handle() as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        st = torch.cuda.current_stream().cuda_stream
+        x, ob = x0.copy(), obst.copy()
+        for k in range(steps):
+            g = s.solve(x, ob, goal)
+            failed = g["status"] == 4
+            if reset and failed.any():      # set_initial_guess() of the failed instances alone, at the state their solve started from
+                X, U = s.get_traj(B)
+                s.reset_guess(x)
+                Xr, Ur = s.get_traj(B)
+                X[failed], U[failed] = Xr[failed], Ur[failed]
+                s.set_warmstart(X, U)
+            x = s.plant_step(x, g["u0"])
+            dob = t(ob)
+            s.obstacle_step_dev(B * no, dob, None if noise is None else t(noise[k]), stream=st)
+            torch.cuda.current_stream().synchronize()
+            ob = c(dob)
+            s.shift(B)
+            X, U = s.get_traj(B)
+            apart.append(dict(X=X, U=U, x=x, obst=ob, u0=g["u0"], cost=g["cost"], status=g["status"], iters=g["iters"]))
+    for k, (a, b) in enumerate(zip(fused, apart)):
+        for key in ("X", "U", "x", "obst", "u0", "cost", "status", "iters"):
+            if reset and key == "cost":     # (of a failed instance the fused step reports the cost of the reset iterate, the solve that of the iterate it left)
+                ok = a["status"] != 4
+                assert np.array_equal(a[key][ok], b[key][ok]), (k, key)
+            else:
+                assert np.array_equal(a[key], b[key], equal_nan=reset and key == "obst"), (k, key)
+    assert not np.array_equal(fused[0]["obst"], obst)
+    return fused
+
+
 def oracle_reference(orc, cfg, x0, P, goal, X, U):
     """Run the oracle on a batch (OpenMP) and return its outputs."""
     return orc.rti_solve_batch(cfg, x0, P, goal, X, U, nthreads=0)

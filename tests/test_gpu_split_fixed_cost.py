@@ -9,33 +9,15 @@ Every comparison is bit for bit (array_equal): nothing here changes arithmetic, 
 import numpy as np
 import pytest
 
-from helpers import random_batch
+from helpers import ARENA, fused_step_is_the_separate_calls, wall_batch
 
 pytestmark = pytest.mark.gpu
-
-ARENA = 8.0     # mpc_default_config: the arena is [-8, 8] x [-8, 8]
 
 
 @pytest.fixture
 def env(built):
     import mpc_gpu
     return mpc_gpu
-
-
-def wall_batch(B, no, seed):
-    """random_batch with obstacles placed so that, at dt = 0.1, coordinates reflect off an arena wall inside a horizon of five stages.  The predictor moves x
-    with vy (defect D1, bug_compat_predict), the ground-truth step moves it with vx: both velocities point at the wall.
-      instance 0, obstacle 0: 0.3 from ymin, moving down at 1.9 -- reflects in the second stage, inside the first block of four;
-      instance 1, obstacle 0: exactly on xmax, moving outwards -- the distance to the wall is zero in the first stage;
-      instance 2, last obstacle: 0.05 from xmin and 0.3 from ymin -- both coordinates reflect, in different stages;
-      instance 0, last obstacle (two or more obstacles): 1.0 from ymax at 1.5 -- reflects in the seventh stage, a later block (horizons of 20 and more)."""
-    x0, goal, obst = random_batch(B, no, seed=seed)
-    obst[0, 0] = [1.0, -ARENA + 0.3, 0.5, -1.9]
-    obst[1, 0] = [ARENA, 2.0, 1.0, 1.0]
-    obst[2, no - 1] = [-ARENA + 0.05, -ARENA + 0.3, -1.5, -1.5]
-    if no >= 2:
-        obst[0, no - 1] = [0.0, ARENA - 1.0, 0.3, 1.5]
-    return x0, goal, obst
 
 
 def lanes_for(N):
@@ -73,7 +55,6 @@ def test_lookahead_in_the_kernel_is_the_lookahead_given(env, N, no):
 @pytest.mark.parametrize("noisy", [False, True], ids=["no-noise", "noise"])
 @pytest.mark.parametrize("N,no", [(5, 3), (20, 3)])
 def test_fused_step_is_the_separate_calls(env, N, no, noisy, waves):
-    import torch
     from mpc_gpu import _lib
     mpc_gpu = env
     B, steps = 5, 3
@@ -81,47 +62,12 @@ def test_fused_step_is_the_separate_calls(env, N, no, noisy, waves):
     # ground-truth reflections as well: the step moves x with vx
     obst[3, 0] = [ARENA - 0.1, -ARENA + 0.1, 1.8, -1.8]
     noise = np.random.default_rng(77).standard_normal((steps, B, no, 2)) if noisy else None
-    dev = torch.device("cuda:0")
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    c = lambda a: a.cpu().numpy()
 
-    def handle():
-        s = mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B)
+    def configure(s):
         s.set_lanes_per_stage(3); s.set_waves_per_simd(waves)
         assert s.lanes_per_stage(B) == 3 and s.waves_per_simd(B) == waves
-        s.reset_guess(x0)
-        return s
 
-    fused, apart = [], []
-    with handle() as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-        st = torch.cuda.current_stream().cuda_stream
-        dx, dobst, dgoal = t(x0), t(obst), t(goal)
-        u0 = torch.zeros(B, 2, dtype=torch.float64, device=dev); cost = torch.zeros(B, dtype=torch.float64, device=dev)
-        status = torch.zeros(B, dtype=torch.int32, device=dev); iters = torch.zeros(B, dtype=torch.int32, device=dev)
-        dX, dU, _ = s.iterate_ptrs()
-        for k in range(steps):
-            s.closed_loop_step_dev(B, dx, dobst, dgoal, dX, dU, u0, cost, status, iters, None if noise is None else t(noise[k]),
-                                   flags=_lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES, stream=st)
-            torch.cuda.current_stream().synchronize()
-            X, U = s.get_traj(B)
-            fused.append(dict(X=X, U=U, x=c(dx), obst=c(dobst), u0=c(u0), cost=c(cost), status=c(status), iters=c(iters)))
-    with handle() as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-        st = torch.cuda.current_stream().cuda_stream
-        x, ob = x0.copy(), obst.copy()
-        for k in range(steps):
-            g = s.solve(x, ob, goal)
-            x = s.plant_step(x, g["u0"])
-            dob = t(ob)
-            s.obstacle_step_dev(B * no, dob, None if noise is None else t(noise[k]), stream=st)
-            torch.cuda.current_stream().synchronize()
-            ob = c(dob)
-            s.shift(B)
-            X, U = s.get_traj(B)
-            apart.append(dict(X=X, U=U, x=x, obst=ob, u0=g["u0"], cost=g["cost"], status=g["status"], iters=g["iters"]))
-    for k, (a, b) in enumerate(zip(fused, apart)):
-        for key in ("X", "U", "x", "obst", "u0", "cost", "status", "iters"):
-            assert np.array_equal(a[key], b[key]), (k, key)
-    assert not np.array_equal(fused[0]["obst"], obst)
+    fused_step_is_the_separate_calls(mpc_gpu, N, no, x0, goal, obst, noise, configure, _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES, steps=steps)
 
 
 def test_a_nan_obstacle_fails_its_instance_alone(env):
