@@ -13,7 +13,7 @@ import mpc_gpu
 from mpc_gpu import _lib
 from oracle import oracle as orc
 from helpers import OracleLoop, adjudicate, random_batch
-from test_gpu_closed_loop import GpuLoop
+from feature_loop import GpuLoop
 
 replay = None
 if len(sys.argv) > 1 and sys.argv[1] == "replay":

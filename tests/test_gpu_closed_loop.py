@@ -4,6 +4,7 @@ sub-goal hook (set_subgoal, :279-284; x_N read-back, :232) and the explicit slac
 import numpy as np
 import pytest
 
+from feature_loop import GpuLoop
 from helpers import OracleLoop, adjudicate, allowed_adjudications, oracle_P, oracle_guess, random_batch
 
 pytestmark = pytest.mark.gpu
@@ -16,55 +17,6 @@ def env(built, request):
     mpc_gpu.BatchedMpc.default_lanes_per_stage = 0 if request.param == "stage-split" else 1
     yield mpc_gpu, orc
     mpc_gpu.BatchedMpc.default_lanes_per_stage = 0
-
-
-class GpuLoop:
-    """device-resident closed loop on the handle-owned iterate, one launch per control step"""
-
-    def __init__(self, mpc_gpu, N, no, Tf, x0, goal, obst, alias=True, **cfg):
-        import torch
-        from mpc_gpu import _lib
-        self.torch, self.B = torch, x0.shape[0]
-        self.m = mpc_gpu.BatchedMpc(N, no, Tf, max_batch=self.B, **cfg)
-        dev = torch.device("cuda:0")
-        self.stream = torch.cuda.Stream(device=dev)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        z = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device=dev)
-        with torch.cuda.stream(self.stream):
-            self.x0, self.goal, self.obst = t(x0), t(goal), t(obst)
-            if alias:
-                self.x0[:, 3:] = 0.0
-            self.u0, self.cost = z(self.B, 2), z(self.B)
-            self.status, self.iters = z(self.B, dt=torch.int32), z(self.B, dt=torch.int32)
-            self.margin = torch.full((self.B,), float("inf"), dtype=torch.float64, device=dev)
-            self.flags, self.steps = z(self.B, dt=torch.int32), z(self.B, dt=torch.int32)
-        self.stream.synchronize()
-        self.dX, self.dU, _ = self.m.iterate_ptrs()              # the handle-owned iterate: terminal_state() / get_traj() see it
-        self.m.reset_guess_dev(self.B, self.x0, self.dX, self.dU, stream=self.stream.cuda_stream)
-        self.fl = (_lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS | _lib.STEP_RESET_ON_FAIL
-                   | (_lib.STEP_ALIAS_BUG if alias else 0))
-        self.dev = dev
-
-    def step(self, noise=None):
-        nz = None if noise is None else self.torch.from_numpy(np.ascontiguousarray(noise)).to(self.dev)
-        self.m.closed_loop_step_dev(self.B, self.x0, self.obst, self.goal, self.dX, self.dU, self.u0, self.cost, self.status, self.iters,
-                                    nz, flags=self.fl, min_margin=self.margin, ep_flags=self.flags, ep_steps=self.steps,
-                                    stream=self.stream.cuda_stream)
-        self.stream.synchronize()
-
-    def host(self):
-        c = lambda a: a.cpu().numpy()
-        X, U = self.m.get_traj(self.B)
-        return dict(x0=c(self.x0), obst=c(self.obst), X=X, U=U, u0=c(self.u0), status=c(self.status), iters=c(self.iters),
-                    margin=c(self.margin), flags=c(self.flags), steps=c(self.steps))
-
-    def set_goal(self, goal):
-        with self.torch.cuda.stream(self.stream):
-            self.goal.copy_(self.torch.from_numpy(np.ascontiguousarray(goal)).to(self.dev))
-        self.stream.synchronize()
-
-    def close(self):
-        self.m.close()
 
 
 def test_fused_step_against_the_oracle_loop_with_resync(env):

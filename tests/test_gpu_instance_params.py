@@ -5,6 +5,8 @@ episode metrics, the fused loop equals host-driven steps, and the refusals."""
 import numpy as np
 import pytest
 
+from feature_loop import (FeatureStack, assert_fused_equals_host, assert_same, cfg_values, fused_loop, host_driven_loop, make, mg, on_own_stream, run,
+                          smooth_path)
 from helpers import allowed_adjudications, exact_qp, judge_against_oracle, oracle_P, oracle_reference, random_batch, step_vector
 from instance_params_qp import cost as np_cost
 from instance_params_qp import draw_sets, hval, retarget_qp, stage_gradient
@@ -12,58 +14,6 @@ from instance_params_qp import draw_sets, hval, retarget_qp, stage_gradient
 pytestmark = pytest.mark.gpu
 
 SIZES = [(20, 3), (30, 10), (20, 15), (50, 10)]      # split x3, split x2 with ten rows, the multi-wavefront kernel (masked), one instance per wavefront
-
-
-@pytest.fixture
-def mg(built):
-    import mpc_gpu
-    from oracle import oracle as orc
-    mpc_gpu.BatchedMpc.default_lanes_per_stage = 0
-    mpc_gpu.BatchedMpc.default_waves_per_simd = 0
-    mpc_gpu.BatchedMpc.default_lanes_per_instance = 0
-    return mpc_gpu, orc
-
-
-def _on_own_stream(fn, *args):
-    """device-API calls on a torch stream of their own: the legacy default stream's handle is 0, which the library reads as the handle's
-    own (non-blocking) stream, unordered with torch's copies"""
-    import torch
-    with torch.cuda.stream(torch.cuda.Stream()):
-        fn(*args)
-        torch.cuda.synchronize()
-
-
-def make(mpc_gpu, N, no, B, **cfg):
-    s = mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B, **cfg)
-    s.set_instance_scheduling(False)      # (the launch order then depends on nothing but the batch)
-    return s
-
-
-def run(s, x0, obst, goal, steps=3):
-    """first solve and warm-started ones; everything a caller sees"""
-    B = x0.shape[0]
-    s.reset_guess(x0)
-    outs = []
-    for _ in range(steps):
-        o = s.solve(x0, obst, goal)
-        X, U = s.get_traj(B)
-        outs.append((X, U, o["u0"], o["cost"], o["status"], o["iters"]))
-    return outs
-
-
-def assert_same(a, b, idx=None, cost_rtol=1e-13):
-    """X, U, u0, status, iterations bit for bit; the reported cost to cost_rtol (None: bit for bit too).  idx: the instances of `a` that `b` holds"""
-    for ra, rb in zip(a, b):
-        for k, (x, y) in enumerate(zip(ra, rb)):
-            x = x if idx is None else x[idx]
-            if k == 3 and cost_rtol is not None:
-                assert np.allclose(x, y, rtol=cost_rtol, atol=0.0)
-            else:
-                assert np.array_equal(x, y), k
-
-
-def cfg_values(s):
-    return np.array([s.cfg.W[k] for k in range(6)]), np.array([s.cfg.We[k] for k in range(4)]), float(s.cfg.r_safe)
 
 
 def ip_name(plain):
@@ -83,18 +33,18 @@ def _body_identity(mg, N, no):
         plain, name = a.kernel_name(B), r.kernel_name(B)
         assert name.endswith(", true, true>"), name
         assert ip_name(plain) == name, (plain, name)      # these four sizes keep their mapping at this batch size: bit for bit
-        assert_same(run(a, x0, obst, goal), run(r, x0, obst, goal))                      # look-ahead in the kernel
+        assert_same(run(a, x0, obst, goal), run(r, x0, obst, goal), cost_rtol=1e-13)                      # look-ahead in the kernel
         P = oracle_P(orc, cfg, obst)
-        assert_same(run(a, x0, P, goal, 2), run(r, x0, P, goal, 2))                      # explicit P
+        assert_same(run(a, x0, P, goal, 2), run(r, x0, P, goal, 2), cost_rtol=1e-13)                      # explicit P
         r.set_instance_params(r_safe=np.full(B, rs))                                     # one group only, (B,) radii: the others keep the handle's values
-        assert_same(run(a, x0, obst, goal, 2), run(r, x0, obst, goal, 2))
+        assert_same(run(a, x0, obst, goal, 2), run(r, x0, obst, goal, 2), cost_rtol=1e-13)
         r.set_instance_params(W=np.tile(W, (B, 1)))
-        assert_same(run(a, x0, obst, goal, 2), run(r, x0, obst, goal, 2))
+        assert_same(run(a, x0, obst, goal, 2), run(r, x0, obst, goal, 2), cost_rtol=1e-13)
 
 
 @pytest.mark.parametrize("N,no", SIZES)
 def test_repeating_the_handle_values_is_bit_identical(mg, N, no):
-    _on_own_stream(_body_identity, mg, N, no)
+    on_own_stream(_body_identity, mg, N, no)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. heterogeneous = homogeneous
@@ -120,13 +70,13 @@ def _body_heterogeneous(mg, N, no):
             assert np.array_equal(Wk, W[k]) and np.array_equal(Wek, We[k]) and rk == r[k]
             h.set_instance_params(W=np.tile(Wk, (n, 1)), We=np.tile(Wek, (n, 1)), r_safe=np.full(n, rk))      # feature on: the same instantiation
             assert h.kernel_name(n) == name
-            assert_same(het, run(h, x0[idx], obst[idx], goal[idx]), idx, cost_rtol=None)
-            assert_same(het_P, run(h, x0[idx], P[idx], goal[idx], 2), idx, cost_rtol=None)
+            assert_same(het, run(h, x0[idx], obst[idx], goal[idx]), rows_a=idx)
+            assert_same(het_P, run(h, x0[idx], P[idx], goal[idx], 2), rows_a=idx)
 
 
 @pytest.mark.parametrize("N,no", SIZES)
 def test_heterogeneous_batch_equals_homogeneous_handles(mg, N, no):
-    _on_own_stream(_body_heterogeneous, mg, N, no)
+    on_own_stream(_body_heterogeneous, mg, N, no)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. against the oracle
@@ -160,7 +110,7 @@ def _body_oracle(mg, N, no):
 
 @pytest.mark.parametrize("N,no", SIZES)
 def test_expressible_sets_against_the_oracle(mg, N, no):
-    _on_own_stream(_body_oracle, mg, N, no)
+    on_own_stream(_body_oracle, mg, N, no)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. per-obstacle radii, exact QP
@@ -222,7 +172,7 @@ def _body_radii(mg, N, no, B, seed, lo, hi):
 
 @pytest.mark.parametrize("N,no,B,seed,lo,hi", RADII_CASES)
 def test_per_obstacle_radii_against_exact_qp(mg, N, no, B, seed, lo, hi):
-    _on_own_stream(_body_radii, mg, N, no, B, seed, lo, hi)
+    on_own_stream(_body_radii, mg, N, no, B, seed, lo, hi)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. a radius matters
@@ -261,150 +211,46 @@ def _body_radius_matters(mg):
 
 
 def test_a_radius_reaches_constraint_and_metrics(mg):
-    _on_own_stream(_body_radius_matters, mg)
+    on_own_stream(_body_radius_matters, mg)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. fused loop and combinations
-def smooth_path(rng, B, T):
-    t = np.linspace(0.0, 1.0, T)
-    R = np.zeros((B, T, 6))
-    for b in range(B):
-        a = rng.uniform(-4, 4, 2); c = rng.uniform(-3, 3, 2); w = rng.uniform(0.5, 2.0)
-        R[b, :, 0] = a[0] + c[0] * np.sin(w * t); R[b, :, 1] = a[1] + c[1] * np.cos(w * t)
-        R[b, :, 2] = rng.uniform(-1, 1) + 0.3 * t; R[b, :, 3] = rng.uniform(-0.5, 0.5) * np.cos(t)
-        R[b, :, 4] = rng.uniform(-0.5, 0.5); R[b, :, 5] = rng.uniform(-0.3, 0.3)
-    return R
-
-
-def loop_inputs(N, no, B, seed):
+def loop_inputs(N, no, B, seed, steps, with_ref):
     rng = np.random.default_rng(seed)
     x0, goal, obst = random_batch(B, no, seed=seed)
     x0[:, 3:] = 0.0
     W = 2.0 * np.exp(rng.uniform(np.log(0.25), np.log(4.0), (B, 6))); W[:, 4:] *= 0.075
     We = 5.0 * np.exp(rng.uniform(np.log(0.25), np.log(4.0), (B, 4)))
-    return x0, goal, obst, W, We, rng.uniform(1.6, 3.0, (B, no)), rng
-
-
-def _fused(mpc_gpu, N, no, B, steps, x0, goal, obst, W, We, R, path, solver=None):
-    """`steps` fused steps, everything resident; per-instance parameters as device tensors when `solver` is a PipelinedMpc"""
-    import torch
-    L = mpc_gpu._lib
-    dev = torch.device("cuda", 0)
-    tt = lambda a: torch.tensor(np.ascontiguousarray(a), device=dev)
-    s = solver or make(mpc_gpu, N, no, B)
-    piped = solver is not None
-    tx, to, tg = tt(x0), tt(obst), tt(goal)
-    X = torch.zeros((B, N + 1, 5), dtype=torch.float64, device=dev); U = torch.zeros((B, N, 2), dtype=torch.float64, device=dev)
-    u0 = torch.zeros((B, 2), dtype=torch.float64, device=dev)
-    mm = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
-    fl = torch.zeros(B, dtype=torch.int32, device=dev); ns = torch.zeros(B, dtype=torch.int32, device=dev)
-    flags = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES | L.STEP_METRICS
-    dW, dWe, dR = tt(W), tt(We), tt(R)
-    if piped:
-        s.set_instance_params_dev(W=dW, We=dWe, r_safe=dR)
-    else:
-        s.set_instance_params(W=W, We=We, r_safe=R)
-    if path is not None:
-        ty, toff = tt(path), torch.zeros(B, dtype=torch.int32, device=dev)
-        if piped:
-            s.set_reference_dev(ty, toff)
-        else:
-            s.set_reference(ty, toff)
-        flags |= L.STEP_ADVANCE_REF
-    us = []
-    if piped:
-        torch.cuda.synchronize()
-        s.reset_guess_dev(B, tx, X, U)
-        for _ in range(steps):
-            s.closed_loop_step_dev(B, tx, to, tg, X, U, u0, flags=flags, min_margin=mm, ep_flags=fl, ep_steps=ns)
-            for _, _, _, st in s.parts:
-                st.synchronize()
-            us.append(u0.cpu().numpy().copy())
-    else:
-        st = torch.cuda.current_stream().cuda_stream
-        s.reset_guess_dev(B, tx, X, U, stream=st)
-        for _ in range(steps):
-            s.closed_loop_step_dev(B, tx, to, tg, X, U, u0, flags=flags, min_margin=mm, ep_flags=fl, ep_steps=ns, stream=st)
-            torch.cuda.synchronize()
-            us.append(u0.cpu().numpy().copy())
-    torch.cuda.synchronize()
-    res = dict(x=tx.cpu().numpy(), obst=to.cpu().numpy(), X=X.cpu().numpy(), U=U.cpu().numpy(), u0=np.array(us), mm=mm.cpu().numpy(),
-               fl=fl.cpu().numpy(), ns=ns.cpu().numpy())
-    if solver is None:
-        s.close()
-    return res
-
-
-def _host_driven(mpc_gpu, N, no, B, steps, x0, goal, obst, W, We, R, path, r_hit):
-    """the same steps through mpc_solve_obst + mpc_plant_step + mpc_shift (and the obstacle motion kernel), the bookkeeping in numpy: an instance that
-    has reached its goal idles, nothing of it is touched"""
-    import torch
-    dev = torch.device("cuda", 0)
-    x, ob = x0.copy(), obst.copy()
-    alive = np.ones(B, bool)
-    mm = np.full(B, np.inf); ns = np.zeros(B, np.int32)
-    us = []
-    u_last = np.zeros((B, 2))
-    off = np.zeros(B, np.int32)
-    with make(mpc_gpu, N, no, B) as s:
-        s.set_instance_params(W=W, We=We, r_safe=R)
-        s.reset_guess(x)
-        for _ in range(steps):
-            Xk, Uk = s.get_traj(B)
-            if path is not None:
-                s.set_reference(path, offset=off)
-            o = s.solve(x, ob, goal)
-            xn = s.plant_step(x, o["u0"])
-            s.shift(B)
-            Xn, Un = s.get_traj(B)
-            to = torch.tensor(ob, device=dev)
-            s.obstacle_step_dev(B * no, to, None, stream=torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            obn = to.cpu().numpy()
-            Xn[~alive] = Xk[~alive]; Un[~alive] = Uk[~alive]
-            s.set_warmstart(Xn, Un)
-            x[alive] = xn[alive]; ob[alive] = obn[alive]; u_last[alive] = o["u0"][alive]
-            off[alive] += 1
-            margin = (np.linalg.norm(x[:, None, :2] - ob[:, :, :2], axis=2) - r_hit).min(axis=1)
-            mm[alive] = np.minimum(mm, margin)[alive]
-            reached = np.linalg.norm(x[:, :2] - goal, axis=1) <= 0.15
-            ns[alive & ~reached] += 1
-            alive &= ~reached
-            us.append(u_last.copy())
-        X, U = s.get_traj(B)
-    return dict(x=x, obst=ob, X=X, U=U, u0=np.array(us), mm=mm, ns=ns)
+    R = rng.uniform(1.6, 3.0, (B, no))
+    path = smooth_path(rng, B, steps + N + 1) if with_ref else None
+    return FeatureStack(W=W, We=We, r_safe=R, path=path), x0, goal, obst
 
 
 def _body_fused_equals_host(mg, N, no, with_ref):
     mpc_gpu, _ = mg
     B, steps = 8, 20
-    x0, goal, obst, W, We, R, rng = loop_inputs(N, no, B, 600 + N + no)
-    path = smooth_path(rng, B, steps + N + 1) if with_ref else None
-    f = _fused(mpc_gpu, N, no, B, steps, x0, goal, obst, W, We, R, path)
-    r_hit = R - (2.4 - 1.2)
-    h = _host_driven(mpc_gpu, N, no, B, steps, x0, goal, obst, W, We, R, path, r_hit)
-    for k in ("x", "obst", "X", "U", "u0", "ns"):
-        assert np.array_equal(f[k], h[k]), k
-    assert np.abs(f["mm"] - h["mm"]).max() <= 1e-12      # (numpy's norm against the kernel's sqrt of a contracted sum)
+    stack, x0, goal, obst = loop_inputs(N, no, B, 600 + N + no, steps, with_ref)
+    f = fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack)
+    h = host_driven_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack)
+    assert_fused_equals_host(f, h)
 
 
 @pytest.mark.parametrize("N,no,with_ref", [(20, 3, False), (20, 3, True), (30, 10, False), (20, 15, True), (50, 10, False)])
 def test_fused_loop_equals_host_driven_steps(mg, N, no, with_ref):
-    _on_own_stream(_body_fused_equals_host, mg, N, no, with_ref)
+    on_own_stream(_body_fused_equals_host, mg, N, no, with_ref)
 
 
 def _body_pipelined(mg, with_ref):
     mpc_gpu, _ = mg
     N, no, B, steps = 20, 3, 10, 12
-    x0, goal, obst, W, We, R, rng = loop_inputs(N, no, B, 911)
-    path = smooth_path(rng, B, steps + N + 1) if with_ref else None
-    one = _fused(mpc_gpu, N, no, B, steps, x0, goal, obst, W, We, R, path)
+    stack, x0, goal, obst = loop_inputs(N, no, B, 911, steps, with_ref)
+    one = fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack)
     from mpc_gpu.pipeline import PipelinedMpc
     with PipelinedMpc(N, no, 0.1 * N, max_batch=B, streams=2) as p:
         for _, _, m, _ in p.parts:
             m.set_instance_scheduling(False)
         assert p.kernel_name().endswith(", true, true>") is False      # (nothing set yet)
-        two = _fused(mpc_gpu, N, no, B, steps, x0, goal, obst, W, We, R, path, solver=p)
+        two = fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack, solver=p)
         assert p.kernel_name().endswith(", true, true>")
     for k in one:
         assert np.array_equal(one[k], two[k]), k      # device arrays through the preparation kernel against host arrays: the same rounding
@@ -412,7 +258,7 @@ def _body_pipelined(mg, with_ref):
 
 @pytest.mark.parametrize("with_ref", [False, True])
 def test_pipelined_sub_batches_equal_one_handle(mg, with_ref):
-    _on_own_stream(_body_pipelined, mg, with_ref)
+    on_own_stream(_body_pipelined, mg, with_ref)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 7. refusals and switching off
@@ -456,7 +302,7 @@ def test_refusals_and_switching_off(mg):
         s.set_instance_params()
         assert s.kernel_name(B) == fresh.kernel_name(B)
         back, want = run(s, x0, obst, goal, 2), run(fresh, x0, obst, goal, 2)
-        assert_same(back, want, cost_rtol=None)
+        assert_same(back, want)
         assert not np.array_equal(changed[0][0], want[0][0])               # (and the values did reach the solve while they were on)
 
 

@@ -11,31 +11,12 @@ import numpy as np
 import pytest
 
 import off_default_cases as oc
+from feature_loop import GpuLoop, assert_same, mg, on_own_stream
 from helpers import OracleLoop, adjudicate, judge_against_oracle, oracle_P
-from test_gpu_closed_loop import GpuLoop
 
 pytestmark = pytest.mark.gpu
 
 ROW_IDS = [r["id"] for r in oc.ROWS]
-
-
-@pytest.fixture
-def mg(built):
-    import mpc_gpu
-    from oracle import oracle as orc
-    mpc_gpu.BatchedMpc.default_lanes_per_stage = 0
-    mpc_gpu.BatchedMpc.default_waves_per_simd = 0
-    mpc_gpu.BatchedMpc.default_lanes_per_instance = 0
-    return mpc_gpu, orc
-
-
-def _on_own_stream(fn, *args):
-    """device-API calls on a torch stream of their own: the legacy default stream's handle is 0, which the library reads as the handle's
-    own (non-blocking) stream, unordered with torch's copies"""
-    import torch
-    with torch.cuda.stream(torch.cuda.Stream()):
-        fn(*args)
-        torch.cuda.synchronize()
 
 
 def gpu_three_solves(s, ref, x0, obst, P, goal):
@@ -70,17 +51,9 @@ def judge_solves(orc, cfg, ref, outs, x0, P, goal, counts, capped, what):
         assert med < 1e-9, (what, k, med)
 
 
-def assert_same(a, b, cost_rtol=None):
-    """[(g, X, U)] of two runs: X, U, u0, status, iterations bit for bit; the cost bit for bit, or to cost_rtol"""
-    assert len(a) == len(b)
-    for k, ((ga, Xa, Ua), (gb, Xb, Ub)) in enumerate(zip(a, b)):
-        assert np.array_equal(Xa, Xb) and np.array_equal(Ua, Ub), k
-        for key in ("u0", "status", "iters"):
-            assert np.array_equal(ga[key], gb[key]), (k, key)
-        if cost_rtol is None:
-            assert np.array_equal(ga["cost"], gb["cost"]), k
-        else:
-            assert np.allclose(ga["cost"], gb["cost"], rtol=cost_rtol, atol=0.0), k
+def as_runs(outs):
+    """[(g, X, U)] in the record layout of feature_loop.run, for assert_same"""
+    return [(X, U, g["u0"], g["cost"], g["status"], g["iters"]) for g, X, U in outs]
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. linearisation, plant, look-ahead
@@ -118,7 +91,7 @@ def _body_linearize(mg, N, no, dt):
 @pytest.mark.parametrize("dt", [0.05, 0.16])
 @pytest.mark.parametrize("N,no", [(20, 3), (5, 1)])
 def test_linearisation_and_plant_step(mg, N, no, dt):
-    _on_own_stream(_body_linearize, mg, N, no, dt)
+    on_own_stream(_body_linearize, mg, N, no, dt)
 
 
 def _body_lookahead(mg, N, dt):
@@ -162,7 +135,7 @@ def _body_lookahead(mg, N, dt):
 @pytest.mark.parametrize("N", [5, 20, 21, 50])
 def test_lookahead_and_obstacle_motion_are_the_oracles(mg, N, dt):
     """predict (with the defect D1 and without) and obstacle_step_dev (without and with noise) under OFF's arena on the wall cases, bit for bit"""
-    _on_own_stream(_body_lookahead, mg, N, dt)
+    on_own_stream(_body_lookahead, mg, N, dt)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. look-ahead in the solve kernel
@@ -184,7 +157,7 @@ def test_lookahead_in_the_kernel_is_the_lookahead_given(mg, rid):
             g = s.solve(x0, obst if how == "obst" else P, goal)
             X, U = s.get_traj(B)
             res[how] = [(g, X, U)]
-    assert_same(res["obst"], res["P"])
+    assert_same(as_runs(res["obst"]), as_runs(res["P"]))
     assert (res["obst"][0][0]["status"] == 0).any()
 
 
@@ -324,14 +297,14 @@ def _body_features(mg, rid, form):
         s.set_obstacle_mask(np.ones((B, no), bool))
         masked = gpu_three_solves(s, ref, x0, obst, P, goal)
         assert s.kernel_name(B).endswith(", true, true, true>"), s.kernel_name(B)
-        assert_same(base, masked, cost_rtol=1e-13)
+        assert_same(as_runs(base), as_runs(masked), cost_rtol=1e-13)
         # uniform bounds equal to the handle's on top: the contract of test_uniform_bounds_are_the_configured_handle (bit for bit)
         s.set_instance_bounds(bx_lo=list(s.cfg.bx_lo), bx_hi=list(s.cfg.bx_hi), bu_lo=list(s.cfg.bu_lo), bu_hi=list(s.cfg.bu_hi))
         assert s.kernel_name(B).endswith(", true, true, true, true>"), s.kernel_name(B)
-        assert_same(masked, gpu_three_solves(s, ref, x0, obst, P, goal))
+        assert_same(as_runs(masked), as_runs(gpu_three_solves(s, ref, x0, obst, P, goal)))
 
 
 @pytest.mark.parametrize("form", ["host", "dev"])
 @pytest.mark.parametrize("rid", sorted(oc.FEATURE_OK))
 def test_feature_levels(mg, rid, form):
-    _on_own_stream(_body_features, mg, rid, form)
+    on_own_stream(_body_features, mg, rid, form)

@@ -6,20 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from feature_loop import assert_same, mg, on_own_stream, run, smooth_path
 from helpers import exact_qp, oracle_P, random_batch, step_vector
 from reference_qp import goal_rows, ls_cost, shift_gradient, slack_penalty, stage_gradient, stage_rows
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture
-def mg(built):
-    import mpc_gpu
-    from oracle import oracle as orc
-    mpc_gpu.BatchedMpc.default_lanes_per_stage = 0
-    mpc_gpu.BatchedMpc.default_waves_per_simd = 0
-    mpc_gpu.BatchedMpc.default_lanes_per_instance = 0
-    return mpc_gpu, orc
 
 
 def goal_ref(goal, T):
@@ -29,30 +20,6 @@ def goal_ref(goal, T):
     return R
 
 
-def smooth_path(rng, B, T):
-    """random smooth reference paths with non-zero v / omega / input rows"""
-    t = np.linspace(0.0, 1.0, T)
-    R = np.zeros((B, T, 6))
-    for b in range(B):
-        a = rng.uniform(-4, 4, 2); c = rng.uniform(-3, 3, 2); w = rng.uniform(0.5, 2.0)
-        R[b, :, 0] = a[0] + c[0] * np.sin(w * t); R[b, :, 1] = a[1] + c[1] * np.cos(w * t)
-        R[b, :, 2] = rng.uniform(-1, 1) + 0.3 * t; R[b, :, 3] = rng.uniform(-0.5, 0.5) * np.cos(t)
-        R[b, :, 4] = rng.uniform(-0.5, 0.5); R[b, :, 5] = rng.uniform(-0.3, 0.3)
-    return R
-
-
-def run(s, x0, obst, goal, steps=3):
-    """first solve and two warm-started ones; everything a caller sees"""
-    B = x0.shape[0]
-    s.reset_guess(x0)
-    outs = []
-    for _ in range(steps):
-        o = s.solve(x0, obst, goal)
-        X, U = s.get_traj(B)
-        outs.append((X, U, o["u0"], o["cost"], o["status"], o["iters"]))
-    return outs
-
-
 def assert_close(a, b):
     for (Xa, Ua, _, ca, sa, _), (Xb, Ub, _, cb, sb, _) in zip(a, b):
         both = (sa == 0) & (sb == 0)
@@ -60,17 +27,6 @@ def assert_close(a, b):
         dx = np.abs(Xa[both] - Xb[both]).reshape(both.sum(), -1).max(axis=1)
         du = np.abs(Ua[both] - Ub[both]).reshape(both.sum(), -1).max(axis=1)
         assert (dx <= 1e-6).mean() >= 0.99 and (du <= 8e-6).mean() >= 0.99
-
-
-def assert_same(a, b):
-    """X, U, u0, status, iterations bit for bit; the reported cost to the last bits (the REF cost is formed from residuals against row values
-    the compiler cannot see are the goal's, and its contraction into fused multiply-adds may differ from the goal path's)"""
-    for ra, rb in zip(a, b):
-        for k, (x, y) in enumerate(zip(ra, rb)):
-            if k == 3:
-                assert np.allclose(x, y, rtol=1e-13, atol=0.0)
-            else:
-                assert np.array_equal(x, y)
 
 
 # (N, n_obst, B, lanes_per_stage, waves_per_simd, lanes_per_instance, expected kernel name); Bbig: above the split crossover of 1024 SIMDs
@@ -123,7 +79,9 @@ def test_goal_equivalent_reference_is_bit_identical(mg, N, no, B, lps, waves, lp
         # the goal path runs the same instantiation without REF: bit for bit; where the reference path keeps a narrower dispatch (the split mapping
         # beyond the crossover, one instance per wavefront on compact blocks) it is compared with the goal path's own kernel within the parity tolerance
         same = a.kernel_name(B)[:-1] + ", true>" == name
-        check = assert_same if same else assert_close
+        # (the REF cost is formed from residuals against row values the compiler cannot see are the goal's, and its contraction into fused multiply-adds
+        # may differ from the goal path's: the reported cost to the last bits)
+        check = (lambda p, q: assert_same(p, q, cost_rtol=1e-13)) if same else assert_close
         # look-ahead in the kernel (obstacle states)
         check(run(a, x0, obst, goal), run(r, x0, obst, goal))
         # explicit P (host path)
@@ -133,11 +91,11 @@ def test_goal_equivalent_reference_is_bit_identical(mg, N, no, B, lps, waves, lp
         ref_runs = run(r, x0, obst, goal, 2)
         r.set_reference(goal_ref(goal, 1), offset=np.full(B, 5, np.int32))
         r.reset_guess(x0)
-        assert_same(ref_runs, run(r, x0, obst, goal, 2))
+        assert_same(ref_runs, run(r, x0, obst, goal, 2), cost_rtol=1e-13)
         # cleared: the goal path again, same kernel family as a handle that never had one
         r.set_reference(None)
         assert r.kernel_name(B) == a.kernel_name(B)
-        assert_same(run(a, x0, obst, goal, 2), run(r, x0, obst, goal, 2))
+        assert_same(run(a, x0, obst, goal, 2), run(r, x0, obst, goal, 2), cost_rtol=1e-13)
 
 
 def _body_goal_equivalent_reference_fused_step(mg, N, no, B):
@@ -350,27 +308,18 @@ def test_shim_stage_yref_matches_set_reference(mg):
     shim.mpc.close()
 
 
-def _on_own_stream(fn, *args):
-    """device-API calls on a torch stream of their own: the legacy default stream's handle is 0, which the library reads as the handle's
-    own (non-blocking) stream, unordered with torch's copies"""
-    import torch
-    with torch.cuda.stream(torch.cuda.Stream()):
-        fn(*args)
-        torch.cuda.synchronize()
-
-
 @pytest.mark.parametrize("N,no,B", [(20, 3, 8), (30, 10, 4), (20, 15, 4), (50, 10, 4)])
 def test_goal_equivalent_reference_fused_step(mg, N, no, B):
     """the fused closed-loop step (device API): bit for bit the same with a goal-equivalent device reference"""
-    _on_own_stream(_body_goal_equivalent_reference_fused_step, mg, N, no, B)
+    on_own_stream(_body_goal_equivalent_reference_fused_step, mg, N, no, B)
 
 
 @pytest.mark.parametrize("N,no,B", NONTRIV)
 def test_nontrivial_reference_against_exact_qp(mg, N, no, B):
     """random smooth paths against the exact QP shifted to them, cost and linearisation (see the body)"""
-    _on_own_stream(_body_nontrivial_reference_against_exact_qp, mg, N, no, B)
+    on_own_stream(_body_nontrivial_reference_against_exact_qp, mg, N, no, B)
 
 
 def test_closed_loop_advancing_window(mg):
     """20 fused steps with ADVANCE_REF equal 20 steps with the window set each step; idle instances do not advance (see the body)"""
-    _on_own_stream(_body_closed_loop_advancing_window, mg)
+    on_own_stream(_body_closed_loop_advancing_window, mg)

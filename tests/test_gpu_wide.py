@@ -90,7 +90,7 @@ def test_wide_fused_step_against_the_oracle_loop_with_resync(mg, no):
     re-seeded with the GPU's state before every step; statuses, obstacle states (bit for bit), flags, step counts, margins, iterates"""
     mpc_gpu, orc = mg
     from mpc_gpu.world import reference_streams
-    from test_gpu_closed_loop import GpuLoop
+    from feature_loop import GpuLoop
     N, Tf, B, K = 20, 2.0, 12, 40
     obst, noise = reference_streams("RANDOM", range(B), no, K)
     x0 = np.tile([-7.0, -7.0, np.pi / 4, 0, 0], (B, 1)); goal = np.tile([7.0, 7.0], (B, 1))
