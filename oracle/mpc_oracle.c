@@ -358,12 +358,29 @@ void orc_shift(const orc_config *c, double *X, double *U)
 /* ------------------------------------------------------------------------------------------ */
 /* OCP pieces                                                                                   */
 /* ------------------------------------------------------------------------------------------ */
+/* Per-obstacle safety radii (orc_set_obstacle_radii): the checker's side of mpc_set_instance_params' r_safe[b][j].  While n radii are set, a config with
+ * n obstacles forms h_j with radius r[j] instead of c->r_safe (every stage; the cost and the exported QP go through obstacle_h too); a config with
+ * another obstacle count is not affected.  Process-wide like the investigation switches, set by a test around the solves of one group of instances that
+ * share their radii, and cleared behind them (n = 0). */
+#define ORC_MAX_RADII 32
+static int g_n_radii = 0;
+static double g_radii[ORC_MAX_RADII];
+int orc_set_obstacle_radii(int n, const double *r)
+{
+    if (n < 0 || n > ORC_MAX_RADII || (n > 0 && !r)) return -1;
+    for (int j = 0; j < n; j++) g_radii[j] = r[j];
+    g_n_radii = n;
+    return 0;
+}
+
 /* robot_model.py:60-65 */
 static void obstacle_h(const orc_config *c, const double *x, const double *p, double *h, double *dh)
 {
+    const int own = g_n_radii > 0 && g_n_radii == c->n_obst;
     for (int j = 0; j < c->n_obst; j++) {
         double ex = x[0] - p[2 * j], ey = x[1] - p[2 * j + 1];
-        h[j] = ex * ex + ey * ey - c->r_safe * c->r_safe;
+        const double r = own ? g_radii[j] : c->r_safe;
+        h[j] = ex * ex + ey * ey - r * r;
         if (dh) { dh[2 * j] = 2 * ex; dh[2 * j + 1] = 2 * ey; }
     }
 }

@@ -162,6 +162,8 @@ double orc_last_res_g(void);
 double orc_last_step_norm(void);
 /* investigation switches of scripts/converged_unmatched.py (mpc_oracle.c says which); process-wide, default 0, never set by tests */
 void orc_set_investigation(int switches);
+/* per-obstacle safety radii for configs with n obstacles (n = 0: off, the default; at most 32); process-wide, see mpc_oracle.c.  0, or -1 for a bad n */
+int orc_set_obstacle_radii(int n, const double *r);
 /* debugging aid: record (mu, sigma, alpha, cmax) of every IPM iteration of subsequent single solves into buf[4*cap] */
 void orc_set_trace(double *buf, int cap);
 

@@ -3,6 +3,7 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 Pinned per seed by the closed-loop tables the reference recorded (see oracle/mpc_oracle.h, tests/test_oracle_golden.py).
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -211,6 +212,23 @@ def set_investigation(switches):
     """investigation switches of scripts/converged_unmatched.py (mpc_oracle.c orc_set_investigation); process-wide, never called by tests"""
     lib().orc_set_investigation.argtypes = [C.c_int]
     lib().orc_set_investigation(int(switches))
+
+
+@contextlib.contextmanager
+def obstacle_radii(r):
+    """per-obstacle safety radii r (n_obst,) for every oracle call inside the block on a config with len(r) obstacles (mpc_oracle.c
+    orc_set_obstacle_radii; process-wide, cleared on the way out); None: nothing is set"""
+    if r is None:
+        yield
+        return
+    r = _a(r)
+    lib().orc_set_obstacle_radii.argtypes = [C.c_int, _dp]
+    if lib().orc_set_obstacle_radii(len(r), r) != 0:
+        raise ValueError(f"obstacle_radii: 1 .. 32 radii, got {len(r)}")
+    try:
+        yield
+    finally:
+        lib().orc_set_obstacle_radii(0, r)
 
 
 def rti_solve_batch(cfg, x0, P, goal, X, U, nthreads=0):

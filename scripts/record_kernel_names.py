@@ -1,14 +1,16 @@
-"""Record what mpc_get_kernel_name answers for every handle state of a sweep: tests/golden/kernel_names.json.
+"""Record what mpc_get_kernel_name answers for every handle state of a sweep: tests/golden/kernel_names.json (feature levels 0 to 3) and
+tests/golden/kernel_names_bounds.json (the states with instance bounds, level 4: a record of its own, run-length encoded, so that adding it left the first
+file byte for byte what it was).
 
 Usage (on the GPU the crossovers were measured on; creating a handle needs a device, naming a kernel launches nothing):
-    python scripts/record_kernel_names.py [OUT.json]
+    python scripts/record_kernel_names.py [OUT_DIRECTORY]
 The record pins the host dispatcher across refactors: tests/test_gpu_kernel_names.py replays `sweep()` on the current build and compares every
 entry -- a kernel name, or the text of the MpcError the call (or a setter in front of it) raised.  Run it on the commit whose answers are to be kept.
 
 The sweep: N x n_obst (mpc_create up to 10 obstacles, mpc_create2 beyond, where N = 40 must refuse) x feature state x the override product of
 tests/test_gpu_every_kernel.py::_configs x batch sizes on either side of every crossover of pick_lanes / pick_split / pick_waves (multiples of the
 device's SIMD count, which is why the record carries the compute-unit count) x look-ahead both ways at N = 40 (the compact / dense LDS decision).
-Entries are indices into one list of distinct strings, in sweep order.
+Entries are indices into one list of distinct strings, in sweep order; in a run-length encoded record ("rle": true) [index, count] pairs.
 """
 import ctypes as C
 import itertools
@@ -26,7 +28,10 @@ for p in (ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd")):
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_names.json")
 HORIZONS = (10, 20, 31, 40)
 OBST_CREATE, OBST_CREATE2 = (2, 3, 4, 5, 7, 10), (11, 15, 20, 25, 32)
+GOLDEN_BOUNDS = os.path.join(ROOT, "tests", "golden", "kernel_names_bounds.json")
 FEATURES = ("none", "reference", "instance parameters", "obstacle mask", "mask + parameters + reference")
+FEATURES_BOUNDS = ("instance bounds", "bounds + mask + parameters + reference")
+RECORDS = ((GOLDEN, FEATURES, False), (GOLDEN_BOUNDS, FEATURES_BOUNDS, True))      # (file, feature states, run-length encoded)
 MAX_BATCH = 4
 
 
@@ -68,13 +73,15 @@ def _open(mpc_gpu, N, no, create):
 
 
 def _set_feature(s, feature):
-    s.set_reference(None); s.set_instance_params(); s.set_obstacle_mask(None)
+    s.set_reference(None); s.set_instance_params(); s.set_obstacle_mask(None); s.set_instance_bounds()
     if "reference" in feature:
         s.set_reference(np.zeros((MAX_BATCH, s.N + 1, 6)))
     if "parameters" in feature:
         s.set_instance_params(W=np.ones((MAX_BATCH, 6)))
     if "mask" in feature:
         s.set_obstacle_mask(np.ones((MAX_BATCH, s.n_obst), dtype=bool))
+    if "bounds" in feature:      # the handle's own values
+        s.set_instance_bounds(bx_lo=list(s.cfg.bx_lo), bx_hi=list(s.cfg.bx_hi), bu_lo=list(s.cfg.bu_lo), bu_hi=list(s.cfg.bu_hi))
 
 
 def _set_overrides(s, lanes, lps, waves, rowpar, mfma, blk2):
@@ -88,7 +95,7 @@ def _set_overrides(s, lanes, lps, waves, rowpar, mfma, blk2):
         s.set_matrix_cores(True)
 
 
-def sweep(mpc_gpu, cu_count):
+def sweep(mpc_gpu, cu_count, features=FEATURES):
     """{"N n_obst entry_point": [entry, ...]}: the answers in sweep order.  A refused creation or a refused setter is ONE entry, its error text."""
     out = {}
     for N, no, create in cases():
@@ -99,7 +106,7 @@ def sweep(mpc_gpu, cu_count):
             entries.append(str(e))
             continue
         with s:
-            for feature in FEATURES:
+            for feature in features:
                 _set_feature(s, feature)
                 for ov in overrides():
                     try:
@@ -120,20 +127,70 @@ def compute_units():
     return int(torch.cuda.get_device_properties(0).multi_processor_count)
 
 
-def main(path):
+def load(path):
+    """(compute units, {case: [entry, ...]}) of a record, either encoding"""
+    with open(path) as f:
+        rec = json.load(f)
+    if rec.get("rle"):
+        cases = {c: [rec["strings"][k] for k, n in runs for _ in range(n)] for c, runs in rec["cases"].items()}
+    else:
+        cases = {c: [rec["strings"][k] for k in idx] for c, idx in rec["cases"].items()}
+    return rec["compute_units"], cases
+
+
+def dump(path, cu, answers, rle):
+    strings = sorted({e for v in answers.values() for e in v})
+    index = {e: k for k, e in enumerate(strings)}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        if not rle:
+            json.dump({"compute_units": cu, "strings": strings, "cases": {k: [index[e] for e in v] for k, v in answers.items()}}, f, separators=(",", ":"))
+            f.write("\n")
+            return strings
+        lines = []      # one case per line: a re-record changes the lines of the cases that changed
+        for case, v in answers.items():
+            runs = []
+            for e in v:
+                if runs and runs[-1][0] == index[e]:
+                    runs[-1][1] += 1
+                else:
+                    runs.append([index[e], 1])
+            lines.append(f"{json.dumps(case)}:{json.dumps(runs, separators=(',', ':'))}")
+        f.write('{"compute_units":%d,"rle":true,\n"strings":[\n%s],\n"cases":{\n%s}}\n' % (cu, ",\n".join(json.dumps(e) for e in strings), ",\n".join(lines)))
+    return strings
+
+
+def against_previous(old_cases, answers):
+    """What a re-record changes, before the file is overwritten: (entries that answer what they did, [(case, position, before, now)] of those that do not,
+    counting a changed length as one)"""
+    kept, changed = 0, []
+    for case, want in old_cases.items():
+        now = answers.get(case, [])
+        if len(now) != len(want):
+            changed.append((case, -1, len(want), len(now)))
+            continue
+        kept += sum(a == b for a, b in zip(now, want))
+        changed += [(case, k, b, a) for k, (a, b) in enumerate(zip(now, want)) if a != b]
+    return kept, changed
+
+
+def main(out_dir=None):
     import mpc_gpu
     mpc_gpu.build()
     cu = compute_units()
-    answers = sweep(mpc_gpu, cu)
-    strings = sorted({e for v in answers.values() for e in v})
-    index = {e: k for k, e in enumerate(strings)}
-    rec = {"compute_units": cu, "strings": strings, "cases": {k: [index[e] for e in v] for k, v in answers.items()}}
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as f:
-        json.dump(rec, f, separators=(",", ":"))
-        f.write("\n")
-    print(f"{path}: {sum(len(v) for v in answers.values())} entries, {len(strings)} distinct, {len(answers)} cases, {cu} compute units")
+    for golden, features, rle in RECORDS:
+        path = golden if out_dir is None else os.path.join(out_dir, os.path.basename(golden))
+        answers = sweep(mpc_gpu, cu, features)
+        if os.path.exists(golden):
+            old_cu, old_cases = load(golden)
+            if old_cu == cu:
+                kept, changed = against_previous(old_cases, answers)
+                print(f"{os.path.basename(golden)}: {kept} entries of {len(old_cases)} recorded cases answer what they did, {len(changed)} do not", changed[:5])
+        strings = dump(path, cu, answers, rle)
+        print(f"{path}: {sum(len(v) for v in answers.values())} entries, {len(strings)} distinct, {len(answers)} cases, {cu} compute units")
+        for e in strings:
+            print("   ", e)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else GOLDEN)
+    main(sys.argv[1] if len(sys.argv) > 1 else None)

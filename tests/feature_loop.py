@@ -2,7 +2,8 @@
 off-default sweep): the `mg` fixture, handles and repeated solves (`make`, `run`, `assert_same`), and the ONE transcription of the fused control
 step's bookkeeping -- `fused_loop` (the resident fused closed loop) against `host_driven_loop` (the same steps through solve + plant_step + shift + the
 obstacle kernel, the episode words in numpy), compared by `assert_fused_equals_host`.  `FeatureStack` says what is layered on the handle; a new feature
-level adds a field to it, not a loop of its own.  (tests/helpers.py is the oracle / QP side.)  torch is imported inside the functions only."""
+level adds a field to it, not a loop of its own.  `step_bookkeeping` is that step's episode bookkeeping in numpy, and `Banded` the guard-banded device
+arrays of the every-kernel sweeps.  (tests/helpers.py is the oracle / QP side.)  torch is imported inside the functions only."""
 import dataclasses
 
 import numpy as np
@@ -88,6 +89,31 @@ def smooth_path(rng, B, T):
         R[b, :, 2] = rng.uniform(-1, 1) + 0.3 * t; R[b, :, 3] = rng.uniform(-0.5, 0.5) * np.cos(t)
         R[b, :, 4] = rng.uniform(-0.5, 0.5); R[b, :, 5] = rng.uniform(-0.3, 0.3)
     return R
+
+
+GUARD = 64           # sentinel words on either side of every array of a Banded buffer
+
+
+class Banded:
+    """device arrays carved out of one sentinel-filled buffer"""
+
+    def __init__(self, torch, dev):
+        self.torch, self.dev, self.items = torch, dev, []
+
+    def f64(self, *shape, init=0.0):
+        t = self.torch.full((int(np.prod(shape)) + 2 * GUARD,), -7.25e77, dtype=self.torch.float64, device=self.dev)
+        v = t[GUARD:-GUARD].view(*shape); v.fill_(init); self.items.append((t, "f64")); return v
+
+    def i32(self, *shape, init=0):
+        t = self.torch.full((int(np.prod(shape)) + 2 * GUARD,), -1234567, dtype=self.torch.int32, device=self.dev)
+        v = t[GUARD:-GUARD].view(*shape); v.fill_(init); self.items.append((t, "i32")); return v
+
+    def intact(self):
+        for t, kind in self.items:
+            s = -7.25e77 if kind == "f64" else -1234567
+            if not (bool((t[:GUARD] == s).all()) and bool((t[-GUARD:] == s).all())):
+                return False
+        return True
 
 
 # ---------------------------------------------------------------------------------------------------------------- the fused loop and its transcription
@@ -182,6 +208,22 @@ def fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack, solver=None):
     return res
 
 
+def step_bookkeeping(x, ob, goal, act, r_hit, arena, alive, mm, fl, ns):
+    """The episode bookkeeping of one fused step in numpy, on the state after the plant step and the obstacle motion: the running minimum margin over the
+    present obstacles (act (B, n_obst); r_hit (B, n_obst)), the arena, hit and goal flags and the step counters, updated in place for the instances
+    `alive` alone.  Returns which instances are within the goal tolerance."""
+    dist = np.linalg.norm(x[:, None, :2] - ob[:, :, :2], axis=2) - r_hit
+    margin = np.where(act, dist, np.inf).min(axis=1)
+    mm[alive] = np.minimum(mm, margin)[alive]
+    a_ = x[:, 0]; b_ = x[:, 1]
+    fl[alive & ((a_ < arena[0]) | (a_ > arena[1]) | (b_ < arena[2]) | (b_ > arena[3]))] |= 2
+    fl[alive & (mm <= 0.0)] |= 4
+    reached = np.linalg.norm(x[:, :2] - goal, axis=1) <= 0.15
+    fl[alive & reached] |= 1
+    ns[alive & ~reached] += 1
+    return reached
+
+
 def host_driven_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack):
     """the same steps through mpc_solve_obst + mpc_plant_step + mpc_shift (and the obstacle motion kernel), a mask or bounds that switch set through
     the host setters at the same step, the bookkeeping in numpy over the present obstacles: an instance that has reached its goal idles, nothing of
@@ -225,16 +267,7 @@ def host_driven_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack):
             s.set_warmstart(Xn, Un)
             x[alive] = xn[alive]; ob[alive] = obn[alive]; u_last[alive] = o["u0"][alive]
             off[alive] += 1
-            dist = np.linalg.norm(x[:, None, :2] - ob[:, :, :2], axis=2) - r_hit
-            margin = np.where(act, dist, np.inf).min(axis=1)
-            mm[alive] = np.minimum(mm, margin)[alive]
-            a_ = x[:, 0]; b_ = x[:, 1]
-            fl[alive & ((a_ < ar[0]) | (a_ > ar[1]) | (b_ < ar[2]) | (b_ > ar[3]))] |= 2
-            fl[alive & (mm <= 0.0)] |= 4
-            reached = np.linalg.norm(x[:, :2] - goal, axis=1) <= 0.15
-            fl[alive & reached] |= 1
-            ns[alive & ~reached] += 1
-            alive &= ~reached
+            alive &= ~step_bookkeeping(x, ob, goal, act, r_hit, ar, alive, mm, fl, ns)
             us.append(u_last.copy())
         X, U = s.get_traj(B)
     return dict(x=x, obst=ob, X=X, U=U, u0=np.array(us), mm=mm, ns=ns, fl=fl)

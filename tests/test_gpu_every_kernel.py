@@ -11,10 +11,10 @@ import itertools
 import numpy as np
 import pytest
 
+from feature_loop import Banded
 from helpers import random_batch
 
 pytestmark = pytest.mark.gpu
-GUARD = 64           # sentinel words on either side of every array
 
 
 def _configs(mpc_gpu):
@@ -42,28 +42,6 @@ def _configs(mpc_gpu):
             if name not in seen:
                 seen.add(name); out.append((N, no, dict(lanes=lanes, lps=lps, waves=waves, rowpar=rowpar, mfma=mfma, blk2=blk2), name))
     return out
-
-
-class Banded:
-    """device arrays carved out of one sentinel-filled buffer"""
-
-    def __init__(self, torch, dev):
-        self.torch, self.dev, self.items = torch, dev, []
-
-    def f64(self, *shape, init=0.0):
-        t = self.torch.full((int(np.prod(shape)) + 2 * GUARD,), -7.25e77, dtype=self.torch.float64, device=self.dev)
-        v = t[GUARD:-GUARD].view(*shape); v.fill_(init); self.items.append((t, "f64")); return v
-
-    def i32(self, *shape, init=0):
-        t = self.torch.full((int(np.prod(shape)) + 2 * GUARD,), -1234567, dtype=self.torch.int32, device=self.dev)
-        v = t[GUARD:-GUARD].view(*shape); v.fill_(init); self.items.append((t, "i32")); return v
-
-    def intact(self):
-        for t, kind in self.items:
-            s = -7.25e77 if kind == "f64" else -1234567
-            if not (bool((t[:GUARD] == s).all()) and bool((t[-GUARD:] == s).all())):
-                return False
-        return True
 
 
 def _one_step(mpc_gpu, torch, N, no, ov, B, x0, goal, obst, noise):
