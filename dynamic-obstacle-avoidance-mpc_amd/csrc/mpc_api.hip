@@ -102,6 +102,10 @@ struct mpc_handle {
     const double *d_ip_b;             // ... the packed table the IBND kernels read (KParams::ip_b), [.][kIpB]
     double *d_ip_b_own;               // ... handle-owned table of the host form, max_batch rows, allocated on first use
     uint32_t *d_omask_full;           // ... every obstacle present in max_batch words: what the IBND kernels (built on the masks' code) read without a mask
+    int sqp_max;                      // SQP iterations per launch (mpc_set_sqp): <= 1 off
+    double sqp_tol;                   // ... the step norm at or below which an instance stops
+    int32_t *d_sqp_iters;             // ... the caller's words for the iterations run (mpc_set_sqp_iters_out_dev), or null
+    double *d_ip_b_cfg;               // ... the handle's own bounds in max_batch rows: what the NSQP kernels (built on the bounds' code) read without instance bounds
 };
 
 namespace {
@@ -182,7 +186,7 @@ mpc::KParams solve_params(mpc_handle *h, int batch, const double *x0, const doub
 // to this mapping; unless overridden.  Packing instances into one wavefront multiplies throughput for large batches.
 // (an obstacle mask is a run-time row count by nature: with one set, a handle whose count fills its capacity runs the run-time-count variants too;
 // the instance bounds are built on the masks' code, so they do the same)
-bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || h->om_mode != 0 || h->bd_mode != 0; }
+bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || h->om_mode != 0 || h->bd_mode != 0 || h->sqp_max > 1; }
 
 int pick_lanes(mpc_handle *h, int batch)
 {
@@ -274,11 +278,13 @@ int check_wide(const mpc_handle *h)
 // mappings, plan and refusals; without instance parameters the tables they read hold the handle's own values
 // Per-instance box bounds (mpc_set_instance_bounds), level 4: the OSEL instantiations with one more flag -- the same mappings, plan and refusals; without a
 // mask they read words of the handle's own that have every obstacle present
-int feature_level(const mpc_handle *h) { return h->bd_mode != 0 ? 4 : (h->om_mode != 0 ? 3 : (h->ip_mode != 0 ? 2 : (h->d_yref != nullptr ? 1 : 0))); }
+// Several SQP iterations per launch (mpc_set_sqp), level 5: the IBND instantiations with one more flag -- the same mappings, plan and refusals; without
+// instance bounds they read a table of the handle's own bounds
+int feature_level(const mpc_handle *h) { return h->sqp_max > 1 ? 5 : h->bd_mode != 0 ? 4 : (h->om_mode != 0 ? 3 : (h->ip_mode != 0 ? 2 : (h->d_yref != nullptr ? 1 : 0))); }
 
 int check_feature_mapping(const mpc_handle *h)
 {
-    const char *what[] = {"", "a per-stage reference", "per-instance parameters", "an obstacle mask", "instance bounds"};
+    const char *what[] = {"", "a per-stage reference", "per-instance parameters", "an obstacle mask", "instance bounds", "several SQP iterations per launch"};
     const char *w = what[feature_level(h)];
     if (h->use_mfma) return fail(MPC_ERR_ARG, "%s: no build for the matrix-core factorisation (mpc_set_matrix_cores)", w);
     if (!h->row_parallel) return fail(MPC_ERR_ARG, "%s: no build for the systolic sweeps (mpc_set_row_parallel(0))", w);
@@ -457,7 +463,7 @@ int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
         p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
     }
     if (what != kForSolve) return MPC_OK;
-    if (h->om_mode || h->bd_mode) {
+    if (h->om_mode || h->bd_mode || h->sqp_max > 1) {
         if (h->om_mode && p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
         if (!h->ip_mode) {
             if (!h->ip_default) return fail(MPC_ERR_ARG, "internal: the default instance tables of the obstacle mask are not filled");
@@ -468,6 +474,10 @@ int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
     if (h->bd_mode) {
         if (p.batch > h->bd_batch) return fail(MPC_ERR_ARG, "the instance bounds set by mpc_set_instance_bounds cover fewer instances than this solve");
         p.ip_b = h->d_ip_b;
+    }
+    if (h->sqp_max > 1) {
+        if (!h->bd_mode) p.ip_b = h->d_ip_b_cfg;
+        p.sqp_max = h->sqp_max; p.sqp_tol = h->sqp_tol; p.sqp_iters = h->d_sqp_iters;
     }
     // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
     p.alpha = h->d_alpha;
@@ -596,7 +606,7 @@ int mpc_destroy(mpc_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
                     h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own,
-                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own, h->d_ip_b_own, h->d_omask_full};
+                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own, h->d_ip_b_own, h->d_omask_full, h->d_ip_b_cfg};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->h_pack) (void)hipHostFree(h->h_pack);
@@ -1182,7 +1192,7 @@ int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const dou
     if (!h) return fail(MPC_ERR_ARG, "null handle");
     if (!W && !We && !r_safe && !r_hit) {
         h->ip_mode = 0; h->ip_batch = 0;
-        if (h->om_mode || h->bd_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
+        if (h->om_mode || h->bd_mode || h->sqp_max > 1) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
         return MPC_OK;
     }
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "per-instance parameters need batch in [1, max_batch]");
@@ -1216,7 +1226,7 @@ int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *
     if (!h) return fail(MPC_ERR_ARG, "null handle");
     if (!d_W && !d_We && !d_r_safe && !d_r_hit) {
         h->ip_mode = 0; h->ip_batch = 0;
-        if (h->om_mode || h->bd_mode) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
+        if (h->om_mode || h->bd_mode || h->sqp_max > 1) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
         return MPC_OK;
     }
     HIPCHK(hipSetDevice(h->device));
@@ -1312,6 +1322,39 @@ int mpc_set_instance_bounds_dev(mpc_handle *h, const double *d_bounds)
     HIPCHK(hipSetDevice(h->device));
     int rc = bounds_companions(h); if (rc) return rc;
     h->d_ip_b = d_bounds; h->bd_mode = 2; h->bd_batch = h->max_batch;
+    return MPC_OK;
+}
+
+/* ---------------------------------------------- several SQP iterations per launch ---------------------------------------------- */
+
+int mpc_set_sqp(mpc_handle *h, int max_iter, double step_tol)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (max_iter < 1 || max_iter > MPC_MAX_SQP_ITER) return fail(MPC_ERR_ARG, "mpc_set_sqp: max_iter must be in [1, MPC_MAX_SQP_ITER]");
+    if (!(step_tol >= 0.0)) return fail(MPC_ERR_ARG, "mpc_set_sqp: step_tol must be >= 0 (+inf is valid, NaN is not)");
+    if (max_iter > 1) {      // what the NSQP kernels read beside the features that are set: the bounds' companions and the handle's own bounds
+        HIPCHK(hipSetDevice(h->device));
+        int rc = bounds_companions(h); if (rc) return rc;
+        if (!h->d_ip_b_cfg) {
+            std::vector<double> tab((size_t)h->max_batch * mpc::kIpB);
+            for (int b = 0; b < h->max_batch; b++) {
+                double *row = tab.data() + (size_t)b * mpc::kIpB;
+                for (int k = 0; k < 2; k++) { row[mpc::kIpBuLo + k] = h->cfg.bu_lo[k]; row[mpc::kIpBuHi + k] = h->cfg.bu_hi[k]; }
+                for (int k = 0; k < 4; k++) { row[mpc::kIpBxLo + k] = h->cfg.bx_lo[k]; row[mpc::kIpBxHi + k] = h->cfg.bx_hi[k]; }
+            }
+            HIPCHK(hipMalloc(&h->d_ip_b_cfg, tab.size() * sizeof(double)));
+            HIPCHK(hipMemcpyAsync(h->d_ip_b_cfg, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+    }
+    h->sqp_max = max_iter; h->sqp_tol = step_tol;
+    return MPC_OK;
+}
+
+int mpc_set_sqp_iters_out_dev(mpc_handle *h, int32_t *d_sqp_iters)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    h->d_sqp_iters = d_sqp_iters;
     return MPC_OK;
 }
 

@@ -109,6 +109,10 @@ struct KParams {
     const uint32_t *omask;    // [B]: bit j set = obstacle j of the instance exists (bits at and above n_obst are ignored)
     // ---- per-instance box bounds (mpc_set_instance_bounds; read only by the IBND instantiations, which read NONE of bx_lo, bx_hi, bu_lo, bu_hi above) ----
     const double *ip_b;       // [B][kIpB]: bu_lo[2], bu_hi[2], bx_lo[4], bx_hi[4] of an instance (bx in mpc_config's order x, y, v, om)
+    // ---- several SQP iterations per launch (mpc_set_sqp; read only by the NSQP instantiations) ----
+    int sqp_max;              // iterations per launch at most (2 .. MPC_MAX_SQP_ITER)
+    double sqp_tol;           // an instance stops behind an iteration whose applied step has max-norm <= sqp_tol (0: never, +inf: behind the first)
+    int32_t *sqp_iters;       // [B] iterations an instance ran, or null
 };
 
 // Layout of one row of KParams::ip_w
@@ -348,6 +352,13 @@ __device__ __forceinline__ void tail_store_iterate(int fused, int i, int N, bool
         }
         if (has_u) { Ug[i * 2] = ui[0]; Ug[i * 2 + 1] = ui[1]; }
     }
+}
+// NSQP (several SQP iterations per launch): max-norm of the step this lane's stage applied -- every entry of dX (stages 0 .. N) and dU, in double, from the step itself
+__device__ __forceinline__ double sqp_step_norm(bool act, bool has_u, const double z[7])
+{
+    const double mx = fmax(fmax(fmax(fabs(z[2]), fabs(z[3])), fabs(z[4])), fmax(fabs(z[5]), fabs(z[6])));
+    const double mu = fmax(fabs(z[0]), fabs(z[1]));
+    return fmax(act ? mx : 0.0, has_u ? mu : 0.0);
 }
 // what a solve adds to KParams::status_acc
 __device__ __forceinline__ int tail_status_acc_word(int status) { return (status == 4 ? 1 : 0) + (status == 2 ? 65536 : 0); }
@@ -2216,9 +2227,12 @@ __device__ __forceinline__ void systolic_rollout(int stage, int N, const StageLi
 // slot replicates the highest present obstacle (zero with an empty word), as the slots beyond the count replicate the last one.  Built on the MASKED IPAR code
 // IBND: per-instance box bounds (KParams::ip_b; mpc_set_instance_bounds): lo[] / hi[] are the instance's row of the table, at the start and in every
 // reload_bounds(), in place of the kernel-argument bounds.  Built on the OSEL code
-template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false>
+// NSQP: up to KParams::sqp_max SQP iterations in one launch (mpc_set_sqp).  Everything from the linearisation to the full step on the iterate runs again on the
+// updated registers (sqp_again below); the inputs of the launch, the look-ahead and the slack schedule are those of the first iteration.  Built on the IBND code
+template <int NOBST, int G, int FACT, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false, bool NSQP = false>
 __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
 {
+    static_assert(!NSQP || IBND, "the SQP loop is built on the per-instance bounds' code");
     static_assert(!IBND || OSEL, "the per-instance bounds are built on the obstacle masks' code");
     static_assert(!REF || (G == 64 && FACT == 3), "the per-stage reference runs on one instance per wavefront, compact stage blocks");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
@@ -2365,6 +2379,9 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     const bool vs = act && (i >= 1) && (p.soft_h ? (zpen > 0.0) : true);   // obstacle rows present at this stage
     const bool soft = p.soft_h != 0;
 
+    // NSQP: iterations run and the interior-point iterations they took; an iteration starts here, on the iterate the registers hold
+    [[maybe_unused]] int sqp_k = 0, sqp_it = 0;      // (read by the NSQP instantiations alone, like the label below)
+sqp_again: ;
     // ---- linearise ----
     double lin0 = 0.0;
     double d0[5] = {0, 0, 0, 0, 0};
@@ -3493,6 +3510,22 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
             gl[0] = gg[0]; gl[1] = gg[1];
         }
     }
+    if constexpr (NSQP) {
+        // the full step of this iteration; then either the next iteration -- the successor state every stage's defect needs comes from the neighbouring lane
+        // (one instance per wavefront), nothing goes through memory -- or the tail below, once, on the last status.  The exit is wave-uniform
+        static_assert(G == 64, "the SQP loop runs one instance per wavefront");
+        status = ipm_finite_step<G>(status, z, lane);
+        tail_full_step(status, z, xi, ui);
+        sqp_k += 1; sqp_it += it_done;
+        const double nrm = wave_uniform(seg_max<G>(sqp_step_norm(act, has_u, z), lane));
+        if (!ep_done && status != 4 && sqp_k < p.sqp_max && !(nrm <= p.sqp_tol)) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) { xi[c] = act ? xi[c] : 0.0; const double r = from_right(xi[c]); xnext[c] = has_u ? r : 0.0; }
+            ui[0] = has_u ? ui[0] : 0.0; ui[1] = has_u ? ui[1] : 0.0;
+            goto sqp_again;
+        }
+        it_done = sqp_it;
+    }
     typedef const __attribute__((address_space(4))) KParams KTail;
     // THE TAIL READS ITS KERNEL ARGUMENTS AGAIN.  Output pointers and fused-step parameters are used only from here on; carried from the prologue they live
     // in (spilled) scalar registers across the whole interior point -- and in one instantiation (rti_solve_kernel<3, 32, 2>) this toolchain's register allocator
@@ -3532,11 +3565,13 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
     // (the step and the iterate's store stay written out here: through tail_full_step / tail_store_iterate the compiler commutes one v_add_f64 of the interior
     // point in 8 resp. 17 instantiations, e.g. rti_solve_kernel<5, 64, 2, true>, listing line 3420 -- same length, same registers, not the same text)
     const bool store = valid && !ep_done;
+    if constexpr (!NSQP) {
     status = ipm_finite_step<G>(status, z, lane);
     if (status != 4) {
 #pragma unroll
         for (int c = 0; c < 5; c++) xi[c] += z[2 + c];
         ui[0] += z[0]; ui[1] += z[1];
+    }
     }
     const double u_apply[2] = {lane_value_seg<G>(ui[0], lane), lane_value_seg<G>(ui[1], lane)};   // u* = U[0] of this instance
     tail_reset_on_fail(t_fused, status, x0v, gl[1], i, N, xi, ui);
@@ -3647,6 +3682,7 @@ __global__ __launch_bounds__(64) void rti_solve_kernel(const KParams p)
         if (t_status_acc) t_status_acc[inst] += tail_status_acc_word(status);
         if (t_status) t_status[inst] = status;
         if (t_iters) t_iters[inst] = it_done;
+        if constexpr (NSQP) { if (pt->sqp_iters) pt->sqp_iters[inst] = sqp_k; }
     }
     if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
         if ((t_fused & kFuseAdvanceRef) && i == 0 && store && pt->ref_off) pt->ref_off[inst] += 1;

@@ -64,9 +64,12 @@ __device__ __forceinline__ double nth_of_six(double a0, double a1, double a2, do
 // obstacle (zero with an empty word), so nothing an absent entry of P / obst holds is ever read into the row state.  Built on the MASKED IPAR code
 // IBND: per-instance box bounds (KParams::ip_b; mpc_set_instance_bounds): the lo / hi of a box row come from the instance's row of the table (scalar loads)
 // in place of the kernel-argument bounds; they are consumed where the rows are initialised and not carried.  Built on the OSEL code
-template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false>
+// NSQP: up to KParams::sqp_max SQP iterations in one launch (mpc_set_sqp), as in rti_solve_kernel: everything from the finite test of the inputs to the full step
+// on the iterate runs again on the updated registers (sqp_again below).  Built on the IBND code
+template <int NOBST, int LPS, bool W2 = false, bool MASKED = false, bool BLK2 = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false, bool NSQP = false>
 __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
 {
+    static_assert(!NSQP || (IBND && !W2 && !BLK2), "the SQP loop is built on the per-instance bounds' code (dense blocks, one wavefront per SIMD)");
     static_assert(!IBND || OSEL, "the per-instance bounds are built on the obstacle masks' code");
     static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
     static_assert(!REF || !BLK2, "the per-stage reference is not built for the block-2 recursions");
@@ -252,6 +255,9 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         }
     }
     const bool ep_done = (ep_word & 1) != 0;
+    // NSQP: iterations run and the interior-point iterations they took; an iteration starts here, on the iterate the registers hold
+    [[maybe_unused]] int sqp_k = 0, sqp_it = 0;      // (read by the NSQP instantiations alone, like the label below)
+sqp_again: ;
     // Non-finite inputs must not pass as a converged solve (fmax() drops NaN, so the residual norm would not show them): one sum over
     // everything this lane read decides, the instance then fails at once (status 4) -- see rti_solve_kernel
     double fin = gl[0] + gl[1] + ui[0] + ui[1];
@@ -1147,6 +1153,28 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         for (int c = 0; c < 5; c++) x0v[c] = xg[c];
         gl[0] = gg[0]; gl[1] = gg[1];
     }
+    if constexpr (NSQP) {
+        // the full step of this iteration; then either the next iteration -- every lane of a stage holds the stage's iterate, so the successor state the defect
+        // needs is LPS lanes to the right (wave shifts, nothing goes through memory); x0 and the goal have just been read again -- or the epilogue below, once,
+        // on the last status.  The exit is wave-uniform
+        status = ipm_finite_step<64>(status, z, lane);
+        tail_full_step(status, z, xi, ui);
+        sqp_k += 1; sqp_it += it_done;
+        const double nrm = wave_uniform(seg_max<64>(sqp_step_norm(act, has_u, z), lane));
+        if (!ep_done && status != 4 && sqp_k < p.sqp_max && !(nrm <= p.sqp_tol)) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) {
+                xi[c] = act ? xi[c] : 0.0;
+                double r = from_right(xi[c]);
+#pragma unroll
+                for (int q = 1; q < LPS; q++) r = from_right(r);
+                xnext[c] = has_u ? r : 0.0;
+            }
+            ui[0] = has_u ? ui[0] : 0.0; ui[1] = has_u ? ui[1] : 0.0;
+            goto sqp_again;
+        }
+        it_done = sqp_it;
+    }
     if constexpr (FX) {
         // ---- epilogue: what it reads from memory is requested first, in one group (the plant state and the goal above, the obstacle states, the accumulators, the
         //      episode words); then the arithmetic; every store comes last, in one group, so that no wait for a load stands behind the acknowledgement of a store ----
@@ -1165,8 +1193,10 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
             if (p.fused & kFuseMetrics) { ep_fl = p.ep_flags[inst]; ep_mm = p.ep_min_margin[inst]; }
         }
         // ---- full step on the iterate; status 4 leaves it unchanged: the solve tail, shared pieces tail_* (rti_kernel.hpp) ----
+        if constexpr (!NSQP) {
         status = ipm_finite_step<64>(status, z, lane);
         tail_full_step(status, z, xi, ui);
+        }
         const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0]
         tail_reset_on_fail(p.fused, status, x0v, gl[1], i, N, xi, ui);
         // ---- plant, obstacles, episode bookkeeping (fused closed-loop step) ----
@@ -1253,6 +1283,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
                                                                                                                    // instantiation of this branch selects the word differently, e.g. <3, 3, false> line 6549)
             if (p.status) p.status[inst] = status;
             if (p.iters) p.iters[inst] = it_done;
+            if constexpr (NSQP) { if (p.sqp_iters) p.sqp_iters[inst] = sqp_k; }
         }
         if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
             if ((p.fused & kFuseAdvanceRef) && lane0s && p.ref_off) p.ref_off[inst] += 1;
@@ -1260,8 +1291,10 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     } else {        // (the order these instantiations had; not indented)
     // ---- full step on the iterate; status 4 leaves it unchanged: the solve tail, shared pieces tail_* (rti_kernel.hpp) ----
     const bool store = !ep_done;
+    if constexpr (!NSQP) {
     status = ipm_finite_step<64>(status, z, lane);
     tail_full_step(status, z, xi, ui);
+    }
     const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0]
     tail_reset_on_fail(p.fused, status, x0v, gl[1], i, N, xi, ui);
     if (store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) tail_store_iterate(p.fused, i, N, act, has_u, xi, ui, Xg, Ug);
@@ -1342,6 +1375,7 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
         if (p.status_acc) p.status_acc[inst] += tail_status_acc_word(status);
         if (p.status) p.status[inst] = status;
         if (p.iters) p.iters[inst] = it_done;
+        if constexpr (NSQP) { if (p.sqp_iters) p.sqp_iters[inst] = sqp_k; }
     }
     if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
         if ((p.fused & kFuseAdvanceRef) && lane == 0 && store && p.ref_off) p.ref_off[inst] += 1;

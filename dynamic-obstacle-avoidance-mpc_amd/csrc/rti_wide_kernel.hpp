@@ -62,9 +62,12 @@ __device__ __forceinline__ void group_sync()
 // IPAR: per-instance cost constants and per-obstacle radii, as in rti_split_kernel (built on the REF code)
 // OSEL: per-instance obstacle masks, as in rti_split_kernel (the word is the same in every wavefront of the workgroup)
 // IBND: per-instance box bounds, as in rti_split_kernel (the row is the same in every wavefront of the workgroup)
-template <int CAP, int LPS, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false>
+// NSQP: up to KParams::sqp_max SQP iterations in one launch (mpc_set_sqp), as in rti_split_kernel; wavefront 0, which alone holds every stage's whole step,
+// hands the updated iterate to the others through the XS words, and the exit is workgroup-uniform (the step norm travels with the finite-step test, kSiteFin)
+template <int CAP, int LPS, bool MASKED = false, bool REF = false, bool IPAR = false, bool OSEL = false, bool IBND = false, bool NSQP = false>
 __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(const KParams p)
 {
+    static_assert(!NSQP || IBND, "the SQP loop is built on the per-instance bounds' code");
     static_assert(!OSEL || (IPAR && MASKED), "the obstacle masks are built on the per-instance parameters' code with a run-time row count");
     static_assert(!IBND || OSEL, "the per-instance bounds are built on the obstacle masks' code");
     static_assert(!IPAR || REF, "the per-instance parameters are built on the per-stage reference's code");
@@ -189,6 +192,9 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
         }
     }
     const bool ep_done = (ep_word & 1) != 0;
+    // NSQP: iterations run and the interior-point iterations they took; an iteration starts here, on the iterate the registers hold
+    [[maybe_unused]] int sqp_k = 0, sqp_it = 0;      // (read by the NSQP instantiations alone, like the label below)
+sqp_again: ;
     double fin = gl[0] + gl[1] + ui[0] + ui[1];
 #pragma unroll
     for (int c = 0; c < 5; c++) fin += x0v[c] + xi[c] + xnext[c];
@@ -793,12 +799,40 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
     // ---- full step on the iterate; status 4 leaves it unchanged.  Wavefront 0 holds every stage's whole step, the others the (x, y) part.  The solve tail,
     //      shared pieces tail_* (rti_kernel.hpp) ----
     const bool store = !ep_done;
+    [[maybe_unused]] double sqp_nrm = 0.0;      // NSQP: wavefront 0's step norm, the same in every wavefront behind the reduction below
     {
         double s4 = ipm_finite_step<64>(status, z, lane) == 4 ? 1.0 : 0.0, unused = 0.0;
+        if constexpr (NSQP) unused = seg_max<64>(w0 ? sqp_step_norm(act, has_u, z) : 0.0, lane);      // (NSQP: the second word carries wavefront 0's step norm)
         group_reduce2(kSiteFin, false, s4, unused);
         if (s4 != 0.0) status = 4;
+        if constexpr (NSQP) sqp_nrm = unused;
     }
     tail_full_step(status, z, xi, ui);
+    if constexpr (NSQP) {
+        // either the next iteration -- wavefront 0 publishes the iterate (7 words per stage in XS, which nothing reads between the barrier above and the
+        // predictor of the next iteration), every lane of every wavefront takes its stage's state and input and the successor state the defect needs; x0 and
+        // the goal have just been read again -- or the tail below, once, on the last status
+        sqp_k += 1; sqp_it += it_done;
+        if (!ep_done && status != 4 && sqp_k < p.sqp_max && !(sqp_nrm <= p.sqp_tol)) {
+            if (w0 && own && act) {
+                double *q = XS + 7 * i;
+#pragma unroll
+                for (int c = 0; c < 5; c++) q[c] = xi[c];
+                q[5] = has_u ? ui[0] : 0.0; q[6] = has_u ? ui[1] : 0.0;
+            }
+            group_sync();
+            {
+                const double *q = XS + 7 * (act ? i : 0), *qn = XS + 7 * (has_u ? i + 1 : 0);
+#pragma unroll
+                for (int c = 0; c < 5; c++) { const double a = q[c], b = qn[c]; xi[c] = act ? a : 0.0; xnext[c] = has_u ? b : 0.0; }
+                const double u0 = q[5], u1 = q[6];
+                ui[0] = has_u ? u0 : 0.0; ui[1] = has_u ? u1 : 0.0;
+            }
+            group_sync();
+            goto sqp_again;
+        }
+        it_done = sqp_it;
+    }
     const double u_apply[2] = {lane_value(ui[0], 0), lane_value(ui[1], 0)};   // u* = U[0] (wavefront 0)
     tail_reset_on_fail(p.fused, status, x0v, gl[1], i, N, xi, ui);
     if (w0 && store && own && (status != 4 || (p.fused & (kFuseResetOnFail | kFuseShift)))) tail_store_iterate(p.fused, i, N, act, has_u, xi, ui, Xg, Ug);
@@ -882,6 +916,7 @@ __global__ __launch_bounds__(64 * WideShape<CAP>::W, 1) void rti_wide_kernel(con
         if (p.status_acc) p.status_acc[inst] += tail_status_acc_word(status);
         if (p.status) p.status[inst] = status;
         if (p.iters) p.iters[inst] = it_done;
+        if constexpr (NSQP) { if (p.sqp_iters) p.sqp_iters[inst] = sqp_k; }
     }
     if constexpr (REF) {      // the reference window moves with the plant: the last access to the offset (the prologue and the cost above read it)
         if ((p.fused & kFuseAdvanceRef) && lane == 0 && store && p.ref_off) p.ref_off[inst] += 1;

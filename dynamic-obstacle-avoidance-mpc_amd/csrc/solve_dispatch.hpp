@@ -15,7 +15,7 @@ namespace mpc {
 enum Family { kOneLane = 0, kSplit = 1, kWide = 2 };      // rti_solve_kernel, rti_split_kernel, rti_wide_kernel
 
 // the template arguments of an instantiation in one word.  a, b, c are the family's shape arguments: (G, FACT, -) one lane per stage,
-// (LPS, W2, BLK2) stage-split, (LPS, -, -) multi-wavefront; level: 0 none, 1 REF, 2 REF + IPAR, 3 REF + IPAR + OSEL, 4 REF + IPAR + OSEL + IBND (the kernels' static_asserts nest them so)
+// (LPS, W2, BLK2) stage-split, (LPS, -, -) multi-wavefront; level: 0 none, 1 REF, 2 REF + IPAR, 3 REF + IPAR + OSEL, 4 REF + IPAR + OSEL + IBND, 5 REF + IPAR + OSEL + IBND + NSQP (the kernels' static_asserts nest them so)
 constexpr uint32_t solve_key(int family, int cap, int a, int b, int c, bool masked, int level)
 {
     if (family > 3 || cap > 63 || a > 127 || b > 3 || c > 1 || level > 7) throw "solve_key: a field does not fit";      // (in the table: a compile error)
@@ -41,14 +41,14 @@ constexpr size_t one_lane_lds(int no, int G, int fact, int N, bool lookahead)
 template <int NO, int G, int FACT, bool MASKED, int L>
 constexpr KernelRow one_lane()
 {
-    return {solve_key(kOneLane, NO, G, FACT, 0, MASKED, L), 64, &rti_solve_kernel<NO, G, FACT, MASKED, (L >= 1), (L >= 2), (L >= 3), (L >= 4)>,
+    return {solve_key(kOneLane, NO, G, FACT, 0, MASKED, L), 64, &rti_solve_kernel<NO, G, FACT, MASKED, (L >= 1), (L >= 2), (L >= 3), (L >= 4), (L >= 5)>,
             [](int N, bool lookahead) { return one_lane_lds(NO, G, FACT, N, lookahead); }};
 }
 
 template <int NO, int LPS, bool W2, bool MASKED, bool BLK2, int L>
 constexpr KernelRow split()
 {
-    return {solve_key(kSplit, NO, LPS, W2, BLK2, MASKED, L), 64, &rti_split_kernel<NO, LPS, W2, MASKED, BLK2, (L >= 1), (L >= 2), (L >= 3), (L >= 4)>,
+    return {solve_key(kSplit, NO, LPS, W2, BLK2, MASKED, L), 64, &rti_split_kernel<NO, LPS, W2, MASKED, BLK2, (L >= 1), (L >= 2), (L >= 3), (L >= 4), (L >= 5)>,
             [](int N, bool lookahead) { return (size_t)SplitLds<LPS, NO, W2, BLK2>::total(N, lookahead) * sizeof(double); }};
 }
 
@@ -56,7 +56,7 @@ constexpr KernelRow split()
 template <int CAP, bool MASKED, int L>
 constexpr KernelRow wide()
 {
-    return {solve_key(kWide, CAP, 2, 0, 0, MASKED, L), 64 * WideShape<CAP>::W, &rti_wide_kernel<CAP, 2, MASKED, (L >= 1), (L >= 2), (L >= 3), (L >= 4)>,
+    return {solve_key(kWide, CAP, 2, 0, 0, MASKED, L), 64 * WideShape<CAP>::W, &rti_wide_kernel<CAP, 2, MASKED, (L >= 1), (L >= 2), (L >= 3), (L >= 4), (L >= 5)>,
             [](int N, bool lookahead) { return (size_t)WideLds<CAP>::total(N, lookahead) * sizeof(double); }};
 }
 
@@ -69,7 +69,7 @@ struct SolvePlan {
     int lps;                  // stage-split and multi-wavefront: lanes per stage
     bool w2, blk2;            // stage-split: two wavefronts per SIMD, block-2 recursions
     bool masked;              // run-time obstacle count
-    int level;                // 0 none, 1 REF, 2 REF + IPAR, 3 REF + IPAR + OSEL, 4 REF + IPAR + OSEL + IBND
+    int level;                // 0 none, 1 REF, 2 REF + IPAR, 3 REF + IPAR + OSEL, 4 REF + IPAR + OSEL + IBND, 5 REF + IPAR + OSEL + IBND + NSQP
     const KernelRow *row;
     unsigned grid, block;
     size_t lds;
@@ -96,6 +96,7 @@ constexpr KernelRow kSolveKernels[] = {
     one_lane<3, 64, 3, true, 2>(), one_lane<5, 64, 3, true, 2>(), one_lane<10, 64, 3, true, 2>(),
     one_lane<3, 64, 3, true, 3>(), one_lane<5, 64, 3, true, 3>(), one_lane<10, 64, 3, true, 3>(),
     one_lane<3, 64, 3, true, 4>(), one_lane<5, 64, 3, true, 4>(), one_lane<10, 64, 3, true, 4>(),
+    one_lane<3, 64, 3, true, 5>(), one_lane<5, 64, 3, true, 5>(), one_lane<10, 64, 3, true, 5>(),
     // stage-split (LPS lanes per stage; W2: two wavefronts per SIMD; BLK2: block-2 recursions, an evidence path without feature levels); the obstacle mask
     // (level 3) is a run-time row count by nature, and the instance bounds (level 4) are built on it
     split<3, 2, false, false, false, 0>(), split<5, 2, false, false, false, 0>(), split<10, 2, false, false, false, 0>(),
@@ -122,6 +123,9 @@ constexpr KernelRow kSolveKernels[] = {
     split<3, 3, false, true, false, 3>(), split<5, 3, false, true, false, 3>(), split<10, 3, false, true, false, 3>(),
     split<3, 2, false, true, false, 4>(), split<5, 2, false, true, false, 4>(), split<10, 2, false, true, false, 4>(),
     split<3, 3, false, true, false, 4>(), split<5, 3, false, true, false, 4>(), split<10, 3, false, true, false, 4>(),
+    // ... and the SQP loop (level 5) on them
+    split<3, 2, false, true, false, 5>(), split<5, 2, false, true, false, 5>(), split<10, 2, false, true, false, 5>(),
+    split<3, 3, false, true, false, 5>(), split<5, 3, false, true, false, 5>(), split<10, 3, false, true, false, 5>(),
     // multi-wavefront, 11 .. 32 obstacles
     wide<20, false, 0>(), wide<32, false, 0>(),
     wide<20, true, 0>(), wide<32, true, 0>(),
@@ -131,6 +135,7 @@ constexpr KernelRow kSolveKernels[] = {
     wide<20, true, 2>(), wide<32, true, 2>(),
     wide<20, true, 3>(), wide<32, true, 3>(),
     wide<20, true, 4>(), wide<32, true, 4>(),
+    wide<20, true, 5>(), wide<32, true, 5>(),
 };
 
 constexpr int kSolveKernelCount = sizeof(kSolveKernels) / sizeof(kSolveKernels[0]);
@@ -154,7 +159,7 @@ inline const KernelRow *find_solve_kernel(uint32_t key)
 // the instantiation as rocprofv3 prints it (without the namespace): the family's own template arguments, then one `, true` per feature level
 inline void format_kernel_name(const SolvePlan &q, char *buf, size_t len)
 {
-    const char *tf[2] = {"false", "true"}, *level[5] = {"", ", true", ", true, true", ", true, true, true", ", true, true, true, true"};
+    const char *tf[2] = {"false", "true"}, *level[6] = {"", ", true", ", true, true", ", true, true, true", ", true, true, true, true", ", true, true, true, true, true"};
     if (q.family == kWide) snprintf(buf, len, "rti_wide_kernel<%d, %d, %s%s>", q.cap, q.lps, tf[q.masked], level[q.level]);
     else if (q.family == kSplit) snprintf(buf, len, "rti_split_kernel<%d, %d, %s, %s, %s%s>", q.cap, q.lps, tf[q.w2], tf[q.masked], tf[q.blk2], level[q.level]);
     else snprintf(buf, len, "rti_solve_kernel<%d, %d, %d, %s%s>", q.cap, q.G, q.fact, tf[q.masked], level[q.level]);

@@ -21,6 +21,7 @@ STEP_SHIFT, STEP_PLANT, STEP_OBSTACLES, STEP_RESET_ON_FAIL, STEP_ALIAS_BUG, STEP
 STEP_ADVANCE_REF = 128
 STEP_MARGIN_ALL = 256
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
+MAX_SQP_ITER = 100       # MPC_MAX_SQP_ITER
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
 
 _d = C.c_double
@@ -73,6 +74,8 @@ SYMBOLS = {
     "mpc_set_obstacle_mask_dev": (C.c_int, [_vp, _vp]),
     "mpc_set_instance_bounds": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_set_instance_bounds_dev": (C.c_int, [_vp, _vp]),
+    "mpc_set_sqp": (C.c_int, [_vp, C.c_int, _d]),
+    "mpc_set_sqp_iters_out_dev": (C.c_int, [_vp, _vp]),
     "mpc_plant_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "mpc_predict": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "mpc_solve_dev": (C.c_int, [_vp, C.c_int] + [_vp] * 10),

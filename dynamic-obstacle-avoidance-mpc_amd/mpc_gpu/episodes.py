@@ -18,7 +18,7 @@ from .solver import BatchedMpc
 
 def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, init_guess_when_error=True,
                  bug_compat_alias=True, seed=0, device=0, solver=None, n_obst=5, first_seed=0, record=False, noise=None,
-                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, active=None, margin_all=False, bounds=None, **cfg):
+                 interpolate_init=False, status_log=False, compact_from=4096, r_safe=None, r_hit=None, active=None, margin_all=False, bounds=None, sqp=None, **cfg):
     """x0 (B,5), goal (B,2), obst (B,n_obst,4) -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): instance s then starts
     from the reference generator's draw for np.random.seed(first_seed + s), produced on the device (experiments.py:26-29).
     record=True also returns simX (steps+1,B,5), obst_traj (steps+1,B,n_obst,4) and pred (steps,B,N+1,5): what the reference keeps
@@ -45,6 +45,8 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     not compacted.
     bounds: optional dict(bx_lo=, bx_hi=, bu_lo=, bu_hi=) of per-instance box bounds, (B, 4) / (B, 2) or one row for all (BatchedMpc.set_instance_bounds):
     episode b is solved inside its own actuator and speed limits.  Episodes with bounds of their own are not compacted.
+    sqp: optional (max_iter, step_tol) (BatchedMpc.set_sqp): every control step runs up to max_iter SQP iterations in its one launch.  Compaction stays on:
+    the setting is per handle, not per episode.
     Returns dict(table (B,6), x_last (B,5), steps_run, solves)."""
     import torch
     x0 = np.ascontiguousarray(x0, dtype=np.float64); B = x0.shape[0]
@@ -74,6 +76,9 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     own_bounds = bounds is not None
     if own_bounds:
         m.set_instance_bounds(**bounds)
+    own_sqp = sqp is not None
+    if own_sqp:
+        m.set_sqp(*sqp)
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
         t = lambda a: torch.from_numpy(a.copy()).to(dev)
@@ -186,6 +191,8 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
             m.set_obstacle_mask(None)
         if own_bounds:
             m.set_instance_bounds()
+        if own_sqp:
+            m.set_sqp()
     return dict(table=table, x_last=xl, steps_run=k, solves=int(steps.sum().item()) + int((fl_h & 1).sum()), **extra)
 
 

@@ -121,6 +121,16 @@ class PipelinedMpc:
         for lo, hi, m, _ in self.parts:
             m.set_instance_bounds_dev(self._sl(table, lo, hi))
 
+    def set_sqp(self, max_iter=1, step_tol=0.0):
+        """several SQP iterations per launch (BatchedMpc.set_sqp) on every sub-handle; max_iter = 1 switches the feature off"""
+        for _, _, m, _ in self.parts:
+            m.set_sqp(max_iter, step_tol)
+
+    def set_sqp_iters_out(self, out=None):
+        """ONE int32 device tensor (max_batch,) for the SQP iterations each instance ran: every sub-handle gets its contiguous slice; None: off"""
+        for lo, hi, m, _ in self.parts:
+            m.set_sqp_iters_out(self._sl(out, lo, hi))
+
     # ------------------------------------------------------------------ the cost exchange lives on the first sub-batch's handle (include/mpc_gpu.h mpc_comm_*)
     def comm_init(self, rank, world, unique_id):
         self.parts[0][2].comm_init(rank, world, unique_id)

@@ -94,6 +94,7 @@ class BatchedMpc:
         self.max_batch = int(max_batch)
         self.device = int(device)
         self._h = C.c_void_p()
+        self._sqp_on, self._sqp_out, self._sqp_own = False, None, None      # set_sqp / set_sqp_iters_out
         _lib.check(_lib.lib().mpc_create2(C.byref(self.cfg), self.device, self.max_batch, C.byref(self._h)))
         if BatchedMpc.default_lanes_per_stage:
             _lib.check(_lib.lib().mpc_set_lanes_per_stage(self._h, int(BatchedMpc.default_lanes_per_stage)))
@@ -156,7 +157,7 @@ class BatchedMpc:
     def solve(self, x0, obstacles, goal):
         """One RTI step for a batch.  `obstacles` is either the explicit parameter tensor P (B,N+1,n_obst,2)
         (reference API, parameterize_model) or obstacle states (B,n_obst,4) = (x,y,vx,vy) whose look-ahead is
-        computed on the device.  Returns dict(u0, cost, status, iters)."""
+        computed on the device.  Returns dict(u0, cost, status, iters); with set_sqp on also sqp_iters, the SQP iterations each instance ran."""
         x0 = _f64(np.atleast_2d(x0)); B = x0.shape[0]
         goal = _f64(np.atleast_2d(goal), (B, 2))
         obstacles = _f64(obstacles)
@@ -168,8 +169,33 @@ class BatchedMpc:
             fn = _lib.lib().mpc_solve_obst
         else:
             raise ValueError(f"obstacles must be (B,{self.N + 1},{self.n_obst},2) or (B,{self.n_obst},4), got {obstacles.shape}")
+        if self._sqp_on and self._sqp_out is None:      # words of the handle's own, so that the count can be returned
+            import torch
+            self._sqp_own = torch.zeros(self.max_batch, dtype=torch.int32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(self.device)
+            self.set_sqp_iters_out(self._sqp_own)
         _lib.check(fn(self._h, B, _ptr(x0), _ptr(obstacles), _ptr(goal), _ptr(u0), _ptr(cost), _ptr(status), _ptr(iters)))
-        return dict(u0=u0, cost=cost, status=status, iters=iters)
+        res = dict(u0=u0, cost=cost, status=status, iters=iters)
+        if self._sqp_on:
+            res["sqp_iters"] = self._sqp_out[:B].cpu().numpy().astype(np.int32)
+        return res
+
+    def set_sqp(self, max_iter=1, step_tol=0.0):
+        """Several SQP iterations per solve launch (include/mpc_gpu.h mpc_set_sqp; acados' nlp_solver_type 'SQP' with nlp_solver_max_iter): every following
+        solve, solve_dev and closed_loop_step_dev runs up to max_iter (2 .. 100) RTI iterations per instance on the launch's inputs, and an instance stops
+        behind the iteration whose applied step has max-norm <= step_tol (0: never, inf: behind the first) or whose status is 4.  max_iter = 1: off."""
+        _lib.check(_lib.lib().mpc_set_sqp(self._h, int(max_iter), float(step_tol)))
+        self._sqp_on = int(max_iter) > 1
+
+    def set_sqp_iters_out(self, out=None):
+        """a contiguous int32 device tensor (max_batch,) that receives the SQP iterations each instance ran at every following solve (the word of an
+        idle instance of the fused step is not written); None: off"""
+        if out is not None and (tuple(out.shape) != (self.max_batch,) or str(out.dtype) != "torch.int32" or not out.is_contiguous()):
+            raise ValueError(f"the SQP iteration counts need a contiguous int32 device tensor ({self.max_batch},)")
+        _lib.check(_lib.lib().mpc_set_sqp_iters_out_dev(self._h, _ptr(out)))
+        self._sqp_out = out
+        if out is not self._sqp_own:
+            self._sqp_own = None
 
     def set_slack_schedule(self, alpha):
         """parameterize_slack(), robot_ocp_problem.py:145-152: explicit zl_i = Zl_i = alpha[b, i] for the following solves

@@ -227,6 +227,29 @@ int mpc_set_obstacle_mask_dev(mpc_handle *h, const uint32_t *d_mask);
 int mpc_set_instance_bounds(mpc_handle *h, int batch, const double *bx_lo, const double *bx_hi, const double *bu_lo, const double *bu_hi);
 int mpc_set_instance_bounds_dev(mpc_handle *h, const double *d_bounds);
 
+/* Several SQP iterations per solve launch: acados' nlp_solver_type = 'SQP' with nlp_solver_max_iter = max_iter in place of the 'SQP_RTI' the reference
+ * configures (robot_ocp_problem.py:126-132), with the plain full step of the real-time iteration (no globalisation).  max_iter = 1 switches the feature
+ * off: the handle runs the kernels and gives the results it had.  max_iter in 2 .. MPC_MAX_SQP_ITER switches it on for every following mpc_solve,
+ * mpc_solve_obst, mpc_solve_dev and mpc_closed_loop_step_dev.  MPC_ERR_ARG (naming the field) for max_iter outside 1 .. MPC_MAX_SQP_ITER and for a
+ * step_tol that is NaN or negative; +inf is valid.
+ * One launch then runs, per instance b and for k = 1, 2, ..., one RTI iteration (linearise, QP, interior point from its cold start, full step) on b's
+ * current iterate.  The inputs are those of the launch and the same for every k: x0, P or the look-ahead computed once, goal, slack schedule, reference,
+ * instance parameters, mask, bounds.  The loop of instance b ends behind iteration k when its status is 4, or k == max_iter, or the step it applied has
+ * max-norm <= step_tol (over every entry of dX, stages 0 .. N, and dU; unscaled, in double, the step itself).  Reported: status = that of the last
+ * iteration run; iters = the sum of the interior-point iterations of all iterations run (the iters accumulator gets the same sum, the status accumulator
+ * one word for the final status); cost and u* = U[0] at the final iterate; sqp_iters[b] = k.  The rest of the fused step -- reset on fail, plant,
+ * obstacles, bookkeeping, shift, MPC_STEP_ADVANCE_REF -- happens once, behind the loop, on the final status.  A status 4 at iteration k leaves the iterate
+ * of iteration k - 1.  In short: the result is that of the same sequence of single-iteration launches stopped by the same rule.  An idle instance
+ * (episode over) runs nothing and its sqp_iters word is not written; mpc_debug_trace records the last iteration run -- every iteration writes its rows from row 0, `iters` is the sum over the
+ * iterations and not the number of valid rows, and rows behind the last iteration's own may be left from an earlier, longer one: trace single
+ * iterations (max_iter = 2, step_tol = +inf) where the rows of one are to be read; mpc_linearize_dev is unaffected.
+ * Runs on feature-level kernels of their own (the instantiations of mpc_set_instance_bounds with one more flag): features that are not set read the
+ * handle's own values; mappings and refusals are those of mpc_set_instance_bounds (above).
+ * mpc_set_sqp_iters_out_dev: int32[max_batch] device words that receive k per instance at every following solve, NULL = off. */
+#define MPC_MAX_SQP_ITER 100   /* acados' default nlp_solver_max_iter */
+int mpc_set_sqp(mpc_handle *h, int max_iter, double step_tol);
+int mpc_set_sqp_iters_out_dev(mpc_handle *h, int32_t *d_sqp_iters);
+
 /* Plant integrator, ocp_integrator.set/solve/get, robot_ocp_problem.py:207-212 (same IRK as the OCP) */
 int mpc_plant_step(mpc_handle *h, int batch, const double *x, const double *u, double *x_next);
 /* Obstacle look-ahead only: obst[B][n_obst][4] -> P[B][N+1][n_obst][2] (visualization.py:62-79) */
