@@ -1009,6 +1009,26 @@ void orc_rti_solve_batch(const orc_config *c, int batch, const double *x0, const
     (void)nthreads;
 }
 
+/* the same with a slack schedule per instance: alpha[batch][N+1] (orc_rti_solve_alpha instance by instance) */
+void orc_rti_solve_batch_alpha(const orc_config *c, int batch, const double *x0, const double *P, const double *goal, const double *alpha,
+                               double *X, double *U, double *u0, double *cost, int *status, int *iters, int nthreads)
+{
+    int N = c->N, no = c->n_obst;
+    size_t sP = (size_t)(N + 1) * no * 2, sX = (size_t)(N + 1) * 5, sU = (size_t)N * 2;
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+    for (int b = 0; b < batch; b++) {
+        int it = 0;
+        int st = orc_rti_solve_alpha(c, x0 + 5 * (size_t)b, P + sP * b, goal + 2 * (size_t)b, alpha + (size_t)(N + 1) * b, X + sX * b, U + sU * b,
+                                     u0 ? u0 + 2 * (size_t)b : NULL, cost ? cost + b : NULL, &it, NULL);
+        if (status) status[b] = st;
+        if (iters) iters[b] = it;
+    }
+    (void)nthreads;
+}
+
 /* bench.py's cpu_baseline only: what surrounds the solve in a closed loop, for a whole batch in one call (the ~6 Python -> C calls per scenario and control step
  * they replace took ten times as long as the timed solves themselves).  orc_predict_params_batch: P[b] from obst[b]; orc_advance_batch: x[b] <- F(x[b], u0[b])
  * (robot_ocp_problem.py:207-212), obstacles one noise-free step (visualization.py:20-23), warm-start shift (:253-258). */
@@ -1029,13 +1049,13 @@ void orc_advance_batch(const orc_config *c, int batch, double *x, const double *
     }
 }
 
-int orc_export_qp(const orc_config *c, const double *x0, const double *P, const double *goal,
-                  const double *X, const double *U,
-                  double *H, double *g, double *Aeq, double *beq, double *lb, double *ub,
-                  double *Cs, double *hs, double *zs, double *Zs)
+static int export_qp(const orc_config *c, const double *x0, const double *P, const double *goal, const double *alpha,
+                     const double *X, const double *U,
+                     double *H, double *g, double *Aeq, double *beq, double *lb, double *ub,
+                     double *Cs, double *hs, double *zs, double *Zs)
 {
     int N = c->N; int nv = 7 * N;
-    qp_t Q; build_qp(c, x0, P, goal, X, U, &Q, NULL);
+    qp_t Q; build_qp(c, x0, P, goal, X, U, &Q, alpha);
     /* variable map: du_i -> 7i + {0,1} ; dx_i (i>=1) -> 7(i-1) + 2 + k */
     memset(H, 0, sizeof(double) * nv * nv); memset(g, 0, sizeof(double) * nv);
     memset(Aeq, 0, sizeof(double) * 5 * N * nv); memset(beq, 0, sizeof(double) * 5 * N);
@@ -1074,4 +1094,20 @@ int orc_export_qp(const orc_config *c, const double *x0, const double *P, const 
     }
     qp_free(&Q);
     return ns;
+}
+
+int orc_export_qp(const orc_config *c, const double *x0, const double *P, const double *goal,
+                  const double *X, const double *U,
+                  double *H, double *g, double *Aeq, double *beq, double *lb, double *ub,
+                  double *Cs, double *hs, double *zs, double *Zs)
+{
+    return export_qp(c, x0, P, goal, NULL, X, U, H, g, Aeq, beq, lb, ub, Cs, hs, zs, Zs);
+}
+
+int orc_export_qp_alpha(const orc_config *c, const double *x0, const double *P, const double *goal, const double *alpha,
+                        const double *X, const double *U,
+                        double *H, double *g, double *Aeq, double *beq, double *lb, double *ub,
+                        double *Cs, double *hs, double *zs, double *Zs)
+{
+    return export_qp(c, x0, P, goal, alpha, X, U, H, g, Aeq, beq, lb, ub, Cs, hs, zs, Zs);
 }

@@ -136,6 +136,10 @@ void orc_rti_solve_batch(const orc_config *c, int batch, const double *x0, const
                          double *X, double *U, double *u0, double *cost, int *status, int *iters,
                          int nthreads);
 
+/* ... with a slack schedule per instance, alpha[batch][N+1] (orc_rti_solve_alpha instance by instance) */
+void orc_rti_solve_batch_alpha(const orc_config *c, int batch, const double *x0, const double *P, const double *goal, const double *alpha,
+                               double *X, double *U, double *u0, double *cost, int *status, int *iters, int nthreads);
+
 /* bench.py's cpu_baseline: the untimed surroundings of the solve for a whole batch per call (look-ahead; plant step + obstacle step + warm-start shift, in place) */
 void orc_predict_params_batch(const orc_config *c, int batch, const double *obst, double *P);
 void orc_advance_batch(const orc_config *c, int batch, double *x, const double *u0, double *obst, double *X, double *U);
@@ -150,6 +154,12 @@ int orc_export_qp(const orc_config *c, const double *x0, const double *P, const 
                   const double *X, const double *U,
                   double *H, double *g, double *Aeq, double *beq, double *lb, double *ub,
                   double *Cs, double *hs, double *zs, double *Zs);
+
+/* the QP of orc_rti_solve_alpha: the same with explicit slack weights alpha[N+1] (a stage with weight 0 has no soft rows); alpha = NULL is orc_export_qp */
+int orc_export_qp_alpha(const orc_config *c, const double *x0, const double *P, const double *goal, const double *alpha,
+                        const double *X, const double *U,
+                        double *H, double *g, double *Aeq, double *beq, double *lb, double *ub,
+                        double *Cs, double *hs, double *zs, double *Zs);
 
 /* debugging aid: number of pairs of the calling thread's last solve that ended with BOTH t and lam at the floor ("dead": complementary whatever the row does) */
 int orc_last_dead_pairs(void);

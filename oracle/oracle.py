@@ -97,6 +97,9 @@ def lib():
         L.orc_rti_solve_batch.argtypes = [cp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int]
         L.orc_export_qp.argtypes = [cp] + [_dp] * 15
         L.orc_export_qp.restype = C.c_int
+        L.orc_export_qp_alpha.argtypes = [cp, _dp, _dp, _dp, C.c_void_p] + [_dp] * 12
+        L.orc_export_qp_alpha.restype = C.c_int
+        L.orc_rti_solve_batch_alpha.argtypes = [cp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int]
     return _LIB
 
 
@@ -231,12 +234,19 @@ def obstacle_radii(r):
         lib().orc_set_obstacle_radii(0, r)
 
 
-def rti_solve_batch(cfg, x0, P, goal, X, U, nthreads=0):
+def rti_solve_batch(cfg, x0, P, goal, X, U, nthreads=0, alpha=None):
+    """alpha: explicit slack weights per instance (B, N+1) (rti_solve(..., alpha=alpha[b]) instance by instance); default the reference's schedule"""
     B = x0.shape[0]
     X, U = _a(X).copy(), _a(U).copy()
     u0, cst = np.zeros((B, 2)), np.zeros(B)
     st, it = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    lib().orc_rti_solve_batch(C.byref(cfg), B, _a(x0), _a(P), _a(goal), X, U, u0, cst, st, it, nthreads)
+    if alpha is None:
+        lib().orc_rti_solve_batch(C.byref(cfg), B, _a(x0), _a(P), _a(goal), X, U, u0, cst, st, it, nthreads)
+    else:
+        alpha = _a(alpha)
+        if alpha.shape != (B, cfg.N + 1):
+            raise ValueError(f"alpha must be ({B}, {cfg.N + 1}), got {alpha.shape}")
+        lib().orc_rti_solve_batch_alpha(C.byref(cfg), B, _a(x0), _a(P), _a(goal), alpha, X, U, u0, cst, st, it, nthreads)
     return dict(X=X, U=U, u0=u0, cost=cst, status=st, iters=it)
 
 
@@ -255,12 +265,19 @@ def advance_batch(cfg, x, u0, obst, X, U):
     lib().orc_advance_batch(C.byref(cfg), x.shape[0], x, _a(u0), obst, X, U)
 
 
-def export_qp(cfg, x0, P, goal, X, U):
+def export_qp(cfg, x0, P, goal, X, U, alpha=None):
+    """the QP of one RTI step, dense (oracle/mpc_oracle.h orc_export_qp); alpha: explicit slack weights (N+1,), as rti_solve takes them"""
     N, no = cfg.N, cfg.n_obst
     nv, nsm = 7 * N, max(1, N * no)
     H, g = np.zeros((nv, nv)), np.zeros(nv)
     Aeq, beq = np.zeros((5 * N, nv)), np.zeros(5 * N)
     lb, ub = np.zeros(nv), np.zeros(nv)
     Cs, hs, zs, Zs = np.zeros((nsm, nv)), np.zeros(nsm), np.zeros(nsm), np.zeros(nsm)
-    ns = lib().orc_export_qp(C.byref(cfg), _a(x0), _a(P), _a(goal), _a(X), _a(U), H, g, Aeq, beq, lb, ub, Cs, hs, zs, Zs)
+    if alpha is None:
+        ns = lib().orc_export_qp(C.byref(cfg), _a(x0), _a(P), _a(goal), _a(X), _a(U), H, g, Aeq, beq, lb, ub, Cs, hs, zs, Zs)
+    else:
+        al = _a(alpha)
+        if al.shape != (N + 1,):
+            raise ValueError(f"alpha must be ({N + 1},), got {al.shape}")
+        ns = lib().orc_export_qp_alpha(C.byref(cfg), _a(x0), _a(P), _a(goal), al.ctypes.data, _a(X), _a(U), H, g, Aeq, beq, lb, ub, Cs, hs, zs, Zs)
     return dict(H=H, g=g, Aeq=Aeq, beq=beq, lb=lb, ub=ub, Cs=Cs[:ns], hs=hs[:ns], zs=zs[:ns], Zs=Zs[:ns])

@@ -97,9 +97,9 @@ def fused_step_is_the_separate_calls(mpc_gpu, N, no, x0, goal, obst, noise, conf
     return fused
 
 
-def oracle_reference(orc, cfg, x0, P, goal, X, U):
-    """Run the oracle on a batch (OpenMP) and return its outputs."""
-    return orc.rti_solve_batch(cfg, x0, P, goal, X, U, nthreads=0)
+def oracle_reference(orc, cfg, x0, P, goal, X, U, alpha=None):
+    """Run the oracle on a batch (OpenMP) and return its outputs.  alpha: explicit slack weights per instance (B, N+1)."""
+    return orc.rti_solve_batch(cfg, x0, P, goal, X, U, nthreads=0, alpha=alpha)
 
 
 def oracle_P(orc, cfg, obst):
@@ -111,11 +111,12 @@ def oracle_guess(orc, cfg, x0):
     return np.stack(Xs), np.stack(Us)
 
 
-def qp_merit(orc, cfg, x0, P, goal, X, U, Xn, Un):
+def qp_merit(orc, cfg, x0, P, goal, X, U, Xn, Un, alpha=None):
     """Solver-independent judgement of one RTI step (X, U) -> (Xn, Un): the step as a point of the QP the oracle assembles from
     (x0, P, goal, X, U) (orc_export_qp; slacks eliminated in closed form, s = max(0, -(Cs v + hs))).
+    alpha: the instance's explicit slack weights (N+1,), None for the built-in schedule.
     Returns (objective, max equality residual, max bound violation)."""
-    q = orc.export_qp(cfg, x0, P, goal, X, U)
+    q = orc.export_qp(cfg, x0, P, goal, X, U, alpha=alpha)
     N = cfg.N
     v = np.zeros(7 * N)
     for i in range(N):
@@ -151,11 +152,12 @@ EXACT_FACTOR = 10.0          # reported, not asserted per instance (see above)
 EXACT_CAP = 3e-6
 
 
-def adjudicate(orc, cfg, x0, P, goal, X0, U0, Xg, Ug, Xo, Uo, factor=EXACT_FACTOR, cap=EXACT_CAP):
-    """One instance, one RTI step from (X0, U0): GPU step (Xg, Ug) and oracle step (Xo, Uo) against the exact solution of the exported QP.
+def adjudicate(orc, cfg, x0, P, goal, X0, U0, Xg, Ug, Xo, Uo, factor=EXACT_FACTOR, cap=EXACT_CAP, alpha=None):
+    """One instance, one RTI step from (X0, U0): GPU step (Xg, Ug) and oracle step (Xo, Uo) against the exact solution of the exported QP
+    (alpha: the instance's explicit slack weights (N+1,), with which both sides solved; None for the built-in schedule).
     Returns dict(kind 'exact' | 'merit', passed, d_gpu, d_oracle, ...); the caller asserts."""
     N = cfg.N
-    q = orc.export_qp(cfg, x0, P, goal, X0, U0)
+    q = orc.export_qp(cfg, x0, P, goal, X0, U0, alpha=alpha)
     vg, vo = step_vector(N, X0, U0, Xg, Ug), step_vector(N, X0, U0, Xo, Uo)
     vex, ok, info = exact_qp(q, vo)
     if not ok:
@@ -165,8 +167,8 @@ def adjudicate(orc, cfg, x0, P, goal, X0, U0, Xg, Ug, Xo, Uo, factor=EXACT_FACTO
         dg, do = float(np.abs(vg - vex).max()), float(np.abs(vo - vex).max())
         return dict(kind="exact", passed=bool(dg <= cap), d_gpu=dg, d_oracle=do, d_gpu_oracle=d_go, ratio=dg / max(do, 1e-9), within_factor=bool(dg <= max(factor * do, 1e-6)),
                     active=info.get("active"), lam_min=info.get("lam_min"))
-    fg, eqg, bg = qp_merit(orc, cfg, x0, P, goal, X0, U0, Xg, Ug)
-    fo, _, _ = qp_merit(orc, cfg, x0, P, goal, X0, U0, Xo, Uo)
+    fg, eqg, bg = qp_merit(orc, cfg, x0, P, goal, X0, U0, Xg, Ug, alpha=alpha)
+    fo, _, _ = qp_merit(orc, cfg, x0, P, goal, X0, U0, Xo, Uo, alpha=alpha)
     return dict(kind="merit", passed=bool(eqg <= 1e-7 and bg <= 1e-7 and fg <= fo + max(1e-9 * abs(fo), 1e-6) and d_go <= cap), d_gpu=None, d_oracle=None,
                 d_gpu_oracle=d_go, f_gpu=fg, f_oracle=fo, eq=eqg, box=bg, why=info.get("why"))
 
@@ -201,6 +203,8 @@ def judge_against_oracle(orc, cfg, x0, P, goal, X0, U0, g, Xg, Ug, o, tol_x=1e-6
       * a converged instance (status 0 on both sides) is within the tolerance of the oracle -- or it is ADJUDICATED against the exact solution of the QP
         (adjudicate(): the GPU's distance from it below EXACT_CAP = 3e-6; the ratio to the oracle's distance is reported, not asserted -- which side holds the
         larger share of a float64-floor remainder is rounding), and the number of instances that need this is bounded (allowed_adjudications(), or max_adjudicated);
+        with an explicit slack schedule (alpha (B, N+1): what the GPU was given and the oracle's solves `o` were run with) the QP is the one exported with the
+        instance's own row (oracle.export_qp(alpha=));
       * the iteration counts are equal, or they differ by at most 2 AND the oracle's own record shows the end-game: where the earlier side stopped, the
         oracle's largest complementarity product was already below 1e-4 (the last, superlinear iterations: from there ONE step takes it to ~1e-10, and a
         rounding difference decides whether that step lands under the tolerance or just above it).
@@ -223,8 +227,7 @@ def judge_against_oracle(orc, cfg, x0, P, goal, X0, U0, g, Xg, Ug, o, tol_x=1e-6
         dx, du = np.abs(Xg[b] - o["X"][b]).max(), np.abs(Ug[b] - o["U"][b]).max()
         n["worst_d_gpu_oracle"] = max(n["worst_d_gpu_oracle"], float(max(dx, du)))
         if dx > tol_x or du > tol_u:
-            assert alpha is None, f"instance {b}: |dX| {dx:.2e} beyond the tolerance with an explicit slack schedule (no QP export for it)"
-            a = adjudicate(orc, cfg, x0[b], P[b], goal[b], X0[b], U0[b], Xg[b], Ug[b], o["X"][b], o["U"][b])
+            a = adjudicate(orc, cfg, x0[b], P[b], goal[b], X0[b], U0[b], Xg[b], Ug[b], o["X"][b], o["U"][b], alpha=None if alpha is None else alpha[b])
             assert a["passed"], f"instance {b}: |GPU - oracle| {max(dx, du):.2e}; adjudication {a}"
             n["judged_by_qp"] += 1
             n["judged_exact" if a["kind"] == "exact" else "judged_merit"] += 1

@@ -4,6 +4,8 @@ rule of include/mpc_gpu.h.  Imports without torch or a GPU; the oracle is passed
 
 The stop rule (one instance): for k = 1, 2, ... solve once from the current iterate; end behind iteration k when its status is 4 (the iterate stays that
 of iteration k - 1), or k == K, or the applied step has max-norm <= step_tol (every entry of dX and dU)."""
+import hashlib
+
 import numpy as np
 
 from feature_kernel_cases import HORIZON
@@ -78,23 +80,30 @@ def step_norm(Xa, Ua, Xb, Ub):
     return float(max(np.abs(Xb - Xa).max(), np.abs(Ub - Ua).max()))
 
 
-def oracle_sequence(orc, c, step_tol=None, max_iter=K):
-    """The reference: per instance the oracle's single solves stopped by the rule above.  Returns dict(X, U, u0, cost, status, iters (the sum), sqp_iters,
+def _digest(a):
+    return None if a is None else hashlib.sha1(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
+
+
+def oracle_sequence(orc, c, step_tol=None, max_iter=K, alpha=None, P=None):
+    """The reference: per instance the oracle's single solves stopped by the rule above.  alpha: an explicit slack schedule (B, N + 1), every solve
+    of instance b run with alpha[b]; P: a look-ahead (B, N + 1, n_obst, 2) in place of the case's own (slack_schedule_cases).
+    Returns dict(X, U, u0, cost, status, iters (the sum), sqp_iters,
     norms (B, max_iter) -- NaN where an iteration did not run or failed --, statuses (B, max_iter) -- -1 where it did not run --, iterates: per
     instance the list of (X, U) in front of every iteration run).  Computed once per (case, step_tol, max_iter) and not to be written to"""
     step_tol = c["step_tol"] if step_tol is None else step_tol
-    key = (c["id"], float(step_tol), int(max_iter))
+    key = (c["id"], float(step_tol), int(max_iter), _digest(alpha), _digest(P))
     if key in _REFERENCE:
         return _REFERENCE[key]
     inp = inputs(orc, c)
     cfg, N = inp["cfg"], inp["N"]
+    P = inp["P"] if P is None else P
     out = dict(X=inp["X0"].copy(), U=inp["U0"].copy(), u0=np.zeros((B, 2)), cost=np.zeros(B), status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32),
                sqp_iters=np.zeros(B, np.int32), norms=np.full((B, max_iter), np.nan), statuses=np.full((B, max_iter), -1, np.int32), iterates=[[] for _ in range(B)])
     for b in range(B):
         X, U = inp["X0"][b].copy(), inp["U0"][b].copy()
         for k in range(1, max_iter + 1):
             out["iterates"][b].append((X.copy(), U.copy()))
-            r = orc.rti_solve(cfg, inp["x0"][b], inp["P"][b], inp["goal"][b], X, U)
+            r = orc.rti_solve(cfg, inp["x0"][b], P[b], inp["goal"][b], X, U, alpha=None if alpha is None else alpha[b])
             out["statuses"][b, k - 1] = r["status"]; out["iters"][b] += r["iters"]; out["sqp_iters"][b] = k
             out["status"][b], out["u0"][b], out["cost"][b] = r["status"], r["u0"], r["cost"]
             if r["status"] == 4:

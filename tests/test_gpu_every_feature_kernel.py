@@ -23,9 +23,10 @@ B = fk.B
 RANDOMNESS, VMAX = 0.1, 2.0      # the obstacle motion's noise scale and speed limit, as the fused step is given them
 
 
-def _launches(mpc_gpu, torch, case, inp, nan_absent_too):
+def _launches(mpc_gpu, torch, case, inp, nan_absent_too, alpha=None):
     """one fused step of the case's kernel on banded arrays -- and, nan_absent_too, the same step again on the same handle with NaN in the absent
-    obstacles' entries and everything else restored; per launch, everything it could have touched comes back as numpy"""
+    obstacles' entries and everything else restored; per launch, everything it could have touched comes back as numpy.  alpha: an explicit slack
+    schedule (B, N + 1), one more banded device array the handle reads in place (set_slack_schedule's device form)"""
     from mpc_gpu import _lib, pack_instance_bounds, pack_obstacle_mask
     N, no, level = inp["N"], inp["no"], inp["level"]
     dev = torch.device("cuda:0")
@@ -57,6 +58,9 @@ def _launches(mpc_gpu, torch, case, inp, nan_absent_too):
         if level >= 4:
             feat["table"] = up(table, bd.f64)
             s.set_instance_bounds_dev(feat["table"])
+        if alpha is not None:
+            feat["alpha"] = up(alpha, bd.f64)
+            s.set_slack_schedule(feat["alpha"])
         torch.cuda.current_stream().synchronize()
         name = s.kernel_name(B)
         assert name == case["name"], (name, case["name"])             # before anything is launched
@@ -68,6 +72,8 @@ def _launches(mpc_gpu, torch, case, inp, nan_absent_too):
             uploaded["mask words"] = (feat["words"], words)
         if level >= 4:
             uploaded["bounds table"] = (feat["table"], table)
+        if alpha is not None:
+            uploaded["slack schedule"] = (feat["alpha"], alpha)
         c = lambda a: a.cpu().numpy().copy()
         fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS | _lib.STEP_RESET_ON_FAIL | _lib.STEP_ADVANCE_REF
         for nan_absent in (False, True) if nan_absent_too else (False,):
@@ -113,8 +119,9 @@ def _placement(inp, r, why):
         if not np.array_equal(r[k][idle], v[idle], equal_nan=(k == "obst")): why.append(f"the idle instance's {k} was written")
 
 
-def _against_oracle(orc, inp, r, why, rep):
-    """the solve, group by group, from the reset guess: the iterate un-shifted (stage 0 is the state the solve started from, u*[0] the applied input)"""
+def _against_oracle(orc, inp, r, why, rep, alpha=None):
+    """the solve, group by group, from the reset guess: the iterate un-shifted (stage 0 is the state the solve started from, u*[0] the applied input).
+    alpha: the explicit slack schedule the launch ran with; a group's instances keep their own rows (an absent obstacle has no row whatever the weight)"""
     N = inp["N"]
     Xn = np.concatenate([inp["x0"][:, None, :], r["X"][:, :N]], axis=1)
     Un = np.concatenate([r["u0"][:, None, :], r["U"][:, :N - 1]], axis=1)
@@ -124,10 +131,11 @@ def _against_oracle(orc, inp, r, why, rep):
         live = inp["ep_flags"][idx] == 0
         idx, Pk = idx[live], np.ascontiguousarray(Pk[live])
         gb = {name: r[name][idx] for name in ("u0", "cost", "status", "iters")}
+        ak = None if alpha is None else np.ascontiguousarray(alpha[idx])
         try:
             with orc.obstacle_radii(radii):      # the oracle's solve, its trace and the exported QP of an adjudication all see the group's radii
-                o = oracle_reference(orc, cfg, inp["x0"][idx], Pk, inp["goal"][idx], r["X0"][idx], r["U0"][idx])
-                n = judge_against_oracle(orc, cfg, inp["x0"][idx], Pk, inp["goal"][idx], r["X0"][idx], r["U0"][idx], gb, Xn[idx], Un[idx], o)
+                o = oracle_reference(orc, cfg, inp["x0"][idx], Pk, inp["goal"][idx], r["X0"][idx], r["U0"][idx], alpha=ak)
+                n = judge_against_oracle(orc, cfg, inp["x0"][idx], Pk, inp["goal"][idx], r["X0"][idx], r["U0"][idx], gb, Xn[idx], Un[idx], o, alpha=ak)
         except AssertionError as e:
             why.append(f"group {k} against the oracle: {str(e)[:400]}")
             continue
@@ -169,20 +177,22 @@ def _bookkeeping(orc, inp, r, why):
     if not np.array_equal(r["steps"], ns): why.append(f"step counters {r['steps'].tolist()} vs {ns.tolist()}")
 
 
-def _body(mg, family, level):
+def _body(mg, family, level, schedule_of=None):
+    """schedule_of(orc, case): (inputs, alpha) -- the case's inputs in the schedule sweep's world and the explicit slack schedule (B, N + 1) layered
+    on top of them (None: the case's own inputs, the built-in schedule)"""
     import torch
     mpc_gpu, orc = mg
     cases = fk.cases_of(family, level)
     bad, ran = [], []
     for case in cases:
-        inp = fk.inputs(orc, case)
+        inp, alpha = (fk.inputs(orc, case), None) if schedule_of is None else schedule_of(orc, case)
         with torch.cuda.stream(torch.cuda.Stream()):      # a stream of its own per kernel
-            r, again = (_launches(mpc_gpu, torch, case, inp, level >= 3) + [None])[:2]
+            r, again = (_launches(mpc_gpu, torch, case, inp, level >= 3, alpha) + [None])[:2]
         ran.append(r["name"])
         why = []
         rep = dict(converged=0, adjudicated=0, status_borderline=0, worst_gpu_oracle=0.0, worst_gpu_exact=0.0)
         _placement(inp, r, why)
-        _against_oracle(orc, inp, r, why, rep)
+        _against_oracle(orc, inp, r, why, rep, alpha)
         _bookkeeping(orc, inp, r, why)
         if again is not None:
             absent = ~inp["mask"]
@@ -202,7 +212,7 @@ def _body(mg, family, level):
                     same = np.array_equal(again[k], r[k])
                 if not same: why.append(f"NaN in the absent obstacles' entries changed {k}")
             if not again["intact"] or again["written"]: why.append(f"second launch: bands {again['intact']}, written {again['written']}")
-        print(f"FEATURE-KERNEL {r['name']} N {case['N']} n_obst {case['no']}: converged {rep['converged']} of {B - 1} worst_gpu_oracle {rep['worst_gpu_oracle']:.3e} "
+        print(f"{'FEATURE-KERNEL' if alpha is None else 'SLACK-SCHEDULE level ' + str(level)} {r['name']} N {case['N']} n_obst {case['no']}: converged {rep['converged']} of {B - 1} worst_gpu_oracle {rep['worst_gpu_oracle']:.3e} "
               f"adjudicated {rep['adjudicated']} worst_gpu_exact {rep['worst_gpu_exact']:.3e} status_borderline {rep['status_borderline']} "
               f"status {r['status'].tolist()} {'FAILED: ' + '; '.join(why) if why else 'ok'}")
         if why:
@@ -215,3 +225,22 @@ def _body(mg, family, level):
 @pytest.mark.parametrize("family", fk.FAMILIES)
 def test_every_feature_instantiation_in_guard_bands_against_the_oracle(mg, family, level):
     on_own_stream(_body, mg, family, level)
+
+
+def _schedule_of(world):
+    def of(orc, case):
+        import slack_schedule_cases as ss
+        prob = ss.feature_problem(orc, case, world)
+        return prob["inp"], prob["alpha"]
+    return of
+
+
+@pytest.mark.parametrize("world", ("crowded", "own"))
+@pytest.mark.parametrize("level", fk.LEVELS)
+@pytest.mark.parametrize("family", fk.FAMILIES)
+def test_every_feature_instantiation_with_an_explicit_slack_schedule(mg, family, level, world):
+    """the same sweep with slack_schedule_cases.schedule layered on top of every case's inputs: rows on the terminal stage,
+    holes inside the horizon, a row per instance -- given as a banded device array, which the launch must leave as it was.  world "own": the case's
+    own inputs as they are; "crowded": their obstacles aimed at the robots (slack_schedule_cases.crowded), where test_slack_schedule_host.py shows
+    that every property of the schedule is felt by three instances or more"""
+    on_own_stream(_body, mg, family, level, _schedule_of(world))

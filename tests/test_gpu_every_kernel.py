@@ -6,42 +6,14 @@ step counter.  Its source is right; in its listing the register allocator re-mat
 became the step counter's.  No parity test saw it (accumulators and episode counters are optional outputs, and the workload kernels were not affected); the
 closed-loop fuzz did.  So: for every instantiation, one fused step with ALL optional outputs wired to distinct guard-banded arrays, the result compared with the
 default mapping's (statuses, iteration counts, flags, step counters exactly; controls, costs, margins to 1e-6), accumulators against what they accumulate, bands intact."""
-import itertools
-
 import numpy as np
 import pytest
 
 from feature_loop import Banded
 from helpers import random_batch
+from kernel_configs import apply, configs as _configs
 
 pytestmark = pytest.mark.gpu
-
-
-def _configs(mpc_gpu):
-    """(N, n_obst, overrides) for every distinct kernel name the dispatcher reports"""
-    seen, out = set(), []
-    for N, no in itertools.product((10, 20, 31, 40), (3, 5, 10, 2, 4, 7)):
-        for lanes, lps, waves, rowpar, mfma, blk2 in itertools.product((0, 16, 21, 32, 64), (0, 1, 2, 3), (0, 1, 2), (1, 0), (0, 1), (0, 1)):
-            if mfma and (lanes != 64 or lps != 1 or not rowpar or blk2 or waves):
-                continue
-            if not rowpar and (lps != 1 or blk2 or waves):
-                continue
-            if blk2 and (lps == 1 or lanes or waves == 2):
-                continue
-            with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=4) as s:
-                try:
-                    s.set_lanes_per_stage(lps); s.set_waves_per_simd(waves)
-                    if lanes:
-                        s.set_lanes_per_instance(lanes)
-                    s.set_row_parallel(bool(rowpar)); s.set_block_riccati(bool(blk2))
-                    if mfma:
-                        s.set_matrix_cores(True)
-                    name = s.kernel_name(4)
-                except mpc_gpu.MpcError:
-                    continue
-            if name not in seen:
-                seen.add(name); out.append((N, no, dict(lanes=lanes, lps=lps, waves=waves, rowpar=rowpar, mfma=mfma, blk2=blk2), name))
-    return out
 
 
 def _one_step(mpc_gpu, torch, N, no, ov, B, x0, goal, obst, noise):
@@ -50,12 +22,7 @@ def _one_step(mpc_gpu, torch, N, no, ov, B, x0, goal, obst, noise):
     with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B) as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
         q = torch.cuda.current_stream().cuda_stream
         if ov is not None:
-            s.set_lanes_per_stage(ov["lps"]); s.set_waves_per_simd(ov["waves"])
-            if ov["lanes"]:
-                s.set_lanes_per_instance(ov["lanes"])
-            s.set_row_parallel(bool(ov["rowpar"])); s.set_block_riccati(bool(ov["blk2"]))
-            if ov["mfma"]:
-                s.set_matrix_cores(True)
+            apply(s, ov)
         name = s.kernel_name(B)
         bd = Banded(torch, dev)
         t = lambda a, mk: mk(*a.shape).copy_(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
