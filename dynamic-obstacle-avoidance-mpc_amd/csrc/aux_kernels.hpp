@@ -362,6 +362,137 @@ __global__ void reset_guess_kernel(int batch, int N, const double *__restrict__ 
     if (i < N) { double *Ui = U + ((size_t)inst * N + i) * 2; Ui[0] = 0.0; Ui[1] = 0.0; }
 }
 
+// EPISODE REFILL (mpc_episode_refill_dev): a sweep over more seeds than there are slots streams the seeds through the slots -- in front of every
+// fused control step, a slot whose episode has ended (ep_flags bit 0: goal reached, robot_ocp_problem.py:247-250; or ep_steps >= max_steps: the budget of
+// experiments.py:20-36) parks its result row under its seed index and starts the next seed that has not been started yet.  Two launches:
+//   refill_decide_kernel, ONE workgroup: reads the finished state of every slot and hands the remaining seed indices to the finished slots in ascending
+//     slot order -- an exclusive scan of the finished flags (wavefront ballot + population count, wave totals through LDS, a running base over chunks of
+//     kRefillThreads slots).  No atomic, nothing that depends on the order workgroups run in: the seed-to-slot schedule is a function of the episode
+//     lengths alone (with three instances per wavefront an episode's rounding depends on its neighbours, so a sweep is reproducible only if this is).
+//     It writes assign[slot] and the cursor and NOTHING the decision reads;
+//   refill_apply_kernel, one thread per slot: parks, reseeds (and draws the step's noise).  Every word it writes belongs to its own slot or its own seed.
+// assign[slot]: kRefillKeep the episode runs on; kRefillDrain it has ended and no seed is left; k >= 0 it has ended and seed index k starts here.
+constexpr int kRefillThreads = 256, kRefillKeep = -2, kRefillDrain = -1;
+enum { kRefillAliasBug = 1, kRefillInterpGuess = 2, kRefillDrawNoise = 4 };
+
+__global__ __launch_bounds__(kRefillThreads) void refill_decide_kernel(int slots, int seed_count, int max_steps, const int32_t *__restrict__ ep_flags,
+                                                                       const int32_t *__restrict__ ep_steps, int32_t *__restrict__ assign,
+                                                                       int32_t *__restrict__ cursor)
+{
+    constexpr int kWaves = kRefillThreads / 64;
+    __shared__ int wave_fin[kWaves];
+    __shared__ int wave_live[kWaves];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int handed = cursor[0];
+    int run = 0;              // finished slots in the chunks before this one (the same value in every thread)
+    int live = 0;             // this thread's slots that run on or start a seed
+    for (int c0 = 0; c0 < slots; c0 += kRefillThreads) {        // (slots <= max_batch: a bounded number of chunks)
+        const int s = c0 + t;
+        const bool fin = s < slots && ((ep_flags[s] & 1) || ep_steps[s] >= max_steps);
+        const unsigned long long mask = __ballot(fin);
+        const int before = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_fin[wave] = __popcll(mask);
+        __syncthreads();
+        int rank = run + before, total = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) { if (w < wave) rank += wave_fin[w]; total += wave_fin[w]; }
+        if (s < slots) {
+            const int k = handed + rank;                        // (handed <= seed_count, rank < slots: no overflow below 2^31 seeds + slots)
+            const bool starts = fin && k < seed_count;
+            assign[s] = fin ? (starts ? k : kRefillDrain) : kRefillKeep;
+            live += (!fin || starts) ? 1 : 0;
+        }
+        run += total;
+        __syncthreads();                                        // wave_fin is rewritten by the next chunk
+    }
+    // live slots of the whole array: the threads' counts summed through LDS
+    __shared__ int part[kRefillThreads];
+    part[t] = live;
+    __syncthreads();
+    if (t < kWaves) {
+        int sum = 0;
+        for (int f = 0; f < 64; f++) sum += part[t * 64 + f];
+        wave_live[t] = sum;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int sum = 0;
+        for (int w = 0; w < kWaves; w++) sum += wave_live[w];
+        const int next = handed + run;
+        cursor[0] = next < seed_count ? next : seed_count;
+        cursor[1] = sum;
+    }
+}
+
+__global__ __launch_bounds__(64) void refill_apply_kernel(int slots, int n_obst, int N, int scenario, unsigned seed_first, int flags, int per_seed,
+                                                          double x_lo, double x_hi, double y_lo, double y_hi, double v_max, double edge,
+                                                          const int32_t *__restrict__ assign, const double *__restrict__ start, const double *__restrict__ goal_src,
+                                                          double *__restrict__ x0, double *__restrict__ obst, double *__restrict__ goal,
+                                                          double *__restrict__ X, double *__restrict__ U, double *__restrict__ min_margin,
+                                                          int32_t *__restrict__ ep_flags, int32_t *__restrict__ ep_steps, unsigned *__restrict__ state,
+                                                          double *__restrict__ noise, int32_t *__restrict__ slot_seed, double *__restrict__ res_f,
+                                                          int32_t *__restrict__ res_i)
+{
+#pragma clang fp contract(off)
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= slots) return;
+    const int a = assign[s];
+    unsigned *st = state + (size_t)s * kNoiseStateWords;
+    if (a != kRefillKeep) {
+        const int old = slot_seed[s];
+        if (old >= 0) {                                         // the raw words of the result row; the table's columns are formed on the host
+            double *rf = res_f + (size_t)old * 6;
+            rf[0] = min_margin[s];
+#pragma unroll
+            for (int c = 0; c < 5; c++) rf[1 + c] = x0[(size_t)s * 5 + c];
+            res_i[(size_t)old * 2] = ep_flags[s]; res_i[(size_t)old * 2 + 1] = ep_steps[s];
+        }
+        if (a == kRefillDrain) {                                // the sweep is exhausted: the slot idles like an episode that has reached its goal
+            if (old >= 0) slot_seed[s] = -1;
+            const int fl = ep_flags[s];
+            if (!(fl & 1)) ep_flags[s] = fl | 1;
+            return;
+        }
+        // np.random.seed(seed_first + a), then the scenario's uniform draws in the reference's order (scenario_wide_kernel's values, which are
+        // scenario_kernel's): behind them the generator is where noise_init_kernel leaves it
+        st[0] = seed_first + (unsigned)a;
+        for (int k = 1; k < 624; k++) st[k] = 1812433253u * (st[k - 1] ^ (st[k - 1] >> 30)) + (unsigned)k;
+        st[624] = 624u; st[625] = 0u; st[626] = 0u; st[627] = 0u;
+        NoiseGen g{st};
+        auto uniform = [&](double lo, double hi) { const double u = g.next_double(); return lo + (hi - lo) * u; };
+        double *o = obst + (size_t)s * n_obst * 4;
+        for (int j = 0; j < n_obst; j++) o[j * 4 + 0] = scenario == kScenarioRandom ? uniform(x_lo, x_hi) : (scenario == kScenarioEdge ? edge : 0.0);
+        for (int j = 0; j < n_obst; j++) o[j * 4 + 1] = scenario == kScenarioRandom ? uniform(y_lo, y_hi) : (scenario == kScenarioEdge ? edge : 0.0);
+        for (int j = 0; j < n_obst; j++) o[j * 4 + 2] = uniform(-v_max, v_max);
+        for (int j = 0; j < n_obst; j++) o[j * 4 + 3] = uniform(-v_max, v_max);
+        const size_t row = per_seed ? (size_t)a : 0;
+        double xs[5];
+#pragma unroll
+        for (int c = 0; c < 5; c++) xs[c] = start[row * 5 + c];
+        if (flags & kRefillAliasBug) { xs[3] = 0.0; xs[4] = 0.0; }      // set_initial_guess() aliases self.x0 and zeroes v, omega (defect D2)
+        const double gx = goal_src[row * 2], gy = goal_src[row * 2 + 1];
+#pragma unroll
+        for (int c = 0; c < 5; c++) x0[(size_t)s * 5 + c] = xs[c];
+        goal[(size_t)s * 2] = gx; goal[(size_t)s * 2 + 1] = gy;
+        double *Xs = X + (size_t)s * (N + 1) * 5, *Us = U + (size_t)s * N * 2;
+        for (int i = 0; i <= N; i++) {                          // reset_guess_kernel's arithmetic, stage by stage
+            double xg[5] = {xs[0], xs[1], xs[2], 0.0, 0.0};
+            if (flags & kRefillInterpGuess) interp_guess(xs, gy, i, N, xg);
+#pragma unroll
+            for (int c = 0; c < 5; c++) Xs[i * 5 + c] = xg[c];
+            if (i < N) { Us[i * 2] = 0.0; Us[i * 2 + 1] = 0.0; }
+        }
+        min_margin[s] = INFINITY; ep_flags[s] = 0; ep_steps[s] = 0;
+        slot_seed[s] = a;
+    }
+    if (flags & kRefillDrawNoise) {                             // noise_draw_kernel for the slots that run: one control step's normals
+        if (a == kRefillKeep && (ep_flags[s] & 1)) return;      // (a kept slot is never finished; the guard keeps the two kernels' conditions the same)
+        NoiseGen g{st};
+        double *nz = noise + (size_t)s * n_obst * 2;
+        for (int j = 0; j < n_obst; j++) { nz[2 * j] = g.gauss(); nz[2 * j + 1] = g.gauss(); }
+    }
+}
+
 // Plant integrator, robot_ocp_problem.py:207-212.
 __global__ void plant_step_kernel(int batch, double dt, const double *__restrict__ x, const double *__restrict__ u, double *__restrict__ xn)
 {

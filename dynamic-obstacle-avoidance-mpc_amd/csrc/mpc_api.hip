@@ -106,6 +106,7 @@ struct mpc_handle {
     double sqp_tol;                   // ... the step norm at or below which an instance stops
     int32_t *d_sqp_iters;             // ... the caller's words for the iterations run (mpc_set_sqp_iters_out_dev), or null
     double *d_ip_b_cfg;               // ... the handle's own bounds in max_batch rows: what the NSQP kernels (built on the bounds' code) read without instance bounds
+    int32_t *d_refill_assign;         // mpc_episode_refill_dev: the per-slot assignment its deciding launch hands to its applying launch, max_batch words, allocated on first use
 };
 
 namespace {
@@ -606,7 +607,7 @@ int mpc_destroy(mpc_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
                     h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own,
-                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own, h->d_ip_b_own, h->d_omask_full, h->d_ip_b_cfg};
+                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own, h->d_ip_b_own, h->d_omask_full, h->d_ip_b_cfg, h->d_refill_assign};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->h_pack) (void)hipHostFree(h->h_pack);
@@ -982,6 +983,38 @@ int mpc_noise_draw_dev(mpc_handle *h, int count, uint32_t *d_state, double *d_no
     if (!d_state || !d_noise) return fail(MPC_ERR_ARG, "null device pointer");
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(mpc::noise_draw_kernel, dim3((count + 63) / 64), dim3(64), 0, pick(h, stream), count, h->cfg.n_obst, d_state, d_noise, d_ep_flags);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+/* ------------------------------------------------- seed sweeps: on-device episode refill -------------------------------------------------- */
+
+int mpc_episode_refill_dev(mpc_handle *h, int slots, int scenario, unsigned seed_first, int seed_count, int max_steps, int flags, const double *box,
+                           const double *d_start, const double *d_goal_rows, int per_seed, double *d_x0, double *d_obst, double *d_goal, double *d_X,
+                           double *d_U, double *d_min_margin, int32_t *d_ep_flags, int32_t *d_ep_steps, uint32_t *d_state, double *d_noise,
+                           int32_t *d_slot_seed, int32_t *d_cursor, double *d_res_f, int32_t *d_res_i, void *stream)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (slots < 1 || slots > h->max_batch) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: slots outside [1, max_batch]");
+    if (scenario < 0 || scenario > 2) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: scenario must be 0 (RANDOM), 1 (CENTER) or 2 (EDGE)");
+    if (seed_count < 0) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: seed_count must be >= 0");
+    if (max_steps < 1) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: max_steps must be >= 1");
+    if (flags & ~(MPC_REFILL_ALIAS_BUG | MPC_REFILL_INTERP_GUESS | MPC_REFILL_DRAW_NOISE)) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: unknown flag");
+    if (per_seed != 0 && per_seed != 1) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: per_seed must be 0 or 1");
+    if (!box || !d_start || !d_goal_rows) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: null box, start or goal rows");
+    if (!d_x0 || !d_obst || !d_goal || !d_X || !d_U || !d_min_margin || !d_ep_flags || !d_ep_steps || !d_state)
+        return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: null slot array");
+    if ((flags & MPC_REFILL_DRAW_NOISE) && !d_noise) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: MPC_REFILL_DRAW_NOISE without a noise array");
+    if (!d_slot_seed || !d_cursor) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: null slot_seed or cursor");
+    if (!d_res_f || !d_res_i) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: null result array");
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->d_refill_assign) HIPCHK(hipMalloc(&h->d_refill_assign, (size_t)h->max_batch * sizeof(int32_t)));
+    hipStream_t s = pick(h, stream);
+    hipLaunchKernelGGL(mpc::refill_decide_kernel, dim3(1), dim3(mpc::kRefillThreads), 0, s, slots, seed_count, max_steps, d_ep_flags, d_ep_steps,
+                       h->d_refill_assign, d_cursor);
+    hipLaunchKernelGGL(mpc::refill_apply_kernel, dim3((slots + 63) / 64), dim3(64), 0, s, slots, h->cfg.n_obst, h->cfg.N, scenario, seed_first, flags, per_seed,
+                       box[0], box[1], box[2], box[3], box[4], box[5], h->d_refill_assign, d_start, d_goal_rows, d_x0, d_obst, d_goal, d_X, d_U,
+                       d_min_margin, d_ep_flags, d_ep_steps, d_state, d_noise, d_slot_seed, d_res_f, d_res_i);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }

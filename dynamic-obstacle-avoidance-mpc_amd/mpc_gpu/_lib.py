@@ -20,6 +20,7 @@ MPC_OK, MPC_ERR_ARG, MPC_ERR_HIP, MPC_ERR_NODEVICE = 0, -1, -2, -3
 STEP_SHIFT, STEP_PLANT, STEP_OBSTACLES, STEP_RESET_ON_FAIL, STEP_ALIAS_BUG, STEP_METRICS, STEP_INTERP_GUESS = 1, 2, 4, 8, 16, 32, 64
 STEP_ADVANCE_REF = 128
 STEP_MARGIN_ALL = 256
+REFILL_ALIAS_BUG, REFILL_INTERP_GUESS, REFILL_DRAW_NOISE = 1, 2, 4      # MPC_REFILL_* (mpc_episode_refill_dev)
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
 MAX_SQP_ITER = 100       # MPC_MAX_SQP_ITER
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
@@ -107,6 +108,7 @@ SYMBOLS = {
     "mpc_noise_state_words": (C.c_int, []),
     "mpc_noise_init_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, _vp, _vp]),
     "mpc_noise_draw_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "mpc_episode_refill_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 15),
     "mpc_comm_unique_id": (C.c_int, [_vp]),
     "mpc_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "mpc_comm_world": (C.c_int, [_vp]),

@@ -196,6 +196,171 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     return dict(table=table, x_last=xl, steps_run=k, solves=int(steps.sum().item()) + int((fl_h & 1).sum()), **extra)
 
 
+def refill_schedule(lengths, slots):
+    """The slot-order assignment of mpc_episode_refill_dev as a pure-numpy model.  lengths[k]: the fused control steps seed index k runs (a table row's
+    `iters + reached`, >= 1); slots: the slot count asked for (min(slots, count) are used).  In front of control step t every slot whose episode has
+    ended takes the lowest seed index not started yet, lowest slot first.  Returns dict(slot (count,), start (count,): the slot and the control
+    step at which each seed starts; steps: the control steps until the last episode ends = the fused steps a sweep launches)."""
+    import heapq
+    lengths = np.asarray(lengths)
+    if lengths.ndim != 1 or not np.issubdtype(lengths.dtype, np.number) or (lengths.size and (lengths != np.floor(lengths)).any()):
+        raise ValueError("lengths must be a 1-d array of whole step counts")
+    lengths = lengths.astype(np.int64)
+    if (lengths < 1).any():
+        raise ValueError("every episode runs at least one fused control step")
+    if int(slots) < 1:
+        raise ValueError("slots must be >= 1")
+    count = lengths.size
+    S = min(int(slots), count)
+    slot = np.zeros(count, dtype=np.int64); start = np.zeros(count, dtype=np.int64)
+    free = [(0, s) for s in range(S)]          # (control step at which the slot is free, slot): the heap pops the earliest step, then the lowest slot
+    heapq.heapify(free)
+    steps = 0
+    for k in range(count):
+        t, s = heapq.heappop(free)
+        slot[k], start[k] = s, t
+        steps = max(steps, t + int(lengths[k]))
+        heapq.heappush(free, (t + int(lengths[k]), s))
+    return dict(slot=slot, start=start, steps=int(steps))
+
+
+def _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every):
+    """run_seed_sweep's arguments, checked on the host before anything touches a device: (first, count, start rows, goal rows, per_seed)"""
+    if not isinstance(scenario, str):
+        raise ValueError("a sweep is defined by a scenario name (\"RANDOM\" | \"CENTER\" | \"EDGE\"): explicit obstacle states are run_episodes' business")
+    if scenario not in BatchedMpc.SCENARIOS:
+        raise ValueError(f"unknown scenario {scenario!r}: one of {sorted(BatchedMpc.SCENARIOS)}")
+    if isinstance(seeds, range):
+        if seeds.step != 1:
+            raise ValueError("seeds must be consecutive: a range with step 1, or (first, count)")
+        first, count = seeds.start, len(seeds)
+    else:
+        try:
+            first, count = seeds
+            first, count = int(first), int(count)
+        except (TypeError, ValueError):
+            raise ValueError("seeds must be (first, count) or a range with step 1") from None
+    if count < 1 or first < 0 or first + count > 2 ** 32:
+        raise ValueError("seeds must name at least one numpy seed in [0, 2^32)")
+    if count >= 2 ** 31:
+        raise ValueError("a sweep holds fewer than 2^31 seeds")
+    if int(slots) != slots or int(slots) < 1:
+        raise ValueError("slots must be a whole number >= 1")
+    if int(max_iter) < 1 or int(poll_every) < 1:
+        raise ValueError("max_iter and poll_every must be >= 1")
+    start = np.ascontiguousarray(start, dtype=np.float64); goal = np.ascontiguousarray(goal, dtype=np.float64)
+    per = []
+    for name, a, cols in (("start", start, 5), ("goal", goal, 2)):
+        if a.shape == (cols,) or a.shape == (1, cols):
+            per.append(False)
+        elif a.ndim == 2 and a.shape[1] == cols:
+            if a.shape[0] != count:
+                raise ValueError(f"per-seed {name} has {a.shape[0]} rows for {count} seeds")
+            per.append(True)
+        else:
+            raise ValueError(f"{name} must be ({cols},) or (count, {cols}), got {a.shape}")
+    per_seed = any(per)
+    rows = count if per_seed else 1
+    start = np.array(np.broadcast_to(start.reshape(-1, 5), (rows, 5)), order="C"); goal = np.array(np.broadcast_to(goal.reshape(-1, 2), (rows, 2)), order="C")      # (copies: writable)
+    return first, count, start, goal, per_seed
+
+
+def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True, init_guess_when_error=True,
+                   bug_compat_alias=True, interpolate_init=False, sqp=None, device=0, solver=None, poll_every=25, **cfg):
+    """experiments.py:20-36 for MORE SEEDS THAN SLOTS: the seeds stream through min(slots, count) slots, and a slot whose episode has ended (goal reached,
+    robot_ocp_problem.py:247-250, or max_iter control steps spent) starts the next seed on the device, in front of the next fused control step
+    (mpc_episode_refill_dev: no host read, no gather, every slot stays live until the seeds run out).  Seed index k is instance k of
+    run_episodes(start, goal, scenario, first_seed=first): the same scenario draw, noise stream, initial guess and control steps -- the table rows are
+    those of that one batch, bit for bit where an instance has a wavefront to itself and to the rounding of the wavefront sums where three share one.
+    scenario: "RANDOM" | "CENTER" | "EDGE".  seeds: (first, count) or a range with step 1.  start (5,), goal (2,): one row for all seeds, or (count, 5) /
+    (count, 2): one per seed.  random_move, init_guess_when_error, bug_compat_alias, interpolate_init, sqp: as run_episodes.
+    poll_every: every poll_every control steps the live-slot count goes to pinned host memory behind an event, and is looked at one poll later (the queue
+    never drains, and the loop ends at most two polls behind the last episode -- on idle slots); 1: after every refill, blocking, which also records the
+    schedule.  The loop launches at most ceil(count / slots) * max_iter + poll_every control steps whatever the device returns.
+    Returns dict(table (count, 6), x_last (count, 5), steps_run, solves, schedule): table as run_episodes builds it; steps_run the fused steps
+    launched -- with T = refill_schedule(table[:, 4] + table[:, 1], slots)["steps"] that is T for poll_every = 1 and (ceil(T / poll_every) + 1) * poll_every
+    otherwise (capped by the loop bound); schedule (count, 2) = slot and control step at
+    which each seed started (poll_every = 1; None otherwise), which is refill_schedule's slot / start.
+    Not offered: record, status_log, per-instance radii / masks / bounds (they need per-seed tables), host noise, PipelinedMpc."""
+    not_offered = sorted(set(cfg) & {"record", "status_log", "r_safe", "r_hit", "active", "margin_all", "bounds", "noise", "seed", "first_seed", "compact_from"})
+    if not_offered:
+        raise TypeError(f"run_seed_sweep has no argument {not_offered[0]!r}: it is run_episodes' (a sweep would need it per seed)")
+    first, count, start, goal, per_seed = _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every)
+    import torch
+    S = min(int(slots), count); max_iter = int(max_iter); poll_every = int(poll_every)
+    if interpolate_init and bug_compat_alias:
+        import warnings
+        warnings.warn("interpolate_init with bug_compat_alias=True: the straight-line guess is built from a plant state whose v, omega the aliasing defect has "
+                      "zeroed; the two recorded `interpolate_init` tables replay with bug_compat_alias=False (tests/test_gpu_replay.py)", stacklevel=2)
+    dev = torch.device("cuda", device)
+    m = solver or BatchedMpc(N, n_obst, Tf, max_batch=S, device=device, **cfg)
+    N, n_obst = m.N, m.n_obst
+    if sqp is not None:
+        m.set_sqp(*sqp)
+    stream = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(stream):
+        f64 = dict(dtype=torch.float64, device=dev); i32 = dict(dtype=torch.int32, device=dev)
+        dstart, dgoal_rows = torch.from_numpy(start).to(dev), torch.from_numpy(goal).to(dev)
+        dx0 = torch.zeros(S, 5, **f64); dgoal = torch.zeros(S, 2, **f64); dobst = torch.zeros(S, n_obst, 4, **f64)
+        X = torch.zeros(S, N + 1, 5, **f64); U = torch.zeros(S, N, 2, **f64)
+        status = torch.zeros(S, **i32); iters = torch.zeros(S, **i32)
+        margin = torch.full((S,), float("inf"), **f64)
+        flags = torch.ones(S, **i32); steps = torch.zeros(S, **i32)          # every slot "finished" and without a seed: the first refill fills them all
+        slot_seed = torch.full((S,), -1, **i32); cursor = torch.zeros(2, **i32)
+        gen_state = torch.zeros(S, _lib.lib().mpc_noise_state_words(), **i32)
+        nbuf = torch.zeros(S, n_obst, 2, **f64) if random_move else None
+        res_f = torch.full((count, 6), float("nan"), **f64); res_i = torch.full((count, 2), -1, **i32)
+        s = stream.cuda_stream
+        fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS
+        if init_guess_when_error:
+            fl |= _lib.STEP_RESET_ON_FAIL | (_lib.STEP_ALIAS_BUG if bug_compat_alias else 0) | (_lib.STEP_INTERP_GUESS if interpolate_init else 0)
+        rf = (_lib.REFILL_ALIAS_BUG if bug_compat_alias else 0) | (_lib.REFILL_INTERP_GUESS if interpolate_init else 0) | (_lib.REFILL_DRAW_NOISE if random_move else 0)
+        bound = -(-count // S) * max_iter + poll_every
+        schedule = np.full((count, 2), -1, dtype=np.int64) if poll_every == 1 else None
+        seen = np.full(S, -1, dtype=np.int64)
+        live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
+        live_event = None
+        k = 0
+        while True:
+            m.episode_refill_dev(S, scenario, first, count, max_iter, dstart, dgoal_rows, per_seed, dx0, dobst, dgoal, X, U, margin, flags, steps,
+                                 gen_state, nbuf, slot_seed, cursor, res_f, res_i, flags=rf, stream=s)
+            if poll_every == 1:
+                now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
+                new = (now != seen) & (now >= 0)
+                schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
+                seen = now
+                if int(cursor[1].item()) == 0:
+                    break
+            elif k % poll_every == 0:
+                # the count of the poll before this one, which the device passed long ago: the host stays at most two polls ahead of the device (no idle
+                # steps by the hundred behind the end of the sweep) and the device always has a poll's worth of steps queued (it never waits for the host)
+                if live_event is not None:
+                    live_event.synchronize()
+                    if int(live_host[0]) == 0:
+                        break
+                live_host.copy_(cursor[1:2], non_blocking=True)
+                live_event = torch.cuda.Event(); live_event.record(stream)
+            if k >= bound:
+                break
+            m.closed_loop_step_dev(S, dx0, dobst, dgoal, X, U, None, None, status, iters, nbuf, flags=fl,
+                                   min_margin=margin, ep_flags=flags, ep_steps=steps, stream=s)
+            k += 1
+        stream.synchronize()
+        left = int(cursor[1].item())
+        ri = res_i.cpu().numpy(); rfh = res_f.cpu().numpy()
+    if solver is None:
+        m.close()
+    elif sqp is not None:            # (a caller's solver leaves as it came)
+        m.set_sqp()
+    if left != 0 or (ri[:, 0] < 0).any():
+        raise _lib.MpcError(f"the sweep did not drain within {bound} control steps ({left} slots live, {int((ri[:, 0] < 0).sum())} rows not parked)")
+    fl_h, st_h, xl = ri[:, 0], ri[:, 1], np.ascontiguousarray(rfh[:, 1:6])
+    goal_all = np.ascontiguousarray(np.broadcast_to(goal, (count, 2)), dtype=np.float64)
+    table = np.column_stack([(fl_h & 4) != 0, (fl_h & 1) != 0, rfh[:, 0],
+                             np.linalg.norm(xl[:, :2] - goal_all, axis=1), st_h, (fl_h & 2) != 0]).astype(np.float64)
+    return dict(table=table, x_last=xl, steps_run=k, solves=int(st_h.sum()) + int((fl_h & 1).sum()), schedule=schedule)
+
+
 def visualisation_inputs(rec, instance, steps=None):
     """What the reference hands to its `VisDynamicRobotEnv` (robot_ocp_problem.py:270-276, visualization.py:135-151) for ONE instance of a
     recorded batch (`rec` = run_episodes(..., record=True)):

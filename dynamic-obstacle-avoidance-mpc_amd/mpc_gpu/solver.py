@@ -366,6 +366,16 @@ class BatchedMpc:
         """one control step's normals of the reference's stream -> noise (count, n_obst, 2); advances `state`"""
         _lib.check(_lib.lib().mpc_noise_draw_dev(self._h, count, _ptr(state), _ptr(noise), _ptr(ep_flags), _ptr(stream)))
 
+    def episode_refill_dev(self, slots, scenario, seed_first, seed_count, max_steps, start, goal_rows, per_seed, x0, obst, goal, X, U, min_margin,
+                           ep_flags, ep_steps, state, noise, slot_seed, cursor, res_f, res_i, flags=0, stream=None):
+        """one refill of a seed sweep, in front of closed_loop_step_dev (include/mpc_gpu.h mpc_episode_refill_dev): finished slots park their result
+        rows under their seed index and start the next seed indices in ascending slot order; flags: OR of _lib.REFILL_*"""
+        box = self._scenario_box()
+        _lib.check(_lib.lib().mpc_episode_refill_dev(self._h, int(slots), self.SCENARIOS[scenario], int(seed_first), int(seed_count), int(max_steps), int(flags),
+                                                     _ptr(box), _ptr(start), _ptr(goal_rows), 1 if per_seed else 0, _ptr(x0), _ptr(obst), _ptr(goal), _ptr(X),
+                                                     _ptr(U), _ptr(min_margin), _ptr(ep_flags), _ptr(ep_steps), _ptr(state), _ptr(noise), _ptr(slot_seed),
+                                                     _ptr(cursor), _ptr(res_f), _ptr(res_i), _ptr(stream)))
+
     # ------------------------------------------------------------------ multi-GPU: all-gather of the costs, RCCL called by the library itself
     @staticmethod
     def comm_unique_id():

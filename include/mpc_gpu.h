@@ -297,6 +297,34 @@ int mpc_obstacle_step_dev(mpc_handle *h, int count, double *d_obst, const double
 int mpc_noise_state_words(void);
 int mpc_noise_init_dev(mpc_handle *h, int count, int scenario, unsigned seed0, uint32_t *d_state, void *stream);
 int mpc_noise_draw_dev(mpc_handle *h, int count, uint32_t *d_state, double *d_noise, const int32_t *d_ep_flags, void *stream);
+/* SEED SWEEPS: on-device episode refill.  experiments.py:20-36 runs seed after seed, each until the goal is reached (robot_ocp_problem.py:247-250) or
+ * max_iter control steps are spent.  A sweep streams seed indices 0 .. seed_count-1 (numpy seeds seed_first + k) through a fixed number of slots: call
+ * this once per control step IN FRONT OF mpc_closed_loop_step_dev, on the same stream, with the slot arrays that call takes.  One call:
+ *   - a slot is FINISHED when ep_flags bit 0 is set or ep_steps >= max_steps;
+ *   - a finished slot with slot_seed >= 0 parks the raw words of its result under its seed index: d_res_f[seed][6] = min_margin, x0[5] and
+ *     d_res_i[seed][2] = ep_flags, ep_steps (table columns such as dist_to_goal are the host's to form);
+ *   - the seed indices not started yet go to the finished slots in ASCENDING SLOT ORDER (lowest finished slot, lowest remaining index): no atomics, no
+ *     dependence on the order workgroups run in, so the seed-to-slot schedule is a function of the episode lengths alone;
+ *   - a finished slot that gets no index (sweep exhausted) has slot_seed = -1 and ep_flags bit 0 set: the fused step and the noise draw skip it;
+ *   - a slot that gets index k is initialised as instance k of a scenario run: generator seeded with seed_first + k (d_state, the layout of
+ *     mpc_noise_init_dev), the scenario's uniform draws taken from it in the reference's order as the slot's obstacle states (the values of
+ *     mpc_generate_scenarios_dev; behind them the state is mpc_noise_init_dev's), x0 = the start row (v = omega = 0 with MPC_REFILL_ALIAS_BUG), the
+ *     goal row, X / U = the initial guess of mpc_reset_guess_dev (MPC_REFILL_INTERP_GUESS: of mpc_reset_guess_interp_dev), min_margin = +inf,
+ *     ep_flags = ep_steps = 0, slot_seed = k;
+ *   - MPC_REFILL_DRAW_NOISE: behind that, one control step's normals for every slot that runs, as mpc_noise_draw_dev writes them into d_noise;
+ *   - d_cursor[0] = seed indices handed out so far, d_cursor[1] = slots that run after this call (poll it; 0 = the sweep is over and every row parked).
+ * d_start [rows][5], d_goal_rows [rows][2]: rows = 1 (per_seed 0) or seed_count (per_seed 1, row k for index k).  box: as mpc_generate_scenarios_dev.
+ * First call of a sweep: slot_seed = -1, ep_flags = 1, cursor = {0, 0} -- every slot is then filled by the same code.  Two launches (a one-workgroup
+ * scan that decides, a grid over the slots that applies); the decision is handed over in words of the handle, so consecutive calls on one handle
+ * belong on one stream.  MPC_ERR_ARG (with a message, nothing launched): slots outside [1, max_batch], seed_count < 0, max_steps < 1, scenario outside
+ * 0 .. 2, unknown flags, per_seed outside {0, 1}, a null array (d_noise may be null without MPC_REFILL_DRAW_NOISE). */
+#define MPC_REFILL_ALIAS_BUG 1
+#define MPC_REFILL_INTERP_GUESS 2
+#define MPC_REFILL_DRAW_NOISE 4
+int mpc_episode_refill_dev(mpc_handle *h, int slots, int scenario, unsigned seed_first, int seed_count, int max_steps, int flags, const double *box,
+                           const double *d_start, const double *d_goal_rows, int per_seed, double *d_x0, double *d_obst, double *d_goal, double *d_X,
+                           double *d_U, double *d_min_margin, int32_t *d_ep_flags, int32_t *d_ep_steps, uint32_t *d_state, double *d_noise,
+                           int32_t *d_slot_seed, int32_t *d_cursor, double *d_res_f, int32_t *d_res_i, void *stream);
 /* MULTI-GPU: one process per GPU, every rank solves its own contiguous slice of the scenarios (the reference's 13 000 closed
  * loops, experiments.py:20-36, are independent), and the only exchange is an all-gather of the per-instance costs -- RCCL over xGMI, called directly
  * from this library (librccl.so.1 is loaded on first use; there is no link-time dependency and no other transport).  A C host does:

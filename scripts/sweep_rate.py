@@ -1,0 +1,143 @@
+"""What a seed sweep with on-device refill (run_seed_sweep) gives over the batch harness, and what the refill costs per control step, on the GPU.
+
+Workload: the reference's experiment (RANDOM, N 20, 5 obstacles, Tf 2, QP_ITER 100, max_iter 400) over --seeds seeds (default 16384), in four forms:
+  "chunks":     run_episodes on chunks of --slots episodes (default 1024), one after the other: what a caller did before;
+  "one_batch":  run_episodes on ONE batch of all seeds with its default compaction;
+  "sweep":      run_seed_sweep through --slots slots;
+  "sweep_wide": run_seed_sweep through 4 x --slots slots.
+Every form runs --reps times (default 3) behind one warm-up, the forms alternating rep by rep; wall time around calls that end in a device synchronise.
+Recorded per form: the times, their spread (max - min over median), episodes/s, fused steps launched.  Beside them the PREDICTED ratio of fused steps
+sweep / chunks -- refill_schedule over the lengths of the chunks' own tables against the sum of the chunks' longest episodes -- and whether the sweep's
+steps_run is what refill_schedule says (exactly, in one more run with poll_every = 1).
+
+Per-step overhead (HIP events on the step's stream, median of --launches single calls at --slots slots): mpc_episode_refill_dev with no slot finished,
+with one slot refilled and with every slot refilled, each with and without the noise draw; mpc_noise_draw_dev alone; the fused step.
+
+    python scripts/sweep_rate.py [--seeds 16384] [--slots 1024] [--reps 3] [--launches 30] [--out profiles/sweep_rates.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seeds", type=int, default=16384)
+    ap.add_argument("--slots", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--scenario", default="RANDOM")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_rates.json"))
+    a = ap.parse_args()
+    import torch
+    import mpc_gpu
+    import sweep_cases as sc
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this script measures on the device only")
+    L = mpc_gpu._lib
+    E, S, scen = a.seeds, a.slots, a.scenario
+    prob = dict(sc.PROBLEM, max_iter=400)
+    x0 = lambda n: np.tile(sc.START, (n, 1))
+    goal = lambda n: np.tile(sc.GOAL, (n, 1))
+
+    def chunks():
+        tabs, steps = [], 0
+        for c0 in range(0, E, S):
+            n = min(S, E - c0)
+            r = mpc_gpu.run_episodes(x0(n), goal(n), scen, first_seed=c0, **prob)
+            tabs.append(r["table"]); steps += r["steps_run"]
+        return dict(table=np.concatenate(tabs), steps_run=steps)
+
+    forms = {"chunks": chunks,
+             "one_batch": lambda: mpc_gpu.run_episodes(x0(E), goal(E), scen, first_seed=0, **prob),
+             "sweep": lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **prob),
+             "sweep_wide": lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), 4 * S, **prob)}
+    times, last = {f: [] for f in forms}, {}
+    for rep in range(a.reps + 1):               # rep 0: warm-up of every form
+        for f, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[f] = fn()
+            torch.cuda.synchronize()
+            if rep:
+                times[f].append(time.perf_counter() - t0)
+            print(json.dumps(dict(rep=rep, form=f, seconds=time.perf_counter() - t0, steps_run=last[f]["steps_run"])), flush=True)
+    res = {}
+    for f in forms:
+        ts = np.array(times[f])
+        res[f] = dict(seconds=[float(t) for t in ts], median_s=float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
+                      episodes_per_s=float(E / np.median(ts)), fused_steps=int(last[f]["steps_run"]),
+                      reached=float(last[f]["table"][:, 1].mean()), mean_steps=float(last[f]["table"][:, 4].mean()))
+    base = last["chunks"]["table"]
+    lengths = (base[:, 4] + base[:, 1]).astype(int)
+    chunk_steps = int(sum(lengths[c0:c0 + S].max() for c0 in range(0, E, S)))
+    pred = {}
+    for f, slots in (("sweep", S), ("sweep_wide", 4 * S)):
+        T = mpc_gpu.refill_schedule(lengths, slots)["steps"]
+        launched = (-(-T // 25) + 1) * 25
+        pred[f] = dict(slots=slots, schedule_steps=int(T), launched_steps_expected=int(launched), launched_steps=res[f]["fused_steps"],
+                       steps_as_predicted=bool(res[f]["fused_steps"] == launched),
+                       rows_equal_chunks=bool(np.array_equal(last[f]["table"], base)), rows_equal_fraction=float((last[f]["table"] == base).all(axis=1).mean()))
+    exact = mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, poll_every=1, **prob)
+    pred["sweep"]["poll_every_1_steps"] = int(exact["steps_run"])
+    pred["sweep"]["poll_every_1_steps_equal_schedule"] = bool(exact["steps_run"] == pred["sweep"]["schedule_steps"])
+    sched = mpc_gpu.refill_schedule(lengths, S)
+    pred["sweep"]["poll_every_1_schedule_equal_model"] = bool(np.array_equal(exact["schedule"][:, 0], sched["slot"]) and np.array_equal(exact["schedule"][:, 1], sched["start"]))
+    summary = dict(chunk_fused_steps_from_lengths=chunk_steps, chunk_fused_steps_launched=res["chunks"]["fused_steps"],
+                   predicted_step_ratio_sweep_over_chunks=pred["sweep"]["schedule_steps"] / chunk_steps,
+                   measured_time_ratio_sweep_over_chunks=res["sweep"]["median_s"] / res["chunks"]["median_s"],
+                   sweep_not_slower_than_chunks_beyond_spread=bool(res["sweep"]["median_s"] <= res["chunks"]["median_s"] * (1 + max(res["sweep"]["spread"], res["chunks"]["spread"]))),
+                   one_batch_rows_equal_fraction=float((last["one_batch"]["table"] == base).all(axis=1).mean()))
+    print(json.dumps(dict(forms=res, prediction=pred, summary=summary)), flush=True)
+
+    # ---- the per-step overhead: single launches between HIP events
+    dev = torch.device("cuda", 0)
+    over = {}
+    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        st = torch.cuda.current_stream(); cs = st.cuda_stream
+        arr = sc.SlotArrays(sc.Plain(torch, dev), m, S, E, L.lib().mpc_noise_state_words())
+        step_flags = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES | L.STEP_METRICS | L.STEP_RESET_ON_FAIL | L.STEP_ALIAS_BUG
+        base_fl = L.REFILL_ALIAS_BUG
+
+        def timed(fn, before=None):
+            ms = []
+            for _ in range(a.launches):
+                if before:
+                    before()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st); fn(); e1.record(st)
+                st.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            return dict(median_us=1e3 * float(np.median(ms)), min_us=1e3 * float(np.min(ms)), max_us=1e3 * float(np.max(ms)))
+
+        def fresh():
+            arr.flags.fill_(1); arr.slot_seed.fill_(-1); arr.cursor.zero_()
+
+        for tag, fl in (("", base_fl), ("_with_noise", base_fl | L.REFILL_DRAW_NOISE)):
+            over["refill_every_slot" + tag] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs), before=fresh)
+        for _ in range(10):                     # a few control steps in: every slot runs
+            arr.refill(m, scen, 0, 400, base_fl | L.REFILL_DRAW_NOISE, cs); arr.step(m, step_flags, cs)
+        st.synchronize()
+        assert int((arr.flags & 1).sum().item()) == 0
+        for tag, fl in (("", base_fl), ("_with_noise", base_fl | L.REFILL_DRAW_NOISE)):
+            over["refill_nothing_finished" + tag] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs))
+            over["refill_one_slot" + tag] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs), before=lambda: arr.flags[S // 2:S // 2 + 1].fill_(1))
+        over["noise_draw_alone"] = timed(lambda: m.noise_draw_dev(S, arr.state, arr.noise, ep_flags=arr.flags, stream=cs))
+        over["fused_step"] = timed(lambda: arr.step(m, step_flags, cs))
+        over["fused_step_kernel"] = m.kernel_name(S)
+    print(json.dumps(dict(per_step_overhead=over)), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(dict(workload=dict(scenario=scen, seeds=E, slots=S, reps=a.reps, **prob), forms=res, prediction=pred, summary=summary,
+                       per_step_overhead=dict(slots=S, launches=a.launches, **over)), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
