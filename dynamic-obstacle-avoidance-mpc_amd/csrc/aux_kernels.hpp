@@ -371,6 +371,7 @@ __global__ void reset_guess_kernel(int batch, int N, const double *__restrict__ 
 //     lengths alone (with three instances per wavefront an episode's rounding depends on its neighbours, so a sweep is reproducible only if this is).
 //     It writes assign[slot] and the cursor and NOTHING the decision reads;
 //   refill_apply_kernel, one thread per slot: parks, reseeds (and draws the step's noise).  Every word it writes belongs to its own slot or its own seed.
+//     (refill_apply_ext_kernel: the same body with per-seed tables, the status log and / or the ring of seeded episodes, RefillExtra below.)
 // assign[slot]: kRefillKeep the episode runs on; kRefillDrain it has ended and no seed is left; k >= 0 it has ended and seed index k starts here.
 constexpr int kRefillThreads = 256, kRefillKeep = -2, kRefillDrain = -1;
 enum { kRefillAliasBug = 1, kRefillInterpGuess = 2, kRefillDrawNoise = 4 };
@@ -424,14 +425,47 @@ __global__ __launch_bounds__(kRefillThreads) void refill_decide_kernel(int slots
     }
 }
 
-__global__ __launch_bounds__(64) void refill_apply_kernel(int slots, int n_obst, int N, int scenario, unsigned seed_first, int flags, int per_seed,
-                                                          double x_lo, double x_hi, double y_lo, double y_hi, double v_max, double edge,
-                                                          const int32_t *__restrict__ assign, const double *__restrict__ start, const double *__restrict__ goal_src,
-                                                          double *__restrict__ x0, double *__restrict__ obst, double *__restrict__ goal,
-                                                          double *__restrict__ X, double *__restrict__ U, double *__restrict__ min_margin,
-                                                          int32_t *__restrict__ ep_flags, int32_t *__restrict__ ep_steps, unsigned *__restrict__ state,
-                                                          double *__restrict__ noise, int32_t *__restrict__ slot_seed, double *__restrict__ res_f,
-                                                          int32_t *__restrict__ res_i)
+// What a sweep may add to the apply launch (mpc_set_refill_tables_dev, mpc_episode_ring_dev); all device pointers, any of them null.
+//   PER-SEED TABLES: row k of a source goes to row s of its destination when seed index k starts in slot s -- the destinations are the per-slot arrays the
+//     solve reads in place (mpc_set_instance_params_dev, mpc_set_obstacle_mask_dev, mpc_set_instance_bounds_dev);
+//   STATUS LOG: log[s] = {n2, n4, first_bad, seen} is reset when a seed starts and counted by status_log_kernel behind every fused step; a parked slot parks
+//     log[s][0..2] under its seed index in res_log;
+//   RING: a cache of seeded episodes (ring_fill_kernel).  Entry k % ring_cap holds generator state and obstacle states of seed index k when its tag says so;
+//     a slot that starts k copies them instead of seeding, and seeds in place otherwise.  seed_src[k] = 1 (ring) / 0 (in place).
+// The rule of the refill holds: every word the apply launch writes belongs to its own slot or its own seed, and it reads nothing another of its threads writes.
+struct RefillExtra {
+    const double *W, *We, *r_safe, *r_hit; const uint32_t *mask; const double *bounds;
+    double *slot_W, *slot_We, *slot_r_safe, *slot_r_hit; uint32_t *slot_mask; double *slot_bounds;
+    int32_t *log, *res_log;
+    int ring_cap; const unsigned *ring_state; const double *ring_obst; const int32_t *ring_tag; int32_t *seed_src;
+};
+
+// np.random.seed(seed), then the scenario's uniform draws in the reference's order (scenario_wide_kernel's values, which are scenario_kernel's) into o[n_obst][4]:
+// behind them the generator is where noise_init_kernel leaves it
+__device__ __forceinline__ void seed_scenario(unsigned *st, double *o, unsigned seed, int n_obst, int scenario, double x_lo, double x_hi, double y_lo, double y_hi,
+                                              double v_max, double edge)
+{
+#pragma clang fp contract(off)
+    st[0] = seed;
+    for (int k = 1; k < 624; k++) st[k] = 1812433253u * (st[k - 1] ^ (st[k - 1] >> 30)) + (unsigned)k;
+    st[624] = 624u; st[625] = 0u; st[626] = 0u; st[627] = 0u;
+    NoiseGen g{st};
+    auto uniform = [&](double lo, double hi) { const double u = g.next_double(); return lo + (hi - lo) * u; };
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 0] = scenario == kScenarioRandom ? uniform(x_lo, x_hi) : (scenario == kScenarioEdge ? edge : 0.0);
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 1] = scenario == kScenarioRandom ? uniform(y_lo, y_hi) : (scenario == kScenarioEdge ? edge : 0.0);
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 2] = uniform(-v_max, v_max);
+    for (int j = 0; j < n_obst; j++) o[j * 4 + 3] = uniform(-v_max, v_max);
+}
+
+template <bool TABLES, bool RING>
+__device__ __forceinline__ void refill_apply_body(int slots, int n_obst, int N, int scenario, unsigned seed_first, int flags, int per_seed,
+                                                  double x_lo, double x_hi, double y_lo, double y_hi, double v_max, double edge,
+                                                  const int32_t *__restrict__ assign, const double *__restrict__ start, const double *__restrict__ goal_src,
+                                                  double *__restrict__ x0, double *__restrict__ obst, double *__restrict__ goal,
+                                                  double *__restrict__ X, double *__restrict__ U, double *__restrict__ min_margin,
+                                                  int32_t *__restrict__ ep_flags, int32_t *__restrict__ ep_steps, unsigned *__restrict__ state,
+                                                  double *__restrict__ noise, int32_t *__restrict__ slot_seed, double *__restrict__ res_f,
+                                                  int32_t *__restrict__ res_i, const RefillExtra &ex)
 {
 #pragma clang fp contract(off)
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -446,6 +480,12 @@ __global__ __launch_bounds__(64) void refill_apply_kernel(int slots, int n_obst,
 #pragma unroll
             for (int c = 0; c < 5; c++) rf[1 + c] = x0[(size_t)s * 5 + c];
             res_i[(size_t)old * 2] = ep_flags[s]; res_i[(size_t)old * 2 + 1] = ep_steps[s];
+            if constexpr (TABLES) {
+                if (ex.log) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) ex.res_log[(size_t)old * 3 + c] = ex.log[(size_t)s * 4 + c];
+                }
+            }
         }
         if (a == kRefillDrain) {                                // the sweep is exhausted: the slot idles like an episode that has reached its goal
             if (old >= 0) slot_seed[s] = -1;
@@ -453,18 +493,29 @@ __global__ __launch_bounds__(64) void refill_apply_kernel(int slots, int n_obst,
             if (!(fl & 1)) ep_flags[s] = fl | 1;
             return;
         }
-        // np.random.seed(seed_first + a), then the scenario's uniform draws in the reference's order (scenario_wide_kernel's values, which are
-        // scenario_kernel's): behind them the generator is where noise_init_kernel leaves it
-        st[0] = seed_first + (unsigned)a;
-        for (int k = 1; k < 624; k++) st[k] = 1812433253u * (st[k - 1] ^ (st[k - 1] >> 30)) + (unsigned)k;
-        st[624] = 624u; st[625] = 0u; st[626] = 0u; st[627] = 0u;
-        NoiseGen g{st};
-        auto uniform = [&](double lo, double hi) { const double u = g.next_double(); return lo + (hi - lo) * u; };
         double *o = obst + (size_t)s * n_obst * 4;
-        for (int j = 0; j < n_obst; j++) o[j * 4 + 0] = scenario == kScenarioRandom ? uniform(x_lo, x_hi) : (scenario == kScenarioEdge ? edge : 0.0);
-        for (int j = 0; j < n_obst; j++) o[j * 4 + 1] = scenario == kScenarioRandom ? uniform(y_lo, y_hi) : (scenario == kScenarioEdge ? edge : 0.0);
-        for (int j = 0; j < n_obst; j++) o[j * 4 + 2] = uniform(-v_max, v_max);
-        for (int j = 0; j < n_obst; j++) o[j * 4 + 3] = uniform(-v_max, v_max);
+        bool cached = false;
+        if constexpr (RING) {                                   // the ring is a cache: an entry whose tag is not this index is not used
+            const int e = a % ex.ring_cap;
+            cached = ex.ring_tag[e] == a;
+            if (cached) {
+                const unsigned *rs = ex.ring_state + (size_t)e * kNoiseStateWords;
+                for (int k = 0; k < kNoiseStateWords; k++) st[k] = rs[k];
+                const double *ro = ex.ring_obst + (size_t)e * n_obst * 4;
+                for (int k = 0; k < n_obst * 4; k++) o[k] = ro[k];
+            }
+            if (ex.seed_src) ex.seed_src[a] = cached ? 1 : 0;
+        }
+        if (!cached) seed_scenario(st, o, seed_first + (unsigned)a, n_obst, scenario, x_lo, x_hi, y_lo, y_hi, v_max, edge);
+        if constexpr (TABLES) {                                 // row a of every per-seed source that is given -> row s of its per-slot destination
+            if (ex.W) for (int c = 0; c < 6; c++) ex.slot_W[(size_t)s * 6 + c] = ex.W[(size_t)a * 6 + c];
+            if (ex.We) for (int c = 0; c < 4; c++) ex.slot_We[(size_t)s * 4 + c] = ex.We[(size_t)a * 4 + c];
+            if (ex.r_safe) for (int j = 0; j < n_obst; j++) ex.slot_r_safe[(size_t)s * n_obst + j] = ex.r_safe[(size_t)a * n_obst + j];
+            if (ex.r_hit) for (int j = 0; j < n_obst; j++) ex.slot_r_hit[(size_t)s * n_obst + j] = ex.r_hit[(size_t)a * n_obst + j];
+            if (ex.mask) ex.slot_mask[s] = ex.mask[a];
+            if (ex.bounds) for (int c = 0; c < kIpB; c++) ex.slot_bounds[(size_t)s * kIpB + c] = ex.bounds[(size_t)a * kIpB + c];
+            if (ex.log) { int32_t *lg = ex.log + (size_t)s * 4; lg[0] = 0; lg[1] = 0; lg[2] = -1; lg[3] = 0; }
+        }
         const size_t row = per_seed ? (size_t)a : 0;
         double xs[5];
 #pragma unroll
@@ -490,6 +541,74 @@ __global__ __launch_bounds__(64) void refill_apply_kernel(int slots, int n_obst,
         NoiseGen g{st};
         double *nz = noise + (size_t)s * n_obst * 2;
         for (int j = 0; j < n_obst; j++) { nz[2 * j] = g.gauss(); nz[2 * j + 1] = g.gauss(); }
+    }
+}
+
+// the plain sweep: no tables, no ring -- the launch of a handle on which neither was set
+__global__ __launch_bounds__(64) void refill_apply_kernel(int slots, int n_obst, int N, int scenario, unsigned seed_first, int flags, int per_seed,
+                                                          double x_lo, double x_hi, double y_lo, double y_hi, double v_max, double edge,
+                                                          const int32_t *__restrict__ assign, const double *__restrict__ start, const double *__restrict__ goal_src,
+                                                          double *__restrict__ x0, double *__restrict__ obst, double *__restrict__ goal,
+                                                          double *__restrict__ X, double *__restrict__ U, double *__restrict__ min_margin,
+                                                          int32_t *__restrict__ ep_flags, int32_t *__restrict__ ep_steps, unsigned *__restrict__ state,
+                                                          double *__restrict__ noise, int32_t *__restrict__ slot_seed, double *__restrict__ res_f,
+                                                          int32_t *__restrict__ res_i)
+{
+    refill_apply_body<false, false>(slots, n_obst, N, scenario, seed_first, flags, per_seed, x_lo, x_hi, y_lo, y_hi, v_max, edge, assign, start, goal_src, x0, obst, goal,
+                                    X, U, min_margin, ep_flags, ep_steps, state, noise, slot_seed, res_f, res_i, RefillExtra{});
+}
+
+// ... with per-seed tables / the status log (TABLES) and / or a ring attached (RING)
+template <bool TABLES, bool RING>
+__global__ __launch_bounds__(64) void refill_apply_ext_kernel(int slots, int n_obst, int N, int scenario, unsigned seed_first, int flags, int per_seed,
+                                                              double x_lo, double x_hi, double y_lo, double y_hi, double v_max, double edge,
+                                                              const int32_t *__restrict__ assign, const double *__restrict__ start, const double *__restrict__ goal_src,
+                                                              double *__restrict__ x0, double *__restrict__ obst, double *__restrict__ goal,
+                                                              double *__restrict__ X, double *__restrict__ U, double *__restrict__ min_margin,
+                                                              int32_t *__restrict__ ep_flags, int32_t *__restrict__ ep_steps, unsigned *__restrict__ state,
+                                                              double *__restrict__ noise, int32_t *__restrict__ slot_seed, double *__restrict__ res_f,
+                                                              int32_t *__restrict__ res_i, RefillExtra ex)
+{
+    refill_apply_body<TABLES, RING>(slots, n_obst, N, scenario, seed_first, flags, per_seed, x_lo, x_hi, y_lo, y_hi, v_max, edge, assign, start, goal_src, x0, obst, goal,
+                                    X, U, min_margin, ep_flags, ep_steps, state, noise, slot_seed, res_f, res_i, ex);
+}
+
+// RING FILL (mpc_episode_ring_fill_dev), one thread per ring entry e.  With handed = cursor[0] (the seed indices started so far) thread e owns the one index k in
+// [handed, handed + capacity) with k % capacity == e; if that index exists and the entry does not hold it yet, the thread seeds seed_first + k there -- refill_apply's
+// own sequence (seed_scenario), so the state is mpc_noise_init_dev's -- and writes the tag LAST.  An entry is overwritten only by k + capacity, which is owned only once
+// k has been handed out (k < handed), i.e. copied by an earlier apply launch.  No atomics, no waiting: each thread reads the cursor and its own entry, and writes its own entry.
+__global__ __launch_bounds__(64) void ring_fill_kernel(int capacity, int n_obst, int scenario, unsigned seed_first, int seed_count,
+                                                       double x_lo, double x_hi, double y_lo, double y_hi, double v_max, double edge,
+                                                       const int32_t *__restrict__ cursor, unsigned *__restrict__ ring_state, double *__restrict__ ring_obst,
+                                                       int32_t *__restrict__ ring_tag)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= capacity) return;
+    const int handed = cursor[0];
+    const int r = handed % capacity;
+    const long long k = (long long)handed + (e >= r ? e - r : e - r + capacity);      // (handed + capacity may pass 2^31)
+    if (k >= seed_count || ring_tag[e] == (int)k) return;
+    seed_scenario(ring_state + (size_t)e * kNoiseStateWords, ring_obst + (size_t)e * n_obst * 4, seed_first + (unsigned)k, n_obst, scenario,
+                  x_lo, x_hi, y_lo, y_hi, v_max, edge);
+    ring_tag[e] = (int)k;
+}
+
+// STATUS LOG (mpc_episode_status_log_dev), behind the fused step, one thread per slot: run_episodes' status2 / status4 / first_bad arithmetic per slot.
+// now = the episode steps the slot has solved (ep_steps counts the steps that did not reach the goal, bit 0 of ep_flags the one that did); if that passed `seen`, the
+// slot solved at episode step `seen` and its status word is that solve's
+__global__ void status_log_kernel(int slots, const int32_t *__restrict__ status, const int32_t *__restrict__ ep_flags, const int32_t *__restrict__ ep_steps,
+                                  int32_t *__restrict__ log)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= slots) return;
+    int32_t *lg = log + (size_t)s * 4;
+    const int now = ep_steps[s] + (ep_flags[s] & 1), seen = lg[3];
+    if (now > seen) {
+        const int st = status[s];
+        if (st == 2) lg[0] += 1;
+        if (st == 4) lg[1] += 1;
+        if (st != 0 && lg[2] < 0) lg[2] = seen;
+        lg[3] = now;
     }
 }
 

@@ -107,6 +107,12 @@ struct mpc_handle {
     int32_t *d_sqp_iters;             // ... the caller's words for the iterations run (mpc_set_sqp_iters_out_dev), or null
     double *d_ip_b_cfg;               // ... the handle's own bounds in max_batch rows: what the NSQP kernels (built on the bounds' code) read without instance bounds
     int32_t *d_refill_assign;         // mpc_episode_refill_dev: the per-slot assignment its deciding launch hands to its applying launch, max_batch words, allocated on first use
+    bool rt_on;                       // per-seed tables / status log of the refill (mpc_set_refill_tables_dev): the caller's device pointers, used in place
+    mpc_refill_tables rt;
+    int ring_cap;                     // ring of seeded episodes (mpc_episode_ring_dev): entries, 0 = none attached; the caller's device arrays
+    uint32_t *ring_state; double *ring_obst; int32_t *ring_tag, *ring_seed_src;
+    bool ring_filled;                 // ... what the last mpc_episode_ring_fill_dev seeded it for: a refill with other values is refused
+    int ring_scenario, ring_seed_count; unsigned ring_seed_first; double ring_box[6];
 };
 
 namespace {
@@ -1007,15 +1013,93 @@ int mpc_episode_refill_dev(mpc_handle *h, int slots, int scenario, unsigned seed
     if ((flags & MPC_REFILL_DRAW_NOISE) && !d_noise) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: MPC_REFILL_DRAW_NOISE without a noise array");
     if (!d_slot_seed || !d_cursor) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: null slot_seed or cursor");
     if (!d_res_f || !d_res_i) return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: null result array");
+    if (h->ring_cap && h->ring_filled && (scenario != h->ring_scenario || seed_first != h->ring_seed_first || seed_count != h->ring_seed_count ||
+                                          memcmp(box, h->ring_box, sizeof(h->ring_box)) != 0))
+        return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: scenario, seed_first, seed_count or box differ from those of the ring's last fill (mpc_episode_ring_fill_dev)");
     HIPCHK(hipSetDevice(h->device));
     if (!h->d_refill_assign) HIPCHK(hipMalloc(&h->d_refill_assign, (size_t)h->max_batch * sizeof(int32_t)));
     hipStream_t s = pick(h, stream);
     hipLaunchKernelGGL(mpc::refill_decide_kernel, dim3(1), dim3(mpc::kRefillThreads), 0, s, slots, seed_count, max_steps, d_ep_flags, d_ep_steps,
                        h->d_refill_assign, d_cursor);
-    hipLaunchKernelGGL(mpc::refill_apply_kernel, dim3((slots + 63) / 64), dim3(64), 0, s, slots, h->cfg.n_obst, h->cfg.N, scenario, seed_first, flags, per_seed,
-                       box[0], box[1], box[2], box[3], box[4], box[5], h->d_refill_assign, d_start, d_goal_rows, d_x0, d_obst, d_goal, d_X, d_U,
-                       d_min_margin, d_ep_flags, d_ep_steps, d_state, d_noise, d_slot_seed, d_res_f, d_res_i);
+    if (!h->rt_on && !h->ring_cap) {      // a handle on which neither was set launches what it always has
+        hipLaunchKernelGGL(mpc::refill_apply_kernel, dim3((slots + 63) / 64), dim3(64), 0, s, slots, h->cfg.n_obst, h->cfg.N, scenario, seed_first, flags, per_seed,
+                           box[0], box[1], box[2], box[3], box[4], box[5], h->d_refill_assign, d_start, d_goal_rows, d_x0, d_obst, d_goal, d_X, d_U,
+                           d_min_margin, d_ep_flags, d_ep_steps, d_state, d_noise, d_slot_seed, d_res_f, d_res_i);
+    } else {
+        mpc::RefillExtra ex;
+        memset(&ex, 0, sizeof(ex));
+        if (h->rt_on) {
+            const mpc_refill_tables &t = h->rt;
+            ex.W = t.W; ex.We = t.We; ex.r_safe = t.r_safe; ex.r_hit = t.r_hit; ex.mask = t.mask; ex.bounds = t.bounds;
+            ex.slot_W = t.slot_W; ex.slot_We = t.slot_We; ex.slot_r_safe = t.slot_r_safe; ex.slot_r_hit = t.slot_r_hit; ex.slot_mask = t.slot_mask; ex.slot_bounds = t.slot_bounds;
+            ex.log = t.log; ex.res_log = t.res_log;
+        }
+        ex.ring_cap = h->ring_cap; ex.ring_state = h->ring_state; ex.ring_obst = h->ring_obst; ex.ring_tag = h->ring_tag; ex.seed_src = h->ring_seed_src;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((slots + 63) / 64), dim3(64), 0, s, slots, h->cfg.n_obst, h->cfg.N, scenario, seed_first, flags, per_seed,
+                               box[0], box[1], box[2], box[3], box[4], box[5], (const int32_t *)h->d_refill_assign, d_start, d_goal_rows, d_x0, d_obst, d_goal, d_X, d_U,
+                               d_min_margin, d_ep_flags, d_ep_steps, d_state, d_noise, d_slot_seed, d_res_f, d_res_i, ex);
+        };
+        if (h->rt_on && h->ring_cap) go(mpc::refill_apply_ext_kernel<true, true>);
+        else if (h->rt_on) go(mpc::refill_apply_ext_kernel<true, false>);
+        else go(mpc::refill_apply_ext_kernel<false, true>);
+    }
     HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_set_refill_tables_dev(mpc_handle *h, const mpc_refill_tables *t)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!t) { h->rt_on = false; memset(&h->rt, 0, sizeof(h->rt)); return MPC_OK; }
+    const struct { const char *name; const void *src, *dst; } pairs[6] = {{"W", t->W, t->slot_W}, {"We", t->We, t->slot_We}, {"r_safe", t->r_safe, t->slot_r_safe},
+                                                                          {"r_hit", t->r_hit, t->slot_r_hit}, {"mask", t->mask, t->slot_mask}, {"bounds", t->bounds, t->slot_bounds}};
+    bool any = false;
+    for (const auto &p : pairs) {
+        if (p.src && !p.dst) return fail(MPC_ERR_ARG, "mpc_set_refill_tables_dev: %s is given without its per-slot destination slot_%s", p.name, p.name);
+        any = any || p.src;
+    }
+    if ((t->log != nullptr) != (t->res_log != nullptr)) return fail(MPC_ERR_ARG, "mpc_set_refill_tables_dev: log and res_log come together (%s is null)", t->log ? "res_log" : "log");
+    if (!any && !t->log) return fail(MPC_ERR_ARG, "mpc_set_refill_tables_dev: no source and no log given (NULL switches the tables off)");
+    h->rt = *t; h->rt_on = true;
+    return MPC_OK;
+}
+
+int mpc_episode_status_log_dev(mpc_handle *h, int slots, const int32_t *d_status, const int32_t *d_ep_flags, const int32_t *d_ep_steps, int32_t *d_log, void *stream)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (slots < 1 || slots > h->max_batch) return fail(MPC_ERR_ARG, "mpc_episode_status_log_dev: slots outside [1, max_batch]");
+    if (!d_status || !d_ep_flags || !d_ep_steps || !d_log) return fail(MPC_ERR_ARG, "mpc_episode_status_log_dev: null status, ep_flags, ep_steps or log");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(mpc::status_log_kernel, dim3((slots + 63) / 64), dim3(64), 0, pick(h, stream), slots, d_status, d_ep_flags, d_ep_steps, d_log);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_episode_ring_dev(mpc_handle *h, int capacity, uint32_t *d_ring_state, double *d_ring_obst, int32_t *d_ring_tag, int32_t *d_seed_src)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (capacity < 0) return fail(MPC_ERR_ARG, "mpc_episode_ring_dev: capacity must be >= 0 (0 detaches the ring)");
+    if (capacity > 0 && (!d_ring_state || !d_ring_obst || !d_ring_tag)) return fail(MPC_ERR_ARG, "mpc_episode_ring_dev: null ring_state, ring_obst or ring_tag");
+    h->ring_filled = false;
+    if (capacity == 0) { h->ring_cap = 0; h->ring_state = nullptr; h->ring_obst = nullptr; h->ring_tag = nullptr; h->ring_seed_src = nullptr; return MPC_OK; }
+    h->ring_cap = capacity; h->ring_state = d_ring_state; h->ring_obst = d_ring_obst; h->ring_tag = d_ring_tag; h->ring_seed_src = d_seed_src;
+    return MPC_OK;
+}
+
+int mpc_episode_ring_fill_dev(mpc_handle *h, int scenario, unsigned seed_first, int seed_count, const double *box, const int32_t *d_cursor, void *stream)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!h->ring_cap) return fail(MPC_ERR_ARG, "mpc_episode_ring_fill_dev: no ring attached (mpc_episode_ring_dev)");
+    if (scenario < 0 || scenario > 2) return fail(MPC_ERR_ARG, "mpc_episode_ring_fill_dev: scenario must be 0 (RANDOM), 1 (CENTER) or 2 (EDGE)");
+    if (seed_count < 0) return fail(MPC_ERR_ARG, "mpc_episode_ring_fill_dev: seed_count must be >= 0");
+    if (!box || !d_cursor) return fail(MPC_ERR_ARG, "mpc_episode_ring_fill_dev: null box or cursor");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(mpc::ring_fill_kernel, dim3((h->ring_cap + 63) / 64), dim3(64), 0, pick(h, stream), h->ring_cap, h->cfg.n_obst, scenario, seed_first, seed_count,
+                       box[0], box[1], box[2], box[3], box[4], box[5], d_cursor, h->ring_state, h->ring_obst, h->ring_tag);
+    HIPCHK(hipGetLastError());
+    h->ring_filled = true; h->ring_scenario = scenario; h->ring_seed_first = seed_first; h->ring_seed_count = seed_count;
+    memcpy(h->ring_box, box, sizeof(h->ring_box));
     return MPC_OK;
 }
 

@@ -48,6 +48,14 @@ class MpcConfig(C.Structure):
 
 # every symbol include/mpc_gpu.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
+
+
+class RefillTables(C.Structure):
+    """Mirror of `struct mpc_refill_tables` (include/mpc_gpu.h): device pointers only -- per-seed sources, per-slot destinations, the status log."""
+    _fields_ = [(n, _vp) for n in ("W", "We", "r_safe", "r_hit", "mask", "bounds",
+                                   "slot_W", "slot_We", "slot_r_safe", "slot_r_hit", "slot_mask", "slot_bounds", "log", "res_log")]
+
+
 _cfgp = C.POINTER(MpcConfig)
 SYMBOLS = {
     "mpc_abi_version": (C.c_int, []),
@@ -109,6 +117,10 @@ SYMBOLS = {
     "mpc_noise_init_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, _vp, _vp]),
     "mpc_noise_draw_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_episode_refill_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 15),
+    "mpc_set_refill_tables_dev": (C.c_int, [_vp, C.POINTER(RefillTables)]),
+    "mpc_episode_status_log_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mpc_episode_ring_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "mpc_episode_ring_fill_dev": (C.c_int, [_vp, C.c_int, C.c_uint, C.c_int, _vp, _vp, _vp]),
     "mpc_comm_unique_id": (C.c_int, [_vp]),
     "mpc_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "mpc_comm_world": (C.c_int, [_vp]),

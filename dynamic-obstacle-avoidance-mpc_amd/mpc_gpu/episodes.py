@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .solver import BatchedMpc
+from .solver import BOUNDS_ROW, BatchedMpc, pack_instance_bounds, pack_obstacle_mask
 
 
 def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, init_guess_when_error=True,
@@ -265,8 +265,88 @@ def _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every):
     return first, count, start, goal, per_seed
 
 
+# mpc_default_config's box bounds (robot_ocp_problem.py:91-96): what a handle run_seed_sweep creates itself holds unless **cfg overrides them -- known here
+# so that per-seed bounds are checked against the other side before a handle exists (tests/test_sweep_features_host.py holds them to the library's)
+DEFAULT_BOUNDS = dict(bx_lo=(-7.0, -7.0, -10.0, -10.0), bx_hi=(7.0, 7.0, 10.0, 10.0), bu_lo=(-8.0, -8.0), bu_hi=(8.0, 8.0))
+
+
+def ring_model(schedule_start, capacity, every):
+    """Which seeds a sweep's ring serves, as a pure-numpy model of mpc_episode_ring_fill_dev.  schedule_start[k]: the control step at which seed index k starts
+    (refill_schedule's `start`, run_seed_sweep's schedule[:, 1]); capacity: ring entries; every: the ring is filled in front of the refill of the control steps
+    t % every == 0.  The fill at step t_f seeds the indices [handed(t_f), handed(t_f) + capacity), handed(t) being the number of seeds started before t; so seed
+    k, started at step t, is served from the ring when k < handed(t_f) + capacity with t_f the last fill step <= t, and seeds in place otherwise.
+    Returns int32 (count,): 1 ring, 0 in place -- run_seed_sweep's `seed_src`."""
+    start = np.asarray(schedule_start)
+    if start.ndim != 1 or (start.size and (start < 0).any()):
+        raise ValueError("schedule_start must be a 1-d array of control steps >= 0")
+    if int(capacity) < 1 or int(every) < 1:
+        raise ValueError("capacity and every must be >= 1")
+    start = start.astype(np.int64)
+    t_f = (start // int(every)) * int(every)
+    handed = np.searchsorted(np.sort(start), t_f, side="left")          # seeds started before t_f
+    return (np.arange(start.size) < handed + int(capacity)).astype(np.int32)
+
+
+def _sweep_features(count, n_obst, handle_cfg, r_safe=None, r_hit=None, W=None, We=None, active=None, margin_all=False, bounds=None, status_log=False,
+                    ring=None, ring_every=None, poll_every=25):
+    """run_seed_sweep's per-seed arguments, checked on the host by the setters' own rules before anything touches a device.  handle_cfg: an object with the
+    handle's bx_lo, bx_hi, bu_lo, bu_hi (an MpcConfig, or a dict over DEFAULT_BOUNDS).  Returns dict(W, We, r_safe, r_hit (float64 (count, .) or None),
+    mask (int32 words (count,) or None), bounds (float64 (count, 12) or None), margin_all, status_log, ring (capacity or None), ring_every)."""
+    out = dict(margin_all=bool(margin_all), status_log=bool(status_log))
+    for name, a, cols, low, open_ in (("W", W, 6, 0.0, False), ("We", We, 4, 0.0, False), ("r_safe", r_safe, n_obst, 0.0, True), ("r_hit", r_hit, n_obst, 0.0, True)):
+        if a is not None:
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 1 and name in ("r_safe", "r_hit"):
+                a = np.repeat(a[:, None], n_obst, axis=1)
+            if a.ndim != 2 or a.shape[1] != cols:
+                raise ValueError(f"{name} must be (count, {cols})" + (" or (count,)" if name in ("r_safe", "r_hit") else "") + f", got {a.shape}")
+            if a.shape[0] != count:
+                raise ValueError(f"per-seed {name} has {a.shape[0]} rows for {count} seeds")
+            if not np.isfinite(a).all() or not ((a > low) if open_ else (a >= low)).all():
+                raise ValueError(f"per-seed {name} must be finite and " + ("> 0" if open_ else ">= 0"))
+            a = np.ascontiguousarray(a)
+        out[name] = a
+    out["mask"] = None
+    if active is not None:
+        a = np.asarray(active)
+        if a.ndim != 2 or a.shape[1] != n_obst:
+            raise ValueError(f"active must be (count, {n_obst}), got {a.shape}: a mask has no bit at or above n_obst")
+        if a.shape[0] != count:
+            raise ValueError(f"per-seed active has {a.shape[0]} rows for {count} seeds")
+        out["mask"] = pack_obstacle_mask(a).view(np.int32)
+    out["bounds"] = None
+    if bounds is not None:
+        if not isinstance(bounds, dict) or set(bounds) - {n for n, _, _ in BOUNDS_ROW}:
+            raise ValueError("bounds must be a dict with keys among bx_lo, bx_hi, bu_lo, bu_hi")
+        given = {n: v for n, v in bounds.items() if v is not None}
+        if not given:
+            raise ValueError("bounds names no group")
+        for n, v in given.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim == 2 and v.shape[0] != count:
+                raise ValueError(f"per-seed {n} has {v.shape[0]} rows for {count} seeds")
+            if not np.isfinite(v).all():
+                raise ValueError(f"bounds: {n} entries must be finite")
+        get = (lambda n: handle_cfg[n]) if isinstance(handle_cfg, dict) else (lambda n: list(getattr(handle_cfg, n)))
+        own = type("Cfg", (), {n: get(n) for n, _, _ in BOUNDS_ROW})
+        tab = pack_instance_bounds(own, count, **given)
+        at = {n: (c0, c) for n, c0, c in BOUNDS_ROW}
+        for lo, hi in (("bu_lo", "bu_hi"), ("bx_lo", "bx_hi")):
+            if not (tab[:, at[lo][0]:at[lo][0] + at[lo][1]] < tab[:, at[hi][0]:at[hi][0] + at[hi][1]]).all():
+                raise ValueError(f"bounds: {lo} must be below {hi} in every component (against the handle's value where one side is missing)")
+        out["bounds"] = tab
+    if ring is not None and (isinstance(ring, bool) or int(ring) != ring or int(ring) < 1):
+        raise ValueError("ring must be None (off) or a capacity >= 1")
+    ring_every = poll_every if ring_every is None else ring_every
+    if int(ring_every) != ring_every or int(ring_every) < 1:
+        raise ValueError("ring_every must be a whole number >= 1")
+    out["ring"] = None if ring is None else int(ring); out["ring_every"] = int(ring_every)
+    return out
+
+
 def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True, init_guess_when_error=True,
-                   bug_compat_alias=True, interpolate_init=False, sqp=None, device=0, solver=None, poll_every=25, **cfg):
+                   bug_compat_alias=True, interpolate_init=False, sqp=None, device=0, solver=None, poll_every=25, r_safe=None, r_hit=None, W=None, We=None,
+                   active=None, margin_all=False, bounds=None, status_log=False, ring=None, ring_every=None, **cfg):
     """experiments.py:20-36 for MORE SEEDS THAN SLOTS: the seeds stream through min(slots, count) slots, and a slot whose episode has ended (goal reached,
     robot_ocp_problem.py:247-250, or max_iter control steps spent) starts the next seed on the device, in front of the next fused control step
     (mpc_episode_refill_dev: no host read, no gather, every slot stays live until the seeds run out).  Seed index k is instance k of
@@ -277,15 +357,30 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
     poll_every: every poll_every control steps the live-slot count goes to pinned host memory behind an event, and is looked at one poll later (the queue
     never drains, and the loop ends at most two polls behind the last episode -- on idle slots); 1: after every refill, blocking, which also records the
     schedule.  The loop launches at most ceil(count / slots) * max_iter + poll_every control steps whatever the device returns.
+    PER SEED, as run_episodes takes them per instance (row k belongs to seed index k; the refill copies it into the slot that starts k, mpc_set_refill_tables_dev;
+    validated here by the setters' rules before anything touches a device): r_safe, r_hit (count, n_obst) or (count,) -- r_hit defaults to
+    r_safe - (cfg.r_safe - 1.2); W (count, 6), We (count, 4) cost weights; active bool (count, n_obst) with margin_all; bounds dict(bx_lo=, bx_hi=, bu_lo=,
+    bu_hi=) of (count, 4) / (count, 2) rows or one row for all.  The feature kernels run one instance per wavefront, so the rows are those of
+    run_episodes on one batch with the same arrays, bit for bit.
+    status_log: per seed, how many of its solves ended with status 2 / status 4 and its first control step with a status != 0 (-1: none), counted on the
+    device behind every fused step (mpc_episode_status_log_dev) -- `status2`, `status4`, `first_bad`, as run_episodes(status_log=True) returns them.
+    ring: None (off, the default) or the capacity of a ring of seeded episodes (mpc_episode_ring_dev): every ring_every control steps (default poll_every;
+    step 0 included) ONE launch seeds the next `ring` seed indices, and a slot that starts a seed copies its generator state and obstacle draw from the ring
+    instead of seeding numpy's generator serially inside the refill.  The ring is a cache validated by tags: an index it does not hold is seeded in place,
+    and the rows are those of the sweep without a ring, bit for bit.
     Returns dict(table (count, 6), x_last (count, 5), steps_run, solves, schedule): table as run_episodes builds it; steps_run the fused steps
     launched -- with T = refill_schedule(table[:, 4] + table[:, 1], slots)["steps"] that is T for poll_every = 1 and (ceil(T / poll_every) + 1) * poll_every
     otherwise (capped by the loop bound); schedule (count, 2) = slot and control step at
-    which each seed started (poll_every = 1; None otherwise), which is refill_schedule's slot / start.
-    Not offered: record, status_log, per-instance radii / masks / bounds (they need per-seed tables), host noise, PipelinedMpc."""
-    not_offered = sorted(set(cfg) & {"record", "status_log", "r_safe", "r_hit", "active", "margin_all", "bounds", "noise", "seed", "first_seed", "compact_from"})
+    which each seed started (poll_every = 1; None otherwise), which is refill_schedule's slot / start.  With status_log: status2, status4, first_bad (count,).
+    With ring and poll_every = 1: seed_src (count,) = 1 where the seed came from the ring, 0 where it was seeded in place = ring_model(schedule[:, 1], ring, ring_every).
+    Not offered: record, a per-seed stage reference, host noise, PipelinedMpc."""
+    not_offered = sorted(set(cfg) & {"record", "noise", "seed", "first_seed", "compact_from"})
     if not_offered:
         raise TypeError(f"run_seed_sweep has no argument {not_offered[0]!r}: it is run_episodes' (a sweep would need it per seed)")
     first, count, start, goal, per_seed = _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every)
+    handle_cfg = solver.cfg if solver is not None else {n: tuple(cfg.get(n, v)) for n, v in DEFAULT_BOUNDS.items()}
+    ft = _sweep_features(count, solver.n_obst if solver is not None else int(n_obst), handle_cfg, r_safe=r_safe, r_hit=r_hit, W=W, We=We, active=active,
+                         margin_all=margin_all, bounds=bounds, status_log=status_log, ring=ring, ring_every=ring_every, poll_every=poll_every)
     import torch
     S = min(int(slots), count); max_iter = int(max_iter); poll_every = int(poll_every)
     if interpolate_init and bug_compat_alias:
@@ -298,6 +393,8 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
     if sqp is not None:
         m.set_sqp(*sqp)
     stream = torch.cuda.Stream(device=dev)
+    own_params = any(ft[n] is not None for n in ("W", "We", "r_safe", "r_hit"))
+    own_mask, own_bounds, own_tables = ft["mask"] is not None, ft["bounds"] is not None, False
     with torch.cuda.stream(stream):
         f64 = dict(dtype=torch.float64, device=dev); i32 = dict(dtype=torch.int32, device=dev)
         dstart, dgoal_rows = torch.from_numpy(start).to(dev), torch.from_numpy(goal).to(dev)
@@ -314,51 +411,109 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
         fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS
         if init_guess_when_error:
             fl |= _lib.STEP_RESET_ON_FAIL | (_lib.STEP_ALIAS_BUG if bug_compat_alias else 0) | (_lib.STEP_INTERP_GUESS if interpolate_init else 0)
+        if own_mask and ft["margin_all"]:
+            fl |= _lib.STEP_MARGIN_ALL
         rf = (_lib.REFILL_ALIAS_BUG if bug_compat_alias else 0) | (_lib.REFILL_INTERP_GUESS if interpolate_init else 0) | (_lib.REFILL_DRAW_NOISE if random_move else 0)
+        # per-seed tables: the sources (count rows) and the per-slot arrays the solve reads in place (max_batch rows, preset with the handle's own values: a
+        # slot that never gets a seed holds valid numbers), registered with the _dev setters; the refill copies row k into the slot that starts k
+        MB = m.max_batch
+        tabs = {}
+        if own_params:
+            r_hit_own = 1.0 + 0.2                               # o.r + R_ROBOT: the fused step's hit radius (mpc_closed_loop_step_dev)
+            preset = dict(W=list(m.cfg.W), We=list(m.cfg.We), r_safe=[m.cfg.r_safe] * n_obst, r_hit=[r_hit_own] * n_obst)
+            slot = {}
+            for name in ("W", "We", "r_safe", "r_hit"):
+                if ft[name] is not None:
+                    tabs[name] = torch.from_numpy(ft[name]).to(dev)
+                    slot[name] = tabs["slot_" + name] = torch.tensor(preset[name], **f64).repeat(MB, 1).contiguous()
+            m.set_instance_params(W=slot.get("W"), We=slot.get("We"), r_safe=slot.get("r_safe"), r_hit=slot.get("r_hit"))
+        if own_mask:
+            tabs["mask"] = torch.from_numpy(ft["mask"].copy()).to(dev)
+            tabs["slot_mask"] = torch.full((MB,), int(np.array([(1 << n_obst) - 1], dtype=np.uint32).view(np.int32)[0]), **i32)
+            m.set_obstacle_mask(tabs["slot_mask"])
+        if own_bounds:
+            tabs["bounds"] = torch.from_numpy(ft["bounds"]).to(dev)
+            tabs["slot_bounds"] = torch.from_numpy(pack_instance_bounds(m.cfg, MB)).to(dev)
+            m.set_instance_bounds_dev(tabs["slot_bounds"])
+        if ft["status_log"]:
+            tabs["log"] = torch.tensor([0, 0, -1, 0], **i32).repeat(S, 1).contiguous()
+            tabs["res_log"] = torch.full((count, 3), -1, **i32)
+        if tabs:
+            m.set_refill_tables_dev(**tabs); own_tables = True
+        ring_cap, ring_every = ft["ring"], ft["ring_every"]
+        seed_src = None
+        if ring_cap is not None:
+            ring_state = torch.zeros(ring_cap, gen_state.shape[1], **i32); ring_obst = torch.zeros(ring_cap, n_obst, 4, **f64)
+            ring_tag = torch.full((ring_cap,), -1, **i32); seed_src = torch.full((count,), -1, **i32)
+            m.episode_ring_dev(ring_cap, ring_state, ring_obst, ring_tag, seed_src)
         bound = -(-count // S) * max_iter + poll_every
         schedule = np.full((count, 2), -1, dtype=np.int64) if poll_every == 1 else None
         seen = np.full(S, -1, dtype=np.int64)
         live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
         live_event = None
         k = 0
-        while True:
-            m.episode_refill_dev(S, scenario, first, count, max_iter, dstart, dgoal_rows, per_seed, dx0, dobst, dgoal, X, U, margin, flags, steps,
-                                 gen_state, nbuf, slot_seed, cursor, res_f, res_i, flags=rf, stream=s)
-            if poll_every == 1:
-                now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
-                new = (now != seen) & (now >= 0)
-                schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
-                seen = now
-                if int(cursor[1].item()) == 0:
-                    break
-            elif k % poll_every == 0:
-                # the count of the poll before this one, which the device passed long ago: the host stays at most two polls ahead of the device (no idle
-                # steps by the hundred behind the end of the sweep) and the device always has a poll's worth of steps queued (it never waits for the host)
-                if live_event is not None:
-                    live_event.synchronize()
-                    if int(live_host[0]) == 0:
+        try:
+            while True:
+                if ring_cap is not None and k % ring_every == 0:
+                    m.episode_ring_fill_dev(scenario, first, count, cursor, stream=s)
+                m.episode_refill_dev(S, scenario, first, count, max_iter, dstart, dgoal_rows, per_seed, dx0, dobst, dgoal, X, U, margin, flags, steps,
+                                     gen_state, nbuf, slot_seed, cursor, res_f, res_i, flags=rf, stream=s)
+                if poll_every == 1:
+                    now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
+                    new = (now != seen) & (now >= 0)
+                    schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
+                    seen = now
+                    if int(cursor[1].item()) == 0:
                         break
-                live_host.copy_(cursor[1:2], non_blocking=True)
-                live_event = torch.cuda.Event(); live_event.record(stream)
-            if k >= bound:
-                break
-            m.closed_loop_step_dev(S, dx0, dobst, dgoal, X, U, None, None, status, iters, nbuf, flags=fl,
-                                   min_margin=margin, ep_flags=flags, ep_steps=steps, stream=s)
-            k += 1
-        stream.synchronize()
-        left = int(cursor[1].item())
-        ri = res_i.cpu().numpy(); rfh = res_f.cpu().numpy()
+                elif k % poll_every == 0:
+                    # the count of the poll before this one, which the device passed long ago: the host stays at most two polls ahead of the device (no idle
+                    # steps by the hundred behind the end of the sweep) and the device always has a poll's worth of steps queued (it never waits for the host)
+                    if live_event is not None:
+                        live_event.synchronize()
+                        if int(live_host[0]) == 0:
+                            break
+                    live_host.copy_(cursor[1:2], non_blocking=True)
+                    live_event = torch.cuda.Event(); live_event.record(stream)
+                if k >= bound:
+                    break
+                m.closed_loop_step_dev(S, dx0, dobst, dgoal, X, U, None, None, status, iters, nbuf, flags=fl,
+                                       min_margin=margin, ep_flags=flags, ep_steps=steps, stream=s)
+                if ft["status_log"]:
+                    m.episode_status_log_dev(S, status, flags, steps, tabs["log"], stream=s)
+                k += 1
+            stream.synchronize()
+            left = int(cursor[1].item())
+            ri = res_i.cpu().numpy(); rfh = res_f.cpu().numpy()
+            extra = {}
+            if ft["status_log"]:
+                rl = tabs["res_log"].cpu().numpy()
+                extra.update(status2=rl[:, 0].copy(), status4=rl[:, 1].copy(), first_bad=rl[:, 2].copy())
+            if ring_cap is not None and poll_every == 1:
+                extra["seed_src"] = seed_src.cpu().numpy()
+        finally:
+            stream.synchronize()
+            if solver is not None:           # (a caller's solver leaves as it came; the handle holds pointers into this call's tensors)
+                if own_tables:
+                    m.set_refill_tables_dev()
+                if ring_cap is not None:
+                    m.episode_ring_dev(0)
+                if own_params:
+                    m.set_instance_params()
+                if own_mask:
+                    m.set_obstacle_mask(None)
+                if own_bounds:
+                    m.set_instance_bounds_dev(None)
+                if sqp is not None:
+                    m.set_sqp()
     if solver is None:
         m.close()
-    elif sqp is not None:            # (a caller's solver leaves as it came)
-        m.set_sqp()
     if left != 0 or (ri[:, 0] < 0).any():
         raise _lib.MpcError(f"the sweep did not drain within {bound} control steps ({left} slots live, {int((ri[:, 0] < 0).sum())} rows not parked)")
     fl_h, st_h, xl = ri[:, 0], ri[:, 1], np.ascontiguousarray(rfh[:, 1:6])
     goal_all = np.ascontiguousarray(np.broadcast_to(goal, (count, 2)), dtype=np.float64)
     table = np.column_stack([(fl_h & 4) != 0, (fl_h & 1) != 0, rfh[:, 0],
                              np.linalg.norm(xl[:, :2] - goal_all, axis=1), st_h, (fl_h & 2) != 0]).astype(np.float64)
-    return dict(table=table, x_last=xl, steps_run=k, solves=int(st_h.sum()) + int((fl_h & 1).sum()), schedule=schedule)
+    return dict(table=table, x_last=xl, steps_run=k, solves=int(st_h.sum()) + int((fl_h & 1).sum()), schedule=schedule, **extra)
 
 
 def visualisation_inputs(rec, instance, steps=None):

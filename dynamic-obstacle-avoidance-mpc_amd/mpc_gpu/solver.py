@@ -376,6 +376,37 @@ class BatchedMpc:
                                                      _ptr(U), _ptr(min_margin), _ptr(ep_flags), _ptr(ep_steps), _ptr(state), _ptr(noise), _ptr(slot_seed),
                                                      _ptr(cursor), _ptr(res_f), _ptr(res_i), _ptr(stream)))
 
+    def set_refill_tables_dev(self, W=None, We=None, r_safe=None, r_hit=None, mask=None, bounds=None, slot_W=None, slot_We=None, slot_r_safe=None,
+                              slot_r_hit=None, slot_mask=None, slot_bounds=None, log=None, res_log=None):
+        """Per-seed tables and the status log of a sweep (include/mpc_gpu.h mpc_set_refill_tables_dev), device tensors used in place: when seed index k
+        starts in slot s, episode_refill_dev copies row k of every source given (W (count, 6), We (count, 4), r_safe / r_hit (count, n_obst), mask (count,)
+        int32 words, bounds (count, 12)) into row s of its slot_ destination -- the per-slot tensor registered with set_instance_params /
+        set_obstacle_mask / set_instance_bounds_dev -- resets log[s] (slots, 4) and parks it under the old seed in res_log (count, 3).  Nothing is validated
+        here beyond source / destination pairing (the library's); all None switches off."""
+        given = dict(W=W, We=We, r_safe=r_safe, r_hit=r_hit, mask=mask, bounds=bounds, slot_W=slot_W, slot_We=slot_We, slot_r_safe=slot_r_safe,
+                     slot_r_hit=slot_r_hit, slot_mask=slot_mask, slot_bounds=slot_bounds, log=log, res_log=res_log)
+        if all(a is None for a in given.values()):
+            _lib.check(_lib.lib().mpc_set_refill_tables_dev(self._h, None))
+            return
+        t = _lib.RefillTables(**{n: _ptr(a) for n, a in given.items()})
+        _lib.check(_lib.lib().mpc_set_refill_tables_dev(self._h, C.byref(t)))
+
+    def episode_status_log_dev(self, slots, status, ep_flags, ep_steps, log, stream=None):
+        """behind closed_loop_step_dev on the same stream: counts the step's status words into log (slots, 4) = n2, n4, first_bad, seen per slot
+        (include/mpc_gpu.h mpc_episode_status_log_dev)"""
+        _lib.check(_lib.lib().mpc_episode_status_log_dev(self._h, int(slots), _ptr(status), _ptr(ep_flags), _ptr(ep_steps), _ptr(log), _ptr(stream)))
+
+    def episode_ring_dev(self, capacity, ring_state=None, ring_obst=None, ring_tag=None, seed_src=None):
+        """attach a ring of `capacity` seeded episodes to the refill (include/mpc_gpu.h mpc_episode_ring_dev): ring_state (capacity, noise state words) int32,
+        ring_obst (capacity, n_obst, 4), ring_tag (capacity,) int32 preset to -1, seed_src (count,) int32 or None; capacity 0 detaches"""
+        _lib.check(_lib.lib().mpc_episode_ring_dev(self._h, int(capacity), _ptr(ring_state), _ptr(ring_obst), _ptr(ring_tag), _ptr(seed_src)))
+
+    def episode_ring_fill_dev(self, scenario, seed_first, seed_count, cursor, stream=None):
+        """one fill of the attached ring, in front of episode_refill_dev on the same stream: seeds the entries of the next `capacity` seed indices behind
+        cursor[0] that the ring does not hold yet (include/mpc_gpu.h mpc_episode_ring_fill_dev)"""
+        box = self._scenario_box()
+        _lib.check(_lib.lib().mpc_episode_ring_fill_dev(self._h, self.SCENARIOS[scenario], int(seed_first), int(seed_count), _ptr(box), _ptr(cursor), _ptr(stream)))
+
     # ------------------------------------------------------------------ multi-GPU: all-gather of the costs, RCCL called by the library itself
     @staticmethod
     def comm_unique_id():

@@ -325,6 +325,58 @@ int mpc_episode_refill_dev(mpc_handle *h, int slots, int scenario, unsigned seed
                            const double *d_start, const double *d_goal_rows, int per_seed, double *d_x0, double *d_obst, double *d_goal, double *d_X,
                            double *d_U, double *d_min_margin, int32_t *d_ep_flags, int32_t *d_ep_steps, uint32_t *d_state, double *d_noise,
                            int32_t *d_slot_seed, int32_t *d_cursor, double *d_res_f, int32_t *d_res_i, void *stream);
+/* SEED SWEEPS, PER SEED: feature tables, a status log and a ring of seeded episodes.  All three are additive, off until set, and change neither the
+ * prototype nor the meaning of mpc_episode_refill_dev: a handle on which none of the calls below was made launches exactly what it launched before.
+ *
+ * PER-SEED TABLES (mpc_set_refill_tables_dev).  The per-instance features -- cost weights and radii (mpc_set_instance_params_dev), obstacle masks
+ * (mpc_set_obstacle_mask_dev), box bounds (mpc_set_instance_bounds_dev) -- read PER-SLOT device arrays in place when a solve is launched.  A sweep varies
+ * them PER SEED: give the per-seed source (row k = seed index k) and the per-slot destination (row s = slot s: the very array registered with the _dev
+ * setter), and the refill's apply launch copies row k of every source that is given into row s of its destination when seed index k starts in slot s.
+ *   sources, each optional (NULL):  W[seed_count][6], We[seed_count][4], r_safe[seed_count][n_obst], r_hit[seed_count][n_obst], mask[seed_count] (uint32),
+ *                                   bounds[seed_count][12] (the packed row of mpc_set_instance_bounds_dev: bu_lo[2], bu_hi[2], bx_lo[4], bx_hi[4]);
+ *   destinations:                   slot_W[slots][6], ... slot_bounds[slots][12] -- a source without its destination is MPC_ERR_ARG, naming the field.
+ * Slots that are kept or drained are not touched, so PRESET the destinations with valid values (the handle's own): a slot that never gets a seed is
+ * still solved by the fused step.  Nothing is validated on the device: the sources hold what the host setters would accept (finite, weights >= 0,
+ * radii > 0, lo < hi, no mask bit at or above n_obst).
+ *
+ * STATUS LOG.  log[slots][4] (int32: n2, n4, first_bad, seen) and res_log[seed_count][3], both or neither.  The apply launch resets
+ * log[s] = {0, 0, -1, 0} when a seed starts in slot s and parks log[s][0..2] under the slot's old seed index beside its result row; behind every fused
+ * step, on the same stream, mpc_episode_status_log_dev counts (one thread per slot): with now = ep_steps[s] + (ep_flags[s] & 1), if now > seen the slot
+ * solved at episode step `seen` -- status 2 counts into n2, status 4 into n4, first_bad = seen if the status is nonzero and first_bad is still -1 --
+ * and seen = now.  res_log[k] is then {solves of seed k that ended with status 2, with status 4, its first control step with a status != 0 or -1}.
+ *
+ * Every word the apply launch writes still belongs to its own slot or its own seed.  mpc_set_refill_tables_dev(h, NULL) switches tables and log off.
+ * The struct holds device pointers only and is copied by the call.
+ *
+ * RING OF SEEDED EPISODES (mpc_episode_ring_dev, mpc_episode_ring_fill_dev), opt-in.  Seeding numpy's generator is ~2000 dependent integer steps that
+ * one thread runs for every slot that starts a seed; the ring takes them out of the refill: it is seeded many entries at a time, every few control
+ * steps, and a slot that starts a seed copies an entry.  Entries are VALIDATED BY TAGS; the ring is a cache and never a condition of correctness.
+ *   attach: d_ring_state[capacity][mpc_noise_state_words()], d_ring_obst[capacity][n_obst][4], d_ring_tag[capacity] (preset to -1 by the caller),
+ *     d_seed_src (int32[seed_count], or NULL).  capacity 0 detaches.  The arrays are the caller's and are used in place.
+ *   fill: ONE launch, one thread per entry e, in front of the refill on the same stream.  With handed = d_cursor[0], thread e owns the one index k in
+ *     [handed, handed + capacity) with k % capacity == e; if k < seed_count and tag[e] != k it seeds seed_first + k into ring_state[e], takes the
+ *     scenario's draws into ring_obst[e] -- the refill's own sequence, so the state is mpc_noise_init_dev's -- and writes tag[e] = k LAST.  An entry is
+ *     overwritten only by k + capacity, which is owned only once k has been handed out.  Call it every few control steps, not every step.
+ *   apply with a ring attached: a slot that starts k copies state and obstacle row of entry k % capacity when its tag is k, and seeds in place, as
+ *     without a ring, otherwise.  d_seed_src[k] = 1 (ring) or 0 (seeded in place).
+ *   refusal: the handle remembers scenario, seed_first, seed_count and box of the last fill; while a ring is attached, a refill whose values differ is
+ *     MPC_ERR_ARG and launches nothing (an entry seeded for another sweep would carry a matching tag).  Attaching forgets them.
+ * No atomics, no spinning, no grid-wide synchronisation; no thread reads a word that another thread of the same launch writes. */
+typedef struct mpc_refill_tables {
+    const double *W, *We, *r_safe, *r_hit;                     /* per-seed sources */
+    const uint32_t *mask;
+    const double *bounds;
+    double *slot_W, *slot_We, *slot_r_safe, *slot_r_hit;       /* per-slot destinations */
+    uint32_t *slot_mask;
+    double *slot_bounds;
+    int32_t *log;                                              /* [slots][4] */
+    int32_t *res_log;                                          /* [seed_count][3] */
+} mpc_refill_tables;
+int mpc_set_refill_tables_dev(mpc_handle *h, const mpc_refill_tables *t);
+int mpc_episode_status_log_dev(mpc_handle *h, int slots, const int32_t *d_status, const int32_t *d_ep_flags, const int32_t *d_ep_steps, int32_t *d_log,
+                               void *stream);
+int mpc_episode_ring_dev(mpc_handle *h, int capacity, uint32_t *d_ring_state, double *d_ring_obst, int32_t *d_ring_tag, int32_t *d_seed_src);
+int mpc_episode_ring_fill_dev(mpc_handle *h, int scenario, unsigned seed_first, int seed_count, const double *box, const int32_t *d_cursor, void *stream);
 /* MULTI-GPU: one process per GPU, every rank solves its own contiguous slice of the scenarios (the reference's 13 000 closed
  * loops, experiments.py:20-36, are independent), and the only exchange is an all-gather of the per-instance costs -- RCCL over xGMI, called directly
  * from this library (librccl.so.1 is loaded on first use; there is no link-time dependency and no other transport).  A C host does:

@@ -14,6 +14,17 @@ Per-step overhead (HIP events on the step's stream, median of --launches single 
 with one slot refilled and with every slot refilled, each with and without the noise draw; mpc_noise_draw_dev alone; the fused step.
 
     python scripts/sweep_rate.py [--seeds 16384] [--slots 1024] [--reps 3] [--launches 30] [--out profiles/sweep_rates.json]
+
+--ring-forms measures the per-seed features instead and writes profiles/sweep_ring_rates.json (profiles/sweep_rates.json is left alone): at every slot count
+of --slot-counts (default 1024,4096) the forms
+  "baseline":   run_seed_sweep of ANOTHER CHECKOUT (--baseline-root DIR, built there; its package and library are loaded beside this one, so the forms
+                alternate in one process) -- the parent commit's sweep; left out without the option;
+  "off":        run_seed_sweep with everything off: must equal "baseline" within the spread;
+  "ring":       ring on, capacity = slots, ring_every = 25;
+  "features":   per-seed radii + mask + bounds;
+  "all":        every per-seed table, the status log and the ring;
+the same protocol (a warm-up, then --reps runs per form, the forms alternating), and the per-call table for the refill with ONE slot refilled, ring on
+against ring off, the ring fill and the status log kernel.
 """
 import argparse
 import json
@@ -27,8 +38,123 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
 
 
+def load_baseline(root):
+    """the mpc_gpu package of another checkout under its own module name: its own Python, its own libmpcgpu.so (built there beforehand)"""
+    import importlib.util
+    pkg = os.path.join(root, "dynamic-obstacle-avoidance-mpc_amd", "mpc_gpu")
+    spec = importlib.util.spec_from_file_location("mpc_gpu_baseline", os.path.join(pkg, "__init__.py"), submodule_search_locations=[pkg])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["mpc_gpu_baseline"] = mod
+    spec.loader.exec_module(mod)
+    if not os.path.exists(mod._lib.LIB_PATH):
+        raise SystemExit(f"{mod._lib.LIB_PATH} is missing: build the baseline checkout first")
+    return mod
+
+
+def ring_forms(a):
+    import torch
+    import mpc_gpu
+    import sweep_cases as sc
+    import sweep_feature_cases as fc
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this script measures on the device only")
+    L = mpc_gpu._lib
+    E, scen = a.seeds, a.scenario
+    prob = dict(sc.PROBLEM, max_iter=400)
+    base = load_baseline(a.baseline_root) if a.baseline_root else None
+    feat = fc.feature_kwargs("all", E)
+    some = {n: feat[n] for n in ("r_safe", "r_hit", "active", "bounds")}
+    out = dict(workload=dict(scenario=scen, seeds=E, reps=a.reps, ring_every=25, **prob), by_slots={})
+    for S in [int(x) for x in a.slot_counts.split(",")]:
+        forms = {}
+        if base is not None:
+            forms["baseline"] = lambda: base.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **prob)
+        forms["off"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **prob)
+        forms["ring"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, ring=S, ring_every=25, **prob)
+        forms["features"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **some, **prob)
+        forms["all"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, ring=S, ring_every=25, status_log=True, **feat, **prob)
+        times, last = {f: [] for f in forms}, {}
+        for rep in range(a.reps + 1):               # rep 0: warm-up of every form
+            for f, fn in forms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                last[f] = fn()
+                torch.cuda.synchronize()
+                if rep:
+                    times[f].append(time.perf_counter() - t0)
+                print(json.dumps(dict(slots=S, rep=rep, form=f, seconds=time.perf_counter() - t0, steps_run=last[f]["steps_run"])), flush=True)
+        res = {}
+        for f in forms:
+            ts = np.array(times[f])
+            res[f] = dict(seconds=[float(t) for t in ts], median_s=float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
+                          episodes_per_s=float(E / np.median(ts)), fused_steps=int(last[f]["steps_run"]), ms_per_step=float(1e3 * np.median(ts) / last[f]["steps_run"]))
+        spread = max(r["spread"] for r in res.values())
+        summary = dict(largest_spread=spread, ring_over_off=res["ring"]["median_s"] / res["off"]["median_s"],
+                       ring_faster_than_off_beyond_spread=bool(res["ring"]["median_s"] < res["off"]["median_s"] * (1 - spread)),
+                       features_over_off=res["features"]["median_s"] / res["off"]["median_s"], all_over_off=res["all"]["median_s"] / res["off"]["median_s"],
+                       ring_rows_equal_off=bool(np.array_equal(last["ring"]["table"], last["off"]["table"])))
+        if base is not None:
+            summary.update(off_over_baseline=res["off"]["median_s"] / res["baseline"]["median_s"],
+                           off_equals_baseline_within_spread=bool(abs(res["off"]["median_s"] / res["baseline"]["median_s"] - 1) <= spread),
+                           off_rows_equal_baseline=bool(np.array_equal(last["off"]["table"], last["baseline"]["table"])))
+        out["by_slots"][str(S)] = dict(forms=res, summary=summary)
+        print(json.dumps({str(S): out["by_slots"][str(S)]}), flush=True)
+
+    # ---- the per-call table: ONE slot refilled, ring on against ring off; the ring fill; the status log
+    S = int(a.slot_counts.split(",")[0])
+    dev = torch.device("cuda", 0)
+    over = {}
+    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        st = torch.cuda.current_stream(); cs = st.cuda_stream
+        plain = sc.Plain(torch, dev)
+        arr = sc.SlotArrays(plain, m, S, E, L.lib().mpc_noise_state_words())
+        words = L.lib().mpc_noise_state_words()
+        ring_state, ring_obst = plain.i32(S, words), plain.f64(S, m.n_obst, 4)
+        ring_tag, seed_src, log = plain.i32(S, init=-1), plain.i32(E, init=-1), plain.i32(S, 4)
+        step_flags = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES | L.STEP_METRICS | L.STEP_RESET_ON_FAIL | L.STEP_ALIAS_BUG
+        fl = L.REFILL_ALIAS_BUG | L.REFILL_DRAW_NOISE
+
+        def timed(fn, before=None):
+            ms = []
+            for _ in range(a.launches):
+                if before:
+                    before()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st); fn(); e1.record(st)
+                st.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            return dict(median_us=1e3 * float(np.median(ms)), min_us=1e3 * float(np.min(ms)), max_us=1e3 * float(np.max(ms)))
+
+        for _ in range(10):                     # a few control steps in: every slot runs
+            arr.refill(m, scen, 0, 400, fl, cs); arr.step(m, step_flags, cs)
+        st.synchronize()
+        assert int((arr.flags & 1).sum().item()) == 0
+        one = lambda: arr.flags[S // 2:S // 2 + 1].fill_(1)
+        over["refill_one_slot_ring_off"] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs), before=one)
+        over["refill_nothing_finished_ring_off"] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs))
+        m.episode_ring_dev(S, ring_state, ring_obst, ring_tag, seed_src)
+        over["ring_fill_every_entry"] = timed(lambda: m.episode_ring_fill_dev(scen, 0, E, arr.cursor, stream=cs), before=lambda: ring_tag.fill_(-1))
+        over["ring_fill_nothing_to_seed"] = timed(lambda: m.episode_ring_fill_dev(scen, 0, E, arr.cursor, stream=cs))
+        over["refill_one_slot_ring_on"] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs), before=one)
+        st.synchronize()
+        over["refill_one_slot_ring_on_hits"] = int((seed_src == 1).sum().item())          # (every timed refill found its index in the ring)
+        over["refill_one_slot_ring_on_misses"] = int((seed_src == 0).sum().item())
+        over["refill_nothing_finished_ring_on"] = timed(lambda: arr.refill(m, scen, 0, 400, fl, cs))
+        over["status_log"] = timed(lambda: m.episode_status_log_dev(S, arr.status, arr.flags, arr.steps, log, stream=cs))
+        m.episode_ring_dev(0)
+    out["per_call"] = dict(slots=S, launches=a.launches, **over)
+    print(json.dumps(dict(per_call=out["per_call"])), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.ring_out)), exist_ok=True)
+    with open(a.ring_out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ring-forms", action="store_true")
+    ap.add_argument("--slot-counts", default="1024,4096")
+    ap.add_argument("--baseline-root", default=None)
+    ap.add_argument("--ring-out", default=os.path.join(ROOT, "profiles", "sweep_ring_rates.json"))
     ap.add_argument("--seeds", type=int, default=16384)
     ap.add_argument("--slots", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
@@ -36,6 +162,8 @@ def main():
     ap.add_argument("--scenario", default="RANDOM")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_rates.json"))
     a = ap.parse_args()
+    if a.ring_forms:
+        return ring_forms(a)
     import torch
     import mpc_gpu
     import sweep_cases as sc
