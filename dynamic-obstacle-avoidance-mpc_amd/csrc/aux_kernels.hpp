@@ -612,6 +612,75 @@ __global__ void status_log_kernel(int slots, const int32_t *__restrict__ status,
     }
 }
 
+// EPISODE TRACE (mpc_episode_trace_set_dev, mpc_episode_trace_dev): what run_episodes(record=True) keeps per experiment -- simX, the obstacle trajectories, the
+// predicted horizons (robot_ocp_problem.py:42-49, 234-241, 270-276) -- for the seeds of a sweep that ask for it, written on the device row by row.  A traced seed
+// index k owns row r = seed_row[k] of every array below (the host hands out distinct rows); slot_state[s] = {seed index the slot is tracing, episode steps seen}.
+// Two launches per control step, because the refill overwrites a finished slot before anything behind it could read its last step:
+//   START, behind the refill: a slot whose seed index differs from slot_state[s].seed has just started it -- the plant and obstacle states are row 0;
+//   STEP, behind the fused step (and the status log): with now = ep_steps + (ep_flags & 1), the status log's "episode steps solved", a slot with now > seen
+//     solved at episode step `seen` -- the states it was left in are row `now`, and u*, status, iterations and the iterate X are row `seen`.
+// One wavefront per slot, four slots per workgroup.  Every lane loads the slot's words first (the same addresses in all 64 lanes: wavefront-uniform), the lanes
+// then stride over the doubles of a row (coalesced on both sides: X[s] is 5 (N + 1) contiguous doubles), and lane 0 writes len and slot_state last.  The refill's
+// rules hold: no atomics, no waiting, bounded loops; every word written belongs to the slot or to the seed's own row; no thread reads a word that another
+// wavefront of the same launch writes (slot_state[s] and len[r] are read and written by the slot's own wavefront only).
+struct TraceArrays {
+    const int32_t *seed_row; int32_t *slot_state, *len;
+    double *x, *obst, *u; int32_t *status, *iters; double *pred;
+    int rows, max_steps;
+};
+constexpr int kTraceThreads = 256, kTraceStart = 0, kTraceStep = 1;
+
+__device__ __forceinline__ void trace_copy_row(double *__restrict__ dst, const double *__restrict__ src, int n, int lane)
+{
+    for (int i = lane; i < n; i += 64) dst[i] = src[i];         // (n <= 5 (N + 1) or 4 n_obst: a handful of rounds)
+}
+
+__global__ __launch_bounds__(kTraceThreads) void episode_trace_kernel(int slots, int phase, int n_obst, int N, TraceArrays t, const int32_t *__restrict__ slot_seed,
+                                                                      const double *__restrict__ x0, const double *__restrict__ obst, const double *__restrict__ X,
+                                                                      const double *__restrict__ u0, const int32_t *__restrict__ status,
+                                                                      const int32_t *__restrict__ iters, const int32_t *__restrict__ ep_flags,
+                                                                      const int32_t *__restrict__ ep_steps)
+{
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * (kTraceThreads / 64) + (threadIdx.x >> 6);
+    if (s >= slots) return;
+    const int k = slot_seed[s];
+    if (k < 0) return;                                          // drained, or never filled
+    const int now = ep_steps[s] + (ep_flags[s] & 1);
+    const int cur = t.slot_state[2 * s], seen = t.slot_state[2 * s + 1];
+    const int r = t.seed_row[k];
+    const bool traced = r >= 0 && r < t.rows;
+    const int ow = 4 * n_obst;
+    const size_t T1 = (size_t)t.max_steps + 1;                  // state rows of a seed
+    if (phase == kTraceStart) {
+        if (k == cur) return;                                   // the slot runs on
+        if (traced && now != 0) {                               // the episode has stepped already: a START call was skipped -- made visible, and nothing else written
+            if (lane == 0) t.len[r] = -1;
+            return;
+        }
+        if (traced) {
+            trace_copy_row(t.x + (size_t)r * T1 * 5, x0 + (size_t)s * 5, 5, lane);
+            trace_copy_row(t.obst + (size_t)r * T1 * ow, obst + (size_t)s * ow, ow, lane);
+            if (lane == 0) t.len[r] = 0;
+        }
+        if (lane == 0) { t.slot_state[2 * s] = k; t.slot_state[2 * s + 1] = 0; }
+        return;
+    }
+    if (k != cur || seen < 0 || now <= seen) return;            // idle, or not started through a START call
+    if (traced && now <= t.max_steps) {                         // (seen < now <= max_steps: every index below is inside the seed's row)
+        const int st = status[s], it = iters[s];
+        trace_copy_row(t.x + ((size_t)r * T1 + now) * 5, x0 + (size_t)s * 5, 5, lane);
+        trace_copy_row(t.obst + ((size_t)r * T1 + now) * ow, obst + (size_t)s * ow, ow, lane);
+        trace_copy_row(t.u + ((size_t)r * t.max_steps + seen) * 2, u0 + (size_t)s * 2, 2, lane);
+        if (t.pred) trace_copy_row(t.pred + ((size_t)r * t.max_steps + seen) * (N + 1) * 5, X + (size_t)s * (N + 1) * 5, (N + 1) * 5, lane);
+        if (lane == 0) {
+            t.status[(size_t)r * t.max_steps + seen] = st; t.iters[(size_t)r * t.max_steps + seen] = it;
+            t.len[r] = now;
+        }
+    }
+    if (lane == 0) t.slot_state[2 * s + 1] = now;
+}
+
 // Plant integrator, robot_ocp_problem.py:207-212.
 __global__ void plant_step_kernel(int batch, double dt, const double *__restrict__ x, const double *__restrict__ u, double *__restrict__ xn)
 {

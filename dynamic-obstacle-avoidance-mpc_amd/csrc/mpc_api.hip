@@ -113,6 +113,8 @@ struct mpc_handle {
     uint32_t *ring_state; double *ring_obst; int32_t *ring_tag, *ring_seed_src;
     bool ring_filled;                 // ... what the last mpc_episode_ring_fill_dev seeded it for: a refill with other values is refused
     int ring_scenario, ring_seed_count; unsigned ring_seed_first; double ring_box[6];
+    int trace_rows, trace_max_steps;  // per-seed trajectories of a sweep (mpc_episode_trace_set_dev): rows, 0 = none attached; the caller's device arrays, used in place
+    mpc_episode_trace trace;
 };
 
 namespace {
@@ -1100,6 +1102,43 @@ int mpc_episode_ring_fill_dev(mpc_handle *h, int scenario, unsigned seed_first, 
     HIPCHK(hipGetLastError());
     h->ring_filled = true; h->ring_scenario = scenario; h->ring_seed_first = seed_first; h->ring_seed_count = seed_count;
     memcpy(h->ring_box, box, sizeof(h->ring_box));
+    return MPC_OK;
+}
+
+int mpc_episode_trace_set_dev(mpc_handle *h, int rows, int max_steps, const mpc_episode_trace *t)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!t || rows == 0) { h->trace_rows = 0; h->trace_max_steps = 0; memset(&h->trace, 0, sizeof(h->trace)); return MPC_OK; }
+    if (rows < 0) return fail(MPC_ERR_ARG, "mpc_episode_trace_set_dev: rows must be >= 0 (0 detaches the trace)");
+    if (max_steps < 1) return fail(MPC_ERR_ARG, "mpc_episode_trace_set_dev: max_steps must be >= 1");
+    const struct { const char *name; const void *p; } need[8] = {{"seed_row", t->seed_row}, {"slot_state", t->slot_state}, {"len", t->len}, {"x", t->x},
+                                                                 {"obst", t->obst}, {"u", t->u}, {"status", t->status}, {"iters", t->iters}};
+    for (const auto &f : need)
+        if (!f.p) return fail(MPC_ERR_ARG, "mpc_episode_trace_set_dev: %s is null (pred alone may be)", f.name);
+    h->trace = *t; h->trace_rows = rows; h->trace_max_steps = max_steps;
+    return MPC_OK;
+}
+
+int mpc_episode_trace_dev(mpc_handle *h, int slots, int phase, const int32_t *d_slot_seed, const double *d_x0, const double *d_obst, const double *d_X,
+                          const double *d_u0, const int32_t *d_status, const int32_t *d_iters, const int32_t *d_ep_flags, const int32_t *d_ep_steps, void *stream)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!h->trace_rows) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: no trace attached (mpc_episode_trace_set_dev)");
+    if (slots < 1 || slots > h->max_batch) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: slots outside [1, max_batch]");
+    if (phase != MPC_TRACE_START && phase != MPC_TRACE_STEP) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: phase must be MPC_TRACE_START (0) or MPC_TRACE_STEP (1)");
+    if (!d_slot_seed || !d_x0 || !d_obst || !d_ep_flags || !d_ep_steps) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: null slot_seed, x0, obst, ep_flags or ep_steps");
+    if (phase == MPC_TRACE_STEP) {
+        if (!d_u0) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: MPC_TRACE_STEP without u0 (hand the fused step a u0 array)");
+        if (!d_status || !d_iters) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: MPC_TRACE_STEP without status or iters");
+        if (h->trace.pred && !d_X) return fail(MPC_ERR_ARG, "mpc_episode_trace_dev: MPC_TRACE_STEP without X while the trace holds pred");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    const mpc_episode_trace &t = h->trace;
+    mpc::TraceArrays a{t.seed_row, t.slot_state, t.len, t.x, t.obst, t.u, t.status, t.iters, t.pred, h->trace_rows, h->trace_max_steps};
+    constexpr int per = mpc::kTraceThreads / 64;
+    hipLaunchKernelGGL(mpc::episode_trace_kernel, dim3((slots + per - 1) / per), dim3(mpc::kTraceThreads), 0, pick(h, stream), slots, phase, h->cfg.n_obst, h->cfg.N,
+                       a, d_slot_seed, d_x0, d_obst, d_X, d_u0, d_status, d_iters, d_ep_flags, d_ep_steps);
+    HIPCHK(hipGetLastError());
     return MPC_OK;
 }
 

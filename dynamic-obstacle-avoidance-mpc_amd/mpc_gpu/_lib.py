@@ -21,6 +21,7 @@ STEP_SHIFT, STEP_PLANT, STEP_OBSTACLES, STEP_RESET_ON_FAIL, STEP_ALIAS_BUG, STEP
 STEP_ADVANCE_REF = 128
 STEP_MARGIN_ALL = 256
 REFILL_ALIAS_BUG, REFILL_INTERP_GUESS, REFILL_DRAW_NOISE = 1, 2, 4      # MPC_REFILL_* (mpc_episode_refill_dev)
+TRACE_START, TRACE_STEP = 0, 1      # MPC_TRACE_* (mpc_episode_trace_dev)
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
 MAX_SQP_ITER = 100       # MPC_MAX_SQP_ITER
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
@@ -54,6 +55,11 @@ class RefillTables(C.Structure):
     """Mirror of `struct mpc_refill_tables` (include/mpc_gpu.h): device pointers only -- per-seed sources, per-slot destinations, the status log."""
     _fields_ = [(n, _vp) for n in ("W", "We", "r_safe", "r_hit", "mask", "bounds",
                                    "slot_W", "slot_We", "slot_r_safe", "slot_r_hit", "slot_mask", "slot_bounds", "log", "res_log")]
+
+
+class EpisodeTrace(C.Structure):
+    """Mirror of `struct mpc_episode_trace` (include/mpc_gpu.h): device pointers only -- the row map, the per-slot state and the per-seed rows of a sweep's trace."""
+    _fields_ = [(n, _vp) for n in ("seed_row", "slot_state", "len", "x", "obst", "u", "status", "iters", "pred")]
 
 
 _cfgp = C.POINTER(MpcConfig)
@@ -121,6 +127,8 @@ SYMBOLS = {
     "mpc_episode_status_log_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mpc_episode_ring_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_episode_ring_fill_dev": (C.c_int, [_vp, C.c_int, C.c_uint, C.c_int, _vp, _vp, _vp]),
+    "mpc_episode_trace_set_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(EpisodeTrace)]),
+    "mpc_episode_trace_dev": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 10),
     "mpc_comm_unique_id": (C.c_int, [_vp]),
     "mpc_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "mpc_comm_world": (C.c_int, [_vp]),

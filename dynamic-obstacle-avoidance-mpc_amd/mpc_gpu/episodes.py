@@ -344,9 +344,52 @@ def _sweep_features(count, n_obst, handle_cfg, r_safe=None, r_hit=None, W=None, 
     return out
 
 
+def trace_bytes(rows, max_iter, N, n_obst, pred=True):
+    """device bytes of a sweep's trace arrays (mpc_episode_trace): per traced seed x (max_iter + 1, 5), obst (max_iter + 1, n_obst, 4), u (max_iter, 2) and,
+    with pred, pred (max_iter, N + 1, 5) in float64, status and iters (max_iter,) and one len word in int32"""
+    rows, T, N, n_obst = int(rows), int(max_iter), int(N), int(n_obst)
+    per_row = 8 * ((T + 1) * 5 + (T + 1) * n_obst * 4 + T * 2 + (T * (N + 1) * 5 if pred else 0)) + 4 * (2 * T + 1)
+    return rows * per_row
+
+
+def _sweep_trace(count, max_iter, N, n_obst, trace=None, trace_pred=True, trace_max_bytes=2 ** 31):
+    """run_seed_sweep's trace arguments, checked on the host before anything touches a device.  Returns None (no trace) or dict(seeds: the traced seed indices
+    (rows,) in the order given, seed_row: int32 (count,) = the row of each seed index or -1, pred, bytes)."""
+    if trace is None or trace is False:
+        return None
+    if not isinstance(trace_pred, (bool, np.bool_)):
+        raise ValueError("trace_pred must be True or False")
+    if isinstance(trace_max_bytes, (bool, np.bool_)) or not isinstance(trace_max_bytes, (int, np.integer)) or trace_max_bytes < 0:
+        raise ValueError("trace_max_bytes must be a whole number of bytes >= 0")
+    if trace is True:
+        seeds = np.arange(count, dtype=np.int64)
+    else:
+        if isinstance(trace, (str, bytes, dict, set, frozenset)) or not hasattr(trace, "__len__"):
+            raise ValueError("trace must be None, True or a sequence of seed indices in 0 .. count-1")
+        try:
+            a = np.asarray(trace)
+        except Exception:
+            raise ValueError("trace must be None, True or a sequence of seed indices in 0 .. count-1") from None
+        if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+            raise ValueError(f"trace must be a non-empty 1-d sequence of whole seed indices (0 .. count-1, not seeds), got {a.dtype} {a.shape}")
+        if (a < 0).any() or (a >= count).any():
+            raise ValueError(f"trace holds a seed index outside 0 .. {count - 1}: {a[(a < 0) | (a >= count)][0]}")
+        seeds = a.astype(np.int64)
+        if np.unique(seeds).size != seeds.size:
+            raise ValueError("trace names a seed index twice (every traced seed owns one row)")
+    need = trace_bytes(seeds.size, max_iter, N, n_obst, pred=bool(trace_pred))
+    if need > trace_max_bytes:
+        raise ValueError(f"trace: the arrays of {seeds.size} seeds x {int(max_iter)} control steps take {need} bytes, more than trace_max_bytes = {int(trace_max_bytes)}: "
+                         "trace fewer seeds" + (" or pass trace_pred=False (the predicted horizons are most of it)" if trace_pred else ""))
+    seed_row = np.full(count, -1, dtype=np.int32)
+    seed_row[seeds] = np.arange(seeds.size, dtype=np.int32)
+    return dict(seeds=seeds, seed_row=seed_row, pred=bool(trace_pred), bytes=need)
+
+
 def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True, init_guess_when_error=True,
                    bug_compat_alias=True, interpolate_init=False, sqp=None, device=0, solver=None, poll_every=25, r_safe=None, r_hit=None, W=None, We=None,
-                   active=None, margin_all=False, bounds=None, status_log=False, ring=None, ring_every=None, **cfg):
+                   active=None, margin_all=False, bounds=None, status_log=False, ring=None, ring_every=None, trace=None, trace_pred=True,
+                   trace_max_bytes=2 ** 31, **cfg):
     """experiments.py:20-36 for MORE SEEDS THAN SLOTS: the seeds stream through min(slots, count) slots, and a slot whose episode has ended (goal reached,
     robot_ocp_problem.py:247-250, or max_iter control steps spent) starts the next seed on the device, in front of the next fused control step
     (mpc_episode_refill_dev: no host read, no gather, every slot stays live until the seeds run out).  Seed index k is instance k of
@@ -373,7 +416,15 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
     otherwise (capped by the loop bound); schedule (count, 2) = slot and control step at
     which each seed started (poll_every = 1; None otherwise), which is refill_schedule's slot / start.  With status_log: status2, status4, first_bad (count,).
     With ring and poll_every = 1: seed_src (count,) = 1 where the seed came from the ring, 0 where it was seeded in place = ring_model(schedule[:, 1], ring, ring_every).
-    Not offered: record, a per-seed stage reference, host noise, PipelinedMpc."""
+    trace: None (off, the default), True (every seed) or a sequence of seed INDICES in 0 .. count-1 without duplicates: what run_episodes(record=True) keeps, per
+    traced seed and recorded on the device (mpc_episode_trace_set_dev / mpc_episode_trace_dev: two small launches per control step, in front of and behind the
+    fused step, which then also writes u*).  `trace` in the result is a dict keyed by seed index; with L = the seed's control steps (= table[k, 4] + table[k, 1])
+    each value holds simX (L + 1, 5), obst_traj (L + 1, n_obst, 4), u (L, 2), status (L,), iters (L,) and, unless trace_pred=False, pred (L, N + 1, 5): the
+    iterate behind each step as run_episodes records it.  sweep_record(result, k) puts one seed into run_episodes(record=True)'s layout for visualisation_inputs.
+    The arrays take trace_bytes(rows, max_iter, N, n_obst, trace_pred) device bytes (90 kB per seed without pred and 426 kB with, at max_iter 400, N 20 and
+    5 obstacles); above trace_max_bytes the call is refused on the host.  The rows are those of the sweep without a trace, bit for bit.
+    Not offered: `record` as an argument (trace= is the sweep's form of it: rows of unequal length per seed, not a batch), a per-seed stage reference, host
+    noise, PipelinedMpc."""
     not_offered = sorted(set(cfg) & {"record", "noise", "seed", "first_seed", "compact_from"})
     if not_offered:
         raise TypeError(f"run_seed_sweep has no argument {not_offered[0]!r}: it is run_episodes' (a sweep would need it per seed)")
@@ -381,6 +432,8 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
     handle_cfg = solver.cfg if solver is not None else {n: tuple(cfg.get(n, v)) for n, v in DEFAULT_BOUNDS.items()}
     ft = _sweep_features(count, solver.n_obst if solver is not None else int(n_obst), handle_cfg, r_safe=r_safe, r_hit=r_hit, W=W, We=We, active=active,
                          margin_all=margin_all, bounds=bounds, status_log=status_log, ring=ring, ring_every=ring_every, poll_every=poll_every)
+    tr = _sweep_trace(count, max_iter, solver.N if solver is not None else int(N), solver.n_obst if solver is not None else int(n_obst), trace=trace,
+                      trace_pred=trace_pred, trace_max_bytes=trace_max_bytes)
     import torch
     S = min(int(slots), count); max_iter = int(max_iter); poll_every = int(poll_every)
     if interpolate_init and bug_compat_alias:
@@ -394,7 +447,7 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
         m.set_sqp(*sqp)
     stream = torch.cuda.Stream(device=dev)
     own_params = any(ft[n] is not None for n in ("W", "We", "r_safe", "r_hit"))
-    own_mask, own_bounds, own_tables = ft["mask"] is not None, ft["bounds"] is not None, False
+    own_mask, own_bounds, own_tables, own_trace = ft["mask"] is not None, ft["bounds"] is not None, False, False
     with torch.cuda.stream(stream):
         f64 = dict(dtype=torch.float64, device=dev); i32 = dict(dtype=torch.int32, device=dev)
         dstart, dgoal_rows = torch.from_numpy(start).to(dev), torch.from_numpy(goal).to(dev)
@@ -446,6 +499,15 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
             ring_state = torch.zeros(ring_cap, gen_state.shape[1], **i32); ring_obst = torch.zeros(ring_cap, n_obst, 4, **f64)
             ring_tag = torch.full((ring_cap,), -1, **i32); seed_src = torch.full((count,), -1, **i32)
             m.episode_ring_dev(ring_cap, ring_state, ring_obst, ring_tag, seed_src)
+        tarr, u0 = None, None
+        if tr is not None:          # the per-seed rows (mpc_episode_trace): row r belongs to seed index tr["seeds"][r]
+            R = tr["seeds"].size
+            tarr = dict(seed_row=torch.from_numpy(tr["seed_row"]).to(dev), slot_state=torch.tensor([-1, 0], **i32).repeat(S, 1).contiguous(),
+                        len=torch.zeros(R, **i32), x=torch.zeros(R, max_iter + 1, 5, **f64), obst=torch.zeros(R, max_iter + 1, n_obst, 4, **f64),
+                        u=torch.zeros(R, max_iter, 2, **f64), status=torch.zeros(R, max_iter, **i32), iters=torch.zeros(R, max_iter, **i32),
+                        pred=torch.zeros(R, max_iter, N + 1, 5, **f64) if tr["pred"] else None)
+            u0 = torch.zeros(S, 2, **f64)
+            m.episode_trace_set_dev(R, max_iter, **tarr); own_trace = True
         bound = -(-count // S) * max_iter + poll_every
         schedule = np.full((count, 2), -1, dtype=np.int64) if poll_every == 1 else None
         seen = np.full(S, -1, dtype=np.int64)
@@ -476,10 +538,14 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
                     live_event = torch.cuda.Event(); live_event.record(stream)
                 if k >= bound:
                     break
-                m.closed_loop_step_dev(S, dx0, dobst, dgoal, X, U, None, None, status, iters, nbuf, flags=fl,
+                if own_trace:                # the state every seed that has just started starts from: behind the refill, in front of the step
+                    m.episode_trace_dev(S, _lib.TRACE_START, slot_seed, dx0, dobst, ep_flags=flags, ep_steps=steps, stream=s)
+                m.closed_loop_step_dev(S, dx0, dobst, dgoal, X, U, u0, None, status, iters, nbuf, flags=fl,
                                        min_margin=margin, ep_flags=flags, ep_steps=steps, stream=s)
                 if ft["status_log"]:
                     m.episode_status_log_dev(S, status, flags, steps, tabs["log"], stream=s)
+                if own_trace:                # the step itself: the next refill overwrites a slot that has just finished
+                    m.episode_trace_dev(S, _lib.TRACE_STEP, slot_seed, dx0, dobst, X, u0, status, iters, flags, steps, stream=s)
                 k += 1
             stream.synchronize()
             left = int(cursor[1].item())
@@ -490,9 +556,12 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
                 extra.update(status2=rl[:, 0].copy(), status4=rl[:, 1].copy(), first_bad=rl[:, 2].copy())
             if ring_cap is not None and poll_every == 1:
                 extra["seed_src"] = seed_src.cpu().numpy()
+            th = {n: a.cpu().numpy() for n, a in tarr.items() if a is not None and n not in ("seed_row", "slot_state")} if own_trace else None
         finally:
             stream.synchronize()
             if solver is not None:           # (a caller's solver leaves as it came; the handle holds pointers into this call's tensors)
+                if own_trace:
+                    m.episode_trace_set_dev(0)
                 if own_tables:
                     m.set_refill_tables_dev()
                 if ring_cap is not None:
@@ -513,7 +582,38 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
     goal_all = np.ascontiguousarray(np.broadcast_to(goal, (count, 2)), dtype=np.float64)
     table = np.column_stack([(fl_h & 4) != 0, (fl_h & 1) != 0, rfh[:, 0],
                              np.linalg.norm(xl[:, :2] - goal_all, axis=1), st_h, (fl_h & 2) != 0]).astype(np.float64)
+    if th is not None:
+        if (th["len"] < 0).any():
+            raise _lib.MpcError(f"trace: seed indices {tr['seeds'][th['len'] < 0].tolist()} started without a START launch (mpc_episode_trace_dev)")
+        want = (table[tr["seeds"], 4] + table[tr["seeds"], 1]).astype(np.int64)
+        if not np.array_equal(th["len"], want):
+            bad = np.nonzero(th["len"] != want)[0]
+            raise _lib.MpcError(f"trace: seed index {int(tr['seeds'][bad[0]])} recorded {int(th['len'][bad[0]])} control steps, its table row says {int(want[bad[0]])}")
+        out = {}
+        for r, ks in enumerate(tr["seeds"].tolist()):
+            L = int(th["len"][r])
+            out[ks] = dict(simX=th["x"][r, :L + 1].copy(), obst_traj=th["obst"][r, :L + 1].copy(), u=th["u"][r, :L].copy(), status=th["status"][r, :L].copy(),
+                           iters=th["iters"][r, :L].copy())
+            if tr["pred"]:
+                out[ks]["pred"] = th["pred"][r, :L].copy()
+        extra["trace"] = out
     return dict(table=table, x_last=xl, steps_run=k, solves=int(st_h.sum()) + int((fl_h & 1).sum()), schedule=schedule, **extra)
+
+
+def sweep_record(result, k):
+    """One traced seed of a sweep in run_episodes(record=True)'s layout, as a batch of one: `result` = run_seed_sweep(..., trace=...), k a traced seed index.
+    Returns dict(simX (L + 1, 1, 5), obst_traj (L + 1, 1, n_obst, 4), pred (L, 1, N + 1, 5), table (1, 6), x_last (1, 5)), so that
+    visualisation_inputs(sweep_record(result, k), 0) is what the reference hands to its VisDynamicRobotEnv for that seed."""
+    tr = result.get("trace") if isinstance(result, dict) else None
+    if tr is None:
+        raise ValueError("the sweep was run without a trace: pass trace=True or the seed indices to run_seed_sweep")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or int(k) not in tr:
+        raise ValueError(f"seed index {k!r} was not traced (traced: {sorted(tr)[:8]}{' ...' if len(tr) > 8 else ''})")
+    t = tr[int(k)]
+    if "pred" not in t:
+        raise ValueError("the trace holds no predicted horizons (trace_pred=False): a record for visualisation_inputs needs them")
+    return dict(simX=t["simX"][:, None].copy(), obst_traj=t["obst_traj"][:, None].copy(), pred=t["pred"][:, None].copy(),
+                table=np.array(result["table"][int(k)][None]), x_last=np.array(result["x_last"][int(k)][None]))
 
 
 def visualisation_inputs(rec, instance, steps=None):

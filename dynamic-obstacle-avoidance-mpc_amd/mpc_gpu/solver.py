@@ -407,6 +407,27 @@ class BatchedMpc:
         box = self._scenario_box()
         _lib.check(_lib.lib().mpc_episode_ring_fill_dev(self._h, self.SCENARIOS[scenario], int(seed_first), int(seed_count), _ptr(box), _ptr(cursor), _ptr(stream)))
 
+    TRACE_FIELDS = ("seed_row", "slot_state", "len", "x", "obst", "u", "status", "iters", "pred")
+
+    def episode_trace_set_dev(self, rows=0, max_steps=0, seed_row=None, slot_state=None, len=None, x=None, obst=None, u=None, status=None, iters=None, pred=None):
+        """attach the per-seed trajectory arrays of a sweep (include/mpc_gpu.h mpc_episode_trace_set_dev), device tensors used in place: seed_row (count,) int32
+        = the row of each seed index or -1 (the non-negative entries distinct: the caller's to guarantee), slot_state (slots, 2) int32 preset {-1, 0}, len (rows,)
+        int32, x (rows, max_steps + 1, 5), obst (rows, max_steps + 1, n_obst, 4), u (rows, max_steps, 2), status / iters (rows, max_steps) int32, pred
+        (rows, max_steps, N + 1, 5) or None.  rows 0 (the default) detaches.  trace_shapes keeps the shapes of the arrays last attached."""
+        given = dict(seed_row=seed_row, slot_state=slot_state, len=len, x=x, obst=obst, u=u, status=status, iters=iters, pred=pred)
+        if int(rows) == 0:
+            _lib.check(_lib.lib().mpc_episode_trace_set_dev(self._h, 0, 0, None))
+            return
+        t = _lib.EpisodeTrace(**{n: _ptr(a) for n, a in given.items()})
+        _lib.check(_lib.lib().mpc_episode_trace_set_dev(self._h, int(rows), int(max_steps), C.byref(t)))
+        self.trace_shapes = {n: tuple(a.shape) for n, a in given.items() if hasattr(a, "shape")}
+
+    def episode_trace_dev(self, slots, phase, slot_seed, x0, obst, X=None, u0=None, status=None, iters=None, ep_flags=None, ep_steps=None, stream=None):
+        """one launch of the attached trace (include/mpc_gpu.h mpc_episode_trace_dev): phase _lib.TRACE_START behind episode_refill_dev, _lib.TRACE_STEP behind
+        closed_loop_step_dev (which then takes a u0 array) and episode_status_log_dev, all on one stream"""
+        _lib.check(_lib.lib().mpc_episode_trace_dev(self._h, int(slots), int(phase), _ptr(slot_seed), _ptr(x0), _ptr(obst), _ptr(X), _ptr(u0), _ptr(status),
+                                                    _ptr(iters), _ptr(ep_flags), _ptr(ep_steps), _ptr(stream)))
+
     # ------------------------------------------------------------------ multi-GPU: all-gather of the costs, RCCL called by the library itself
     @staticmethod
     def comm_unique_id():

@@ -377,6 +377,50 @@ int mpc_episode_status_log_dev(mpc_handle *h, int slots, const int32_t *d_status
                                void *stream);
 int mpc_episode_ring_dev(mpc_handle *h, int capacity, uint32_t *d_ring_state, double *d_ring_obst, int32_t *d_ring_tag, int32_t *d_seed_src);
 int mpc_episode_ring_fill_dev(mpc_handle *h, int scenario, unsigned seed_first, int seed_count, const double *box, const int32_t *d_cursor, void *stream);
+/* SEED SWEEPS, PER-SEED TRAJECTORIES (mpc_episode_trace_set_dev, mpc_episode_trace_dev), opt-in and additive like the calls above: a handle on which
+ * neither was made launches exactly what it launched before.  What the reference keeps per experiment for its visualisation -- simX, the obstacle
+ * trajectories, the predicted horizons (robot_ocp_problem.py:42-49, 234-241, 270-276) -- is recorded ON THE DEVICE for the seed indices that ask for it,
+ * whatever slot and control step they run at.  seed_row[k] >= 0 names the row of seed index k in the arrays below, -1 = not traced; the NON-NEGATIVE
+ * ENTRIES MUST BE DISTINCT AND BELOW rows -- that is the host's to guarantee, nothing on the device checks distinctness (an entry >= rows is not traced).
+ * Rows hold max_steps control steps: give the refill's max_steps.  The struct holds device pointers only and is copied by the call; the arrays are the
+ * caller's and are used in place.  mpc_episode_trace_set_dev(h, 0, 0, NULL) (NULL, or rows == 0) detaches.
+ *
+ * PROTOCOL of one control step, everything on one stream, in this order:
+ *   1. mpc_episode_ring_fill_dev (if a ring is attached)   2. mpc_episode_refill_dev   3. mpc_episode_trace_dev, MPC_TRACE_START
+ *   4. mpc_closed_loop_step_dev WITH a d_u0 array          5. mpc_episode_status_log_dev (if on)   6. mpc_episode_trace_dev, MPC_TRACE_STEP
+ * Two phases, because the refill overwrites a finished slot before anything behind it could read the slot's last step: the last step of an episode is
+ * recorded behind the fused step that made it (STEP), the state a seed starts from behind the refill that wrote it (START).
+ * In both, for slot s: k = slot_seed[s], now = ep_steps[s] + (ep_flags[s] & 1) (the status log's "episode steps solved"), r = seed_row[k].
+ *   START: if k >= 0 and k != slot_state[s].seed, seed k has just started here: slot_state[s] = {k, 0}; if r >= 0, x[r][0] = x0[s], obst[r][0] = obst[s],
+ *     len[r] = 0.  If r >= 0 but now != 0 the caller skipped a START call: len[r] = -1 and nothing else is written (the seed is then never recorded: a
+ *     protocol error is visible instead of a wrong row 0).
+ *   STEP: acts only if k >= 0, k == slot_state[s].seed and now > seen; the slot then solved at episode step `seen`.  If r >= 0 and now <= max_steps:
+ *     x[r][now] = x0[s], obst[r][now] = obst[s], u[r][seen] = u0[s], status[r][seen], iters[r][seen], pred[r][seen] = X[s] if pred is given (the RAW
+ *     iterate as the fused step left it, i.e. shifted: stage j of the solve sits at X[j - 1], stage N is kept), len[r] = now.  Then seen = now.
+ *   Slots that are drained (slot_seed = -1), idle or untraced write nothing but `seen`.
+ * One wavefront per slot, 256-thread workgroups; the lanes stride over the doubles of a row, lane 0 writes len and slot_state last.  No atomics, no
+ * spinning, no grid-wide synchronisation, bounded loops; every word written belongs to the slot or to the seed's own row; no thread reads a word that
+ * another wavefront of the same launch writes.
+ * MPC_ERR_ARG (with a message naming the field, nothing launched): rows < 0, max_steps < 1, a null required pointer (pred alone is optional); phase
+ * outside {0, 1}, slots outside [1, max_batch], no trace attached, d_u0 / d_status / d_iters null in phase STEP (d_X too while pred is attached; START
+ * reads none of the four). */
+typedef struct mpc_episode_trace {
+    const int32_t *seed_row;   /* [seed_count]: row of seed index k in the arrays below, or -1 = not traced */
+    int32_t *slot_state;       /* [slots][2] = {seed index being traced, seen}; the caller presets {-1, 0} */
+    int32_t *len;              /* [rows]  control steps recorded for the row (preset 0); -1 = protocol error */
+    double *x;                 /* [rows][max_steps + 1][5]          plant state; row 0 = the state the seed started from */
+    double *obst;              /* [rows][max_steps + 1][n_obst][4]  obstacle states, likewise */
+    double *u;                 /* [rows][max_steps][2]              u* applied at the step */
+    int32_t *status;           /* [rows][max_steps]                 the solve's status */
+    int32_t *iters;            /* [rows][max_steps]                 its interior-point iterations */
+    double *pred;              /* [rows][max_steps][N + 1][5] or NULL: the iterate X as the fused step left it */
+} mpc_episode_trace;
+int mpc_episode_trace_set_dev(mpc_handle *h, int rows, int max_steps, const mpc_episode_trace *t);
+#define MPC_TRACE_START 0
+#define MPC_TRACE_STEP 1
+int mpc_episode_trace_dev(mpc_handle *h, int slots, int phase, const int32_t *d_slot_seed, const double *d_x0, const double *d_obst, const double *d_X,
+                          const double *d_u0, const int32_t *d_status, const int32_t *d_iters, const int32_t *d_ep_flags, const int32_t *d_ep_steps,
+                          void *stream);
 /* MULTI-GPU: one process per GPU, every rank solves its own contiguous slice of the scenarios (the reference's 13 000 closed
  * loops, experiments.py:20-36, are independent), and the only exchange is an all-gather of the per-instance costs -- RCCL over xGMI, called directly
  * from this library (librccl.so.1 is loaded on first use; there is no link-time dependency and no other transport).  A C host does:

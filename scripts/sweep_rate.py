@@ -14,6 +14,7 @@ Per-step overhead (HIP events on the step's stream, median of --launches single 
 with one slot refilled and with every slot refilled, each with and without the noise draw; mpc_noise_draw_dev alone; the fused step.
 
     python scripts/sweep_rate.py [--seeds 16384] [--slots 1024] [--reps 3] [--launches 30] [--out profiles/sweep_rates.json]
+    python scripts/sweep_rate.py --trace off all all-nopred [--baseline-root DIR] [--trace-out profiles/sweep_trace_rates.json]
 
 --ring-forms measures the per-seed features instead and writes profiles/sweep_ring_rates.json (profiles/sweep_rates.json is left alone): at every slot count
 of --slot-counts (default 1024,4096) the forms
@@ -25,6 +26,12 @@ of --slot-counts (default 1024,4096) the forms
   "all":        every per-seed table, the status log and the ring;
 the same protocol (a warm-up, then --reps runs per form, the forms alternating), and the per-call table for the refill with ONE slot refilled, ring on
 against ring off, the ring fill and the status log kernel.
+
+--trace FORM [FORM ...] (off, all, all-nopred) measures the per-seed trajectories instead and writes profiles/sweep_trace_rates.json: run_seed_sweep at --slots
+slots over --seeds seeds with trace off, with every seed traced, and with every seed traced without the predicted horizons -- beside "baseline", the parent
+commit's sweep, when --baseline-root is given.  The same protocol (a warm-up, then --reps runs per form, the forms alternating in one process); wall time
+around the whole call, read-back of the rows to the host included, and solves/s = the table's solves over the median time.  Beside the forms: the trace
+launches per call (HIP events, START and STEP, with and without pred) at --slots slots.
 """
 import argparse
 import json
@@ -149,8 +156,113 @@ def ring_forms(a):
         json.dump(out, f, indent=1)
 
 
+def trace_forms(a):
+    import torch
+    import mpc_gpu
+    import sweep_cases as sc
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this script measures on the device only")
+    L = mpc_gpu._lib
+    E, S, scen = a.seeds, a.slots, a.scenario
+    prob = dict(sc.PROBLEM, max_iter=400)
+    base = load_baseline(a.baseline_root) if a.baseline_root else None
+    run = lambda **kw: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, trace_max_bytes=2 ** 40, **kw, **prob)
+    forms = {}
+    if base is not None:
+        forms["baseline"] = lambda: base.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **prob)
+    for f in a.trace:
+        forms[f] = {"off": lambda: run(), "all": lambda: run(trace=True), "all-nopred": lambda: run(trace=True, trace_pred=False)}[f]
+    times, last = {f: [] for f in forms}, {}
+    for rep in range(a.reps + 1):               # rep 0: warm-up of every form
+        for f, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            last[f] = dict(table=r["table"], steps_run=r["steps_run"], solves=r["solves"], traced=len(r.get("trace", ())),
+                           trace_rows=int(sum(t["u"].shape[0] for t in r["trace"].values())) if "trace" in r else 0)
+            del r                                # (a trace of every seed is gigabytes on the host: one at a time)
+            if rep:
+                times[f].append(dt)
+            print(json.dumps(dict(slots=S, rep=rep, form=f, seconds=dt, steps_run=last[f]["steps_run"])), flush=True)
+    res = {}
+    for f in forms:
+        ts = np.array(times[f])
+        res[f] = dict(seconds=[float(t) for t in ts], median_s=float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
+                      solves=int(last[f]["solves"]), solves_per_s=float(last[f]["solves"] / np.median(ts)), episodes_per_s=float(E / np.median(ts)),
+                      fused_steps=int(last[f]["steps_run"]), ms_per_step=float(1e3 * np.median(ts) / last[f]["steps_run"]), traced_seeds=int(last[f]["traced"]),
+                      traced_steps=int(last[f]["trace_rows"]))
+    ref = "off" if "off" in res else next(iter(res))
+    summary = dict(largest_spread=max(r["spread"] for r in res.values()))
+    for f in res:
+        if f != ref:
+            summary[f.replace("-", "_") + "_over_" + ref] = res[f]["median_s"] / res[ref]["median_s"]
+            summary[f.replace("-", "_") + "_rows_equal_" + ref] = bool(np.array_equal(last[f]["table"], last[ref]["table"]))
+    if base is not None and "off" in res:
+        spread = max(res["off"]["spread"], res["baseline"]["spread"])
+        summary.update(off_over_baseline=res["off"]["median_s"] / res["baseline"]["median_s"], off_baseline_spread=spread,
+                       off_equals_baseline_within_spread=bool(abs(res["off"]["median_s"] / res["baseline"]["median_s"] - 1) <= spread))
+    for f, pred in (("all", True), ("all-nopred", False)):
+        if f in res:
+            res[f]["device_bytes"] = int(mpc_gpu.trace_bytes(E, 400, sc.PROBLEM["N"], sc.PROBLEM["n_obst"], pred=pred))
+    out = dict(workload=dict(scenario=scen, seeds=E, slots=S, reps=a.reps, **prob), forms=res, summary=summary)
+    print(json.dumps(out), flush=True)
+
+    # ---- the trace launches on their own: every slot a few steps into a traced episode
+    dev = torch.device("cuda", 0)
+    over = {}
+    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        st = torch.cuda.current_stream(); cs = st.cuda_stream
+        plain = sc.Plain(torch, dev)
+        arr = sc.SlotArrays(plain, m, S, E, L.lib().mpc_noise_state_words())
+        N, no, T = m.N, m.n_obst, 400
+        step_flags = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES | L.STEP_METRICS | L.STEP_RESET_ON_FAIL | L.STEP_ALIAS_BUG
+        fl = L.REFILL_ALIAS_BUG | L.REFILL_DRAW_NOISE
+        u0 = plain.f64(S, 2)
+        seed_row = plain.i32(E, init=-1); seed_row[:S] = torch.arange(S, dtype=torch.int32, device=dev)
+        t = dict(seed_row=seed_row, slot_state=plain.i32(S, 2), len=plain.i32(S), x=plain.f64(S, T + 1, 5), obst=plain.f64(S, T + 1, no, 4), u=plain.f64(S, T, 2),
+                 status=plain.i32(S, T), iters=plain.i32(S, T), pred=plain.f64(S, T, N + 1, 5))
+
+        def timed(fn, before=None):
+            ms = []
+            for _ in range(a.launches):
+                if before:
+                    before()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st); fn(); e1.record(st)
+                st.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            return dict(median_us=1e3 * float(np.median(ms)), min_us=1e3 * float(np.min(ms)), max_us=1e3 * float(np.max(ms)))
+
+        def step():
+            m.closed_loop_step_dev(S, arr.x0, arr.obst, arr.goal, arr.X, arr.U, u0, None, arr.status, arr.iters, arr.noise, flags=step_flags, min_margin=arr.margin,
+                                   ep_flags=arr.flags, ep_steps=arr.steps, stream=cs)
+        start = lambda: m.episode_trace_dev(S, L.TRACE_START, arr.slot_seed, arr.x0, arr.obst, ep_flags=arr.flags, ep_steps=arr.steps, stream=cs)
+        record = lambda: m.episode_trace_dev(S, L.TRACE_STEP, arr.slot_seed, arr.x0, arr.obst, arr.X, u0, arr.status, arr.iters, arr.flags, arr.steps, stream=cs)
+        for tag, pred in (("", t["pred"]), ("_nopred", None)):
+            t["slot_state"].copy_(torch.tensor([-1, 0], dtype=torch.int32, device=dev).repeat(S, 1))
+            arr.flags.fill_(1); arr.steps.zero_(); arr.slot_seed.fill_(-1); arr.cursor.zero_()
+            m.episode_trace_set_dev(S, T, **dict(t, pred=pred))
+            arr.refill(m, scen, 0, 400, fl, cs)
+            over["trace_start_every_slot_starts" + tag] = timed(start, before=lambda: t["slot_state"][:, 0].fill_(-1))
+            over["trace_start_nothing_starts" + tag] = timed(start)
+            over["trace_step_every_slot_stepped" + tag] = timed(record, before=lambda: (arr.refill(m, scen, 0, 400, fl, cs), step()))
+            over["trace_step_nothing_stepped" + tag] = timed(record)
+            st.synchronize()
+            over["rows_with_every_timed_step_recorded" + tag] = int((t["len"] == a.launches).sum().item())      # (of --slots; an episode shorter than that has ended)
+        m.episode_trace_set_dev(0)
+    out["per_call"] = dict(slots=S, launches=a.launches, **over)
+    print(json.dumps(dict(per_call=out["per_call"])), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.trace_out)), exist_ok=True)
+    with open(a.trace_out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--trace", nargs="+", choices=["off", "all", "all-nopred"], default=None)
+    ap.add_argument("--trace-out", default=os.path.join(ROOT, "profiles", "sweep_trace_rates.json"))
     ap.add_argument("--ring-forms", action="store_true")
     ap.add_argument("--slot-counts", default="1024,4096")
     ap.add_argument("--baseline-root", default=None)
@@ -164,6 +276,8 @@ def main():
     a = ap.parse_args()
     if a.ring_forms:
         return ring_forms(a)
+    if a.trace:
+        return trace_forms(a)
     import torch
     import mpc_gpu
     import sweep_cases as sc
