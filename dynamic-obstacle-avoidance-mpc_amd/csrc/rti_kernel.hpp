@@ -916,8 +916,15 @@ __device__ __forceinline__ void wave_sync()
 
 __device__ __forceinline__ uint32_t lds_address(const void *p) { return (uint32_t)(uintptr_t)p; }     // low half of a flat LDS address = LDS byte offset
 
-template <class LT>
-__device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool worker_row)
+// TERMS: how stepM starts the accumulators of M~ = H~aug + W~' T.
+//   kSweepTermsOutOfPlace  every first term is an out-of-place instruction on the fetched word, the term with the constant factor 1 or dt (no copy of the column);
+//   kSweepTermsCopied      the same term order on a copied column: the compact blocks of the 256-register stage-split kernels (two wavefronts per SIMD), which
+//                          spill as they are and answer the longer live range of the fetched column with more scratch -- every bit equals the build above;
+//   kSweepTermsParent      the sweep before this change, bit for bit (copied column, terms in the order of the rows of W~): rti_wide_kernel, whose QPs with
+//                          hundreds of active rows amplify a last-bit difference to 1e-5.
+enum { kSweepTermsOutOfPlace = 0, kSweepTermsCopied = 1, kSweepTermsParent = 2 };
+template <class LT, int TERMS = (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace)>
+__device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool worker_row, double dt)
 {
     constexpr int WS = LT::WS, HS = LT::HS;
     const int j = lane & 7, l15 = lane & 15;    // column; lanes 8..15 of a row mirror 0..7
@@ -994,66 +1001,181 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
     };
     // second half: M~ (accumulated onto the H~aug column in M), L D L' of Muu, column j of K~, P~+ in M[0..5]
     auto stepM = [&](int t, const double Wc[5], const double Hc[8], const double T[6], double M[8]) {
-        // M~ = H~aug + W~' T over the structural non-zeros of W~ (A = I + E, B: 24 of 40 products), rows 6, 7 (the input block) first;
+        // M~ = H~aug + W~' T over the structural non-zeros of W~ (A = I + E, B: 24 of 40 products, 7 of them with a constant), rows 6, 7 (the input block) first;
         // then Muu = M~[6..7][6..7] -> L D L' (backward stable, see systolic_factor) and column j of K~ = -Muu^-1 M~[u, :],
         // computed in every lane and hand-interleaved with the remaining rows of M~ so that the serial reciprocal / Newton
         // chain (~15 dependent instructions) hides behind independent FMAs
-        // the accumulators start as copies of the H~aug column made HERE, after the operands have arrived: accumulating in place
-        // into registers that a ds_read2_b64 delivers makes the compiler copy them out right behind the request (a stall)
-        asm volatile("v_mov_b64_e32 %0, %8\nv_mov_b64_e32 %1, %9\nv_mov_b64_e32 %2, %10\nv_mov_b64_e32 %3, %11\n"
-                     "v_mov_b64_e32 %4, %12\nv_mov_b64_e32 %5, %13\nv_mov_b64_e32 %6, %14\nv_mov_b64_e32 %7, %15\n"
-                     : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
-                     : "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]), "v"(Hc[5]), "v"(Hc[6]), "v"(Hc[7]));
-        double K0, K1, i00, l, i11, m66, m67, m77, e_, r_;
-        asm volatile(
-            "s_nop 1\n"
-            "v_fmac_f64_dpp %6, %18, %23 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %7, %18, %23 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %6, %19, %24 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %7, %19, %24 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %7, %20, %25 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %6, %21, %26 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %7, %22, %27 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %0, %18, %23 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %2, %18, %23 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
-            "v_mov_b64_dpp %13, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
-            "v_mov_b64_dpp %14, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
-            "v_mov_b64_dpp %15, %7 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
-            "v_fmac_f64_dpp %3, %18, %23 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
-            "v_rcp_f64_e32 %17, %13\n"
-            "v_fmac_f64_dpp %4, %18, %23 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %16, -%13, %17, 1.0\n"
-            "v_fmac_f64_dpp %5, %18, %23 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %17, %16, %17, %17\n"
-            "v_fmac_f64_dpp %1, %19, %24 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %16, -%13, %17, 1.0\n"
-            "v_fmac_f64_dpp %2, %19, %24 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %10, %16, %17, %17\n"
-            "v_fmac_f64_dpp %3, %19, %24 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
-            "v_mul_f64 %11, %14, %10\n"
-            "v_fmac_f64_dpp %4, %19, %24 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %15, -%11, %14, %15\n"
-            "v_fmac_f64_dpp %5, %19, %24 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
-            "v_rcp_f64_e32 %17, %15\n"
-            "v_fmac_f64_dpp %2, %20, %25 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %16, -%15, %17, 1.0\n"
-            "v_fmac_f64_dpp %4, %20, %25 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %17, %16, %17, %17\n"
-            "v_fmac_f64_dpp %5, %20, %25 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %16, -%15, %17, 1.0\n"
-            "v_fmac_f64_dpp %3, %21, %26 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %12, %16, %17, %17\n"
-            "v_fmac_f64_dpp %5, %21, %26 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %16, %11, %6, -%7\n"
-            "v_fmac_f64_dpp %4, %22, %27 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
-            "v_mul_f64 %9, %16, %12\n"
-            "v_mul_f64 %16, %6, %10\n"
-            "v_fmac_f64_dpp %5, %22, %27 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
-            "v_fma_f64 %8, -%11, %9, -%16\n"
-            : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[5]), "+v"(M[6]), "+v"(M[7]),
-              "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m66), "=&v"(m67), "=&v"(m77), "=&v"(e_), "=&v"(r_)
-            : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]));
-        M[5] += T[5];                                                  // r = 5 term of W~' T
+        double K0, K1, i00, l, i11, m67;
+        if constexpr (TERMS == kSweepTermsOutOfPlace) {
+            // every accumulator's FIRST term is an out-of-place instruction that reads the fetched H~aug word as its addend: the term of W~' T whose
+            // factor all lanes know -- W~[i][i] = 1 (A = I + E) for M[0..4], row 5 of W~ = e_5' for M[5], W~[3][6] = W~[4][7] = dt for M[6], M[7].
+            // No copy of the column, and no DPP FMA that multiplies by a broadcast 1.0 or dt.  (Accumulating IN PLACE into registers that a
+            // ds_read2_b64 delivers makes the compiler copy them out right behind the request, a stall: DESIGN.md section 4.)  Those of M[2..4]
+            // are issued inside the block, as fillers of the reciprocal chain; the chain's temporaries live in its result registers
+            // (e, r in K0, K1; m66, m77 in i00, i11 until the reciprocals replace them), so the block holds no more registers than it did.
+            // (asm, not C++: the compiler turns fma(dt, T, Hc) into an in-place v_fmac on the fetched register -- and copies the next request out again)
+            asm volatile("v_fma_f64 %3, %10, %8, %13\nv_fma_f64 %4, %10, %9, %14\nv_add_f64 %0, %11, %5\nv_add_f64 %1, %12, %6\nv_add_f64 %2, %15, %7\n"
+                         : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
+                         : "v"(T[0]), "v"(T[1]), "v"(T[5]), "v"(T[3]), "v"(T[4]), "s"(dt), "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[6]), "v"(Hc[7]), "v"(Hc[5]));
+            asm volatile(
+                "s_nop 1\n"
+                "v_fmac_f64_dpp %5, %12, %17 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %5, %13, %18 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %5, %14, %19 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %4, %12, %17 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %4, %13, %18 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_add_f64 %2, %24, %21\n"
+                "v_mov_b64_dpp %10, %5 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %8, %4 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %11, %4 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_add_f64 %0, %22, %19\n"
+                "v_rcp_f64_e32 %7, %8\n"
+                "v_add_f64 %1, %23, %20\n"
+                "v_fma_f64 %6, -%8, %7, 1.0\n"
+                "v_fmac_f64_dpp %0, %12, %17 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %7, %6, %7, %7\n"
+                "v_fmac_f64_dpp %1, %12, %17 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %6, -%8, %7, 1.0\n"
+                "v_fmac_f64_dpp %2, %12, %17 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %8, %6, %7, %7\n"
+                "v_fmac_f64_dpp %3, %12, %17 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %9, %11, %8\n"
+                "v_fmac_f64_dpp %0, %13, %18 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %10, -%9, %11, %10\n"
+                "v_fmac_f64_dpp %1, %13, %18 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %7, %10\n"
+                "v_fmac_f64_dpp %2, %13, %18 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %6, -%10, %7, 1.0\n"
+                "v_fmac_f64_dpp %3, %13, %18 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %7, %6, %7, %7\n"
+                "v_fmac_f64_dpp %2, %14, %19 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %6, -%10, %7, 1.0\n"
+                "v_fmac_f64_dpp %3, %14, %19 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %10, %6, %7, %7\n"
+                "v_fma_f64 %6, %9, %4, -%5\n"
+                "v_fmac_f64_dpp %3, %15, %20 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %7, %6, %10\n"
+                "v_mul_f64 %6, %4, %8\n"
+                "v_fmac_f64_dpp %3, %16, %21 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %6, -%9, %7, -%6\n"
+                : "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "+v"(M[5]), "+v"(M[6]), "+v"(M[7]),
+                  "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m67)
+                : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]),
+                  "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]));
+        } else if constexpr (TERMS == kSweepTermsParent) {
+            // the sweep as it was before the out-of-place first terms, bit for bit: copies of the column, the terms in the order of the rows of W~, T[5] last
+            asm volatile("v_mov_b64_e32 %0, %8\nv_mov_b64_e32 %1, %9\nv_mov_b64_e32 %2, %10\nv_mov_b64_e32 %3, %11\n"
+                         "v_mov_b64_e32 %4, %12\nv_mov_b64_e32 %5, %13\nv_mov_b64_e32 %6, %14\nv_mov_b64_e32 %7, %15\n"
+                         : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
+                         : "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]), "v"(Hc[5]), "v"(Hc[6]), "v"(Hc[7]));
+            double m66, m77, e_, r_;
+            asm volatile(
+                "s_nop 1\n"
+                "v_fmac_f64_dpp %6, %18, %23 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %18, %23 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %19, %24 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %19, %24 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %20, %25 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %21, %26 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %22, %27 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %18, %23 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %2, %18, %23 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %13, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %14, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %15, %7 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %3, %18, %23 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %17, %13\n"
+                "v_fmac_f64_dpp %4, %18, %23 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%13, %17, 1.0\n"
+                "v_fmac_f64_dpp %5, %18, %23 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %17, %16, %17, %17\n"
+                "v_fmac_f64_dpp %1, %19, %24 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%13, %17, 1.0\n"
+                "v_fmac_f64_dpp %2, %19, %24 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %10, %16, %17, %17\n"
+                "v_fmac_f64_dpp %3, %19, %24 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %11, %14, %10\n"
+                "v_fmac_f64_dpp %4, %19, %24 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%11, %14, %15\n"
+                "v_fmac_f64_dpp %5, %19, %24 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %17, %15\n"
+                "v_fmac_f64_dpp %2, %20, %25 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%15, %17, 1.0\n"
+                "v_fmac_f64_dpp %4, %20, %25 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %17, %16, %17, %17\n"
+                "v_fmac_f64_dpp %5, %20, %25 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%15, %17, 1.0\n"
+                "v_fmac_f64_dpp %3, %21, %26 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %12, %16, %17, %17\n"
+                "v_fmac_f64_dpp %5, %21, %26 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, %11, %6, -%7\n"
+                "v_fmac_f64_dpp %4, %22, %27 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %9, %16, %12\n"
+                "v_mul_f64 %16, %6, %10\n"
+                "v_fmac_f64_dpp %5, %22, %27 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %8, -%11, %9, -%16\n"
+                : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[5]), "+v"(M[6]), "+v"(M[7]),
+                  "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m66), "=&v"(m67), "=&v"(m77), "=&v"(e_), "=&v"(r_)
+                : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]));
+            M[5] += T[5];                                                  // r = 5 term of W~' T
+        } else {
+            // the accumulators start as copies of the H~aug column made HERE, after the operands have arrived; the terms
+            // with a constant factor come first, as above
+            asm volatile("v_mov_b64_e32 %0, %8\nv_mov_b64_e32 %1, %9\nv_mov_b64_e32 %2, %10\nv_mov_b64_e32 %3, %11\n"
+                         "v_mov_b64_e32 %4, %12\nv_mov_b64_e32 %5, %13\nv_mov_b64_e32 %6, %14\nv_mov_b64_e32 %7, %15\n"
+                         : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
+                         : "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]), "v"(Hc[5]), "v"(Hc[6]), "v"(Hc[7]));
+            double m66, m77, e_, r_;
+            asm volatile(
+                "s_nop 1\n"
+                "v_add_f64 %5, %5, %28\n"
+                "v_fmac_f64_dpp %6, %21, %26 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %22, %27 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %18, %23 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %18, %23 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %19, %24 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %19, %24 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %7, %20, %25 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %18, %23 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %2, %20, %25 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %13, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %14, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %15, %7 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %3, %21, %26 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %17, %13\n"
+                "v_fmac_f64_dpp %4, %22, %27 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%13, %17, 1.0\n"
+                "v_fmac_f64_dpp %1, %19, %24 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %17, %16, %17, %17\n"
+                "v_fmac_f64_dpp %2, %18, %23 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%13, %17, 1.0\n"
+                "v_fmac_f64_dpp %3, %18, %23 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %10, %16, %17, %17\n"
+                "v_fmac_f64_dpp %4, %18, %23 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %11, %14, %10\n"
+                "v_fmac_f64_dpp %5, %18, %23 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%11, %14, %15\n"
+                "v_fmac_f64_dpp %2, %19, %24 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %17, %15\n"
+                "v_fmac_f64_dpp %3, %19, %24 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%15, %17, 1.0\n"
+                "v_fmac_f64_dpp %4, %19, %24 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %17, %16, %17, %17\n"
+                "v_fmac_f64_dpp %5, %19, %24 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, -%15, %17, 1.0\n"
+                "v_fmac_f64_dpp %4, %20, %25 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %12, %16, %17, %17\n"
+                "v_fmac_f64_dpp %5, %20, %25 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, %11, %6, -%7\n"
+                "v_fmac_f64_dpp %5, %21, %26 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %9, %16, %12\n"
+                "v_mul_f64 %16, %6, %10\n"
+                "v_fmac_f64_dpp %5, %22, %27 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %8, -%11, %9, -%16\n"
+                : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[5]), "+v"(M[6]), "+v"(M[7]),
+                  "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m66), "=&v"(m67), "=&v"(m77), "=&v"(e_), "=&v"(r_)
+                : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]), "v"(T[5]));
+        }
         kp[HS * t] = K0; kp[HS * t + 8] = K1;
         fp[HS * t] = i00; fp[HS * t + 1] = l; fp[HS * t + 8] = i11;
         // P~+ = M~[0..5][0..5] + M~[0..5][u] K~   (M~[i][6] = M~[6][i] is lane i's register 6)
@@ -1308,8 +1430,9 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
     if (m == 0) { stepT(Wa, Pb, T); stepM(0, Wa, Ha, T, Pa); }
 }
 
-// THE SAME SWEEP AS ONE ASM BLOCK (rowpar_factor_fast; text generated from the three blocks above, identical arithmetic and results).
-// What it saves per stage: the eight accumulator copies (the H~aug column is requested straight INTO the accumulator registers -- inside
+// THE SAME SWEEP AS ONE ASM BLOCK (rowpar_factor_fast; text generated from the three blocks above, identical arithmetic and results: every
+// accumulator of M~ takes its terms in the order of stepM, the one with the constant factor 1 or dt first -- here still a DPP FMA on the staged word).
+// What it saves per stage: the accumulator copies (the H~aug column is requested straight INTO the accumulator registers -- inside
 // one block no compiler can touch a register with a load in flight), four address updates, and every wait is counted exactly
 // (s_waitcnt lgkmcnt(7) before a T block: the 4 accumulator requests and 3 stores younger than its W~ operands; lgkmcnt(10) before an M
 // block: 3 stores and the 7 requests of the next stage).  Two stages per loop pass (register sets a / b), the operands of a stage are
@@ -1416,50 +1539,50 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "ds_read2_b64 v[128:131], " V##_H_L67 "\n" \
         "s_waitcnt lgkmcnt(10)\n" \
         "s_nop 1\n" \
+        "v_fmac_f64_dpp v[112:113], v[150:151], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[114:115], v[152:153], v[140:141] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[112:113], v[144:145], v[132:133] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[114:115], v[144:145], v[132:133] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[112:113], v[146:147], v[134:135] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[114:115], v[146:147], v[134:135] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[114:115], v[148:149], v[136:137] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[112:113], v[150:151], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[114:115], v[152:153], v[140:141] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[100:101], v[144:145], v[132:133] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[104:105], v[144:145], v[132:133] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[104:105], v[148:149], v[136:137] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[174:175], v[112:113] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[176:177], v[112:113] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[178:179], v[114:115] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[106:107], v[144:145], v[132:133] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[106:107], v[150:151], v[138:139] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[174:175]\n" \
-        "v_fmac_f64_dpp v[108:109], v[144:145], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[152:153], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[110:111], v[144:145], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_add_f64 v[110:111], v[110:111], v[142:143]\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
         "v_fmac_f64_dpp v[102:103], v[146:147], v[134:135] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[104:105], v[146:147], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[104:105], v[144:145], v[132:133] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[168:169], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[106:107], v[146:147], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[106:107], v[144:145], v[132:133] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[170:171], v[176:177], v[168:169]\n" \
-        "v_fmac_f64_dpp v[108:109], v[146:147], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[144:145], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[178:179], -v[170:171], v[176:177], v[178:179]\n" \
-        "v_fmac_f64_dpp v[110:111], v[146:147], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[144:145], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[178:179]\n" \
-        "v_fmac_f64_dpp v[104:105], v[148:149], v[136:137] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[104:105], v[146:147], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[108:109], v[148:149], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[146:147], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[148:149], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[146:147], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[106:107], v[150:151], v[138:139] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[106:107], v[146:147], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[172:173], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[150:151], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[148:149], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], v[170:171], v[112:113], -v[114:115]\n" \
-        "v_fmac_f64_dpp v[108:109], v[152:153], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[148:149], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[166:167], v[180:181], v[172:173]\n" \
         "v_mul_f64 v[180:181], v[112:113], v[168:169]\n" \
-        "v_fmac_f64_dpp v[110:111], v[152:153], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[150:151], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[164:165], -v[170:171], v[166:167], -v[180:181]\n" \
-        "v_add_f64 v[110:111], v[110:111], v[142:143]\n" \
+        "v_fmac_f64_dpp v[110:111], v[152:153], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_write2_b64 %2, v[164:165], v[166:167] " V##_K_U "\n" \
         "ds_write2_b64 %3, v[168:169], v[170:171] " V##_F_U "\n" \
         "ds_write_b64 %3, v[172:173] " V##_F_U8 "\n" \
@@ -1525,50 +1648,50 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "ds_read2_b64 v[112:115], " V##_H_U67 "\n" \
         "s_waitcnt lgkmcnt(10)\n" \
         "s_nop 1\n" \
+        "v_fmac_f64_dpp v[128:129], v[160:161], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[130:131], v[162:163], v[140:141] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[128:129], v[154:155], v[132:133] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[130:131], v[154:155], v[132:133] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[128:129], v[156:157], v[134:135] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[130:131], v[156:157], v[134:135] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[130:131], v[158:159], v[136:137] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[128:129], v[160:161], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[130:131], v[162:163], v[140:141] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[116:117], v[154:155], v[132:133] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[120:121], v[154:155], v[132:133] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[120:121], v[158:159], v[136:137] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[174:175], v[128:129] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[176:177], v[128:129] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[178:179], v[130:131] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[122:123], v[154:155], v[132:133] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[122:123], v[160:161], v[138:139] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[174:175]\n" \
-        "v_fmac_f64_dpp v[124:125], v[154:155], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[124:125], v[162:163], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[126:127], v[154:155], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_add_f64 v[126:127], v[126:127], v[142:143]\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
         "v_fmac_f64_dpp v[118:119], v[156:157], v[134:135] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[120:121], v[156:157], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[120:121], v[154:155], v[132:133] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[168:169], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[122:123], v[156:157], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[122:123], v[154:155], v[132:133] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[170:171], v[176:177], v[168:169]\n" \
-        "v_fmac_f64_dpp v[124:125], v[156:157], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[124:125], v[154:155], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[178:179], -v[170:171], v[176:177], v[178:179]\n" \
-        "v_fmac_f64_dpp v[126:127], v[156:157], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[126:127], v[154:155], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[178:179]\n" \
-        "v_fmac_f64_dpp v[120:121], v[158:159], v[136:137] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[120:121], v[156:157], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[124:125], v[158:159], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[124:125], v[156:157], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[126:127], v[158:159], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[126:127], v[156:157], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[122:123], v[160:161], v[138:139] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[122:123], v[156:157], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[172:173], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[126:127], v[160:161], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[126:127], v[158:159], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], v[170:171], v[128:129], -v[130:131]\n" \
-        "v_fmac_f64_dpp v[124:125], v[162:163], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[124:125], v[158:159], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[166:167], v[180:181], v[172:173]\n" \
         "v_mul_f64 v[180:181], v[128:129], v[168:169]\n" \
-        "v_fmac_f64_dpp v[126:127], v[162:163], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[126:127], v[160:161], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[164:165], -v[170:171], v[166:167], -v[180:181]\n" \
-        "v_add_f64 v[126:127], v[126:127], v[142:143]\n" \
+        "v_fmac_f64_dpp v[126:127], v[162:163], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_write2_b64 %2, v[164:165], v[166:167] offset0:0 offset1:8\n" \
         "ds_write2_b64 %3, v[168:169], v[170:171] offset0:0 offset1:1\n" \
         "ds_write_b64 %3, v[172:173] offset:64\n" \
@@ -1633,50 +1756,50 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_fmac_f64_dpp v[142:143], v[124:125], v[152:153] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "s_waitcnt lgkmcnt(3)\n" \
         "s_nop 1\n" \
+        "v_fmac_f64_dpp v[112:113], v[150:151], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[114:115], v[152:153], v[140:141] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[112:113], v[144:145], v[132:133] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[114:115], v[144:145], v[132:133] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[112:113], v[146:147], v[134:135] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[114:115], v[146:147], v[134:135] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[114:115], v[148:149], v[136:137] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[112:113], v[150:151], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[114:115], v[152:153], v[140:141] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[100:101], v[144:145], v[132:133] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[104:105], v[144:145], v[132:133] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[104:105], v[148:149], v[136:137] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[174:175], v[112:113] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[176:177], v[112:113] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
         "v_mov_b64_dpp v[178:179], v[114:115] row_newbcast:7 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[106:107], v[144:145], v[132:133] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[106:107], v[150:151], v[138:139] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[174:175]\n" \
-        "v_fmac_f64_dpp v[108:109], v[144:145], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[152:153], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[110:111], v[144:145], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_add_f64 v[110:111], v[110:111], v[142:143]\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
         "v_fmac_f64_dpp v[102:103], v[146:147], v[134:135] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[104:105], v[146:147], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[104:105], v[144:145], v[132:133] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[168:169], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[106:107], v[146:147], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[106:107], v[144:145], v[132:133] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[170:171], v[176:177], v[168:169]\n" \
-        "v_fmac_f64_dpp v[108:109], v[146:147], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[144:145], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[178:179], -v[170:171], v[176:177], v[178:179]\n" \
-        "v_fmac_f64_dpp v[110:111], v[146:147], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[144:145], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[178:179]\n" \
-        "v_fmac_f64_dpp v[104:105], v[148:149], v[136:137] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[104:105], v[146:147], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[108:109], v[148:149], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[146:147], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[148:149], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[146:147], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
-        "v_fmac_f64_dpp v[106:107], v[150:151], v[138:139] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[106:107], v[146:147], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[172:173], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[150:151], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[148:149], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], v[170:171], v[112:113], -v[114:115]\n" \
-        "v_fmac_f64_dpp v[108:109], v[152:153], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[108:109], v[148:149], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[166:167], v[180:181], v[172:173]\n" \
         "v_mul_f64 v[180:181], v[112:113], v[168:169]\n" \
-        "v_fmac_f64_dpp v[110:111], v[152:153], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
+        "v_fmac_f64_dpp v[110:111], v[150:151], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[164:165], -v[170:171], v[166:167], -v[180:181]\n" \
-        "v_add_f64 v[110:111], v[110:111], v[142:143]\n" \
+        "v_fmac_f64_dpp v[110:111], v[152:153], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_write2_b64 %2, v[164:165], v[166:167] " V##_K_U "\n" \
         "ds_write2_b64 %3, v[168:169], v[170:171] " V##_F_U "\n" \
         "ds_write_b64 %3, v[172:173] " V##_F_U8 "\n" \
@@ -2766,11 +2889,11 @@ sqp_again: ;
         wave_sync();
         MPC_TICK(9);
 #ifdef MPC_FACTOR_PLAIN
-        rowpar_factor(lane, N, RS, sweep_worker);
+        rowpar_factor(lane, N, RS, sweep_worker, dt);
 #else
         if constexpr (COMPACT) {
 #ifdef MPC_COMPACT_PLAIN
-            rowpar_factor(lane, N, RS, sweep_worker);
+            rowpar_factor(lane, N, RS, sweep_worker, dt);
 #else
             rowpar_factor_fast_c(lane, N, RS, sweep_worker);
 #endif

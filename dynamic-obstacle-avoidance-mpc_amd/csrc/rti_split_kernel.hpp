@@ -821,7 +821,7 @@ sqp_again: ;
 #ifdef MPC_MFMA4
         if constexpr (!W2) mfma4_factor(lane, N, RL); else
 #endif
-        rowpar_factor(lane, N, RL, lane < 16);
+        rowpar_factor(lane, N, RL, lane < 16, dt);
         wave_sync();
         if (has_u) {
             const double *ko = RL.R + LT::HS * i;

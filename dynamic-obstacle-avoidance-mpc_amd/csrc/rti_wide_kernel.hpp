@@ -531,7 +531,7 @@ sqp_again: ;
                 }
             }
             wave_sync();
-            rowpar_factor(lane, N, RL, lane < 16);
+            rowpar_factor<RowLds, kSweepTermsParent>(lane, N, RL, lane < 16, dt);      // (the sweep's term order of every earlier build: rti_kernel.hpp)
             wave_sync();
             if (has_u) {
                 const double *ko = RL.R + RowLds::HS * i;
