@@ -5,15 +5,188 @@ Output table columns are the reference's (src/simulation/robot_ocp_problem.py:27
     [hit, reached_goal, min_margin, dist_to_goal, iters, out_of_bounds]
 and `write_experiment` stores them as `;`-separated CSV + spec JSON like experiments.py:40-43, so tooling written for the
 reference's `test_data/` (evaluate_experiments.py:8-18) reads them.
+
+The two drivers, run_episodes (one batch) and run_seed_sweep (seeds streaming through slots), share the pieces below them: _HandleLease owns what a driver
+borrows on a handle, step_flags / refill_flags / result_table are the reference's protocol in one place each.
 """
 import json
 import os
 import time
+import warnings
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _lib
-from .solver import BOUNDS_ROW, BatchedMpc, pack_instance_bounds, pack_obstacle_mask
+from .solver import BOUNDS_ROW, INSTANCE_ROW, BatchedMpc, instance_rows, mask_rows, pack_instance_bounds, pack_obstacle_mask
+
+
+class _HandleLease:
+    """The one owner of what a driver borrows on a handle (pure Python: anything with the setters' names will do as a solver).  `solver` is a caller's
+    handle or None; then the lease makes one of its own with `make()`.  Inside `with` the handle is `.m`, and every mutation of it goes through attach(),
+    which registers the setter's off call as soon as the setter has returned.  On exit, normal or by exception, in this order: the driver's stream (`.stream`,
+    if one was given) is synchronised -- the handle must not lose pointers a queued launch still reads, nor the tensors die before that --; the features are
+    switched off in reverse order of attachment; the handle is closed if and only if the lease made it.  Off means off: a caller's earlier setting of the
+    same feature is not re-created.  A step of the exit that raises does not stop the steps behind it, and the first exception (the block's own, if it
+    raised) is the one that leaves."""
+    OFF = {"set_instance_params": (), "set_obstacle_mask": (None,), "set_instance_bounds": (), "set_instance_bounds_dev": (None,), "set_sqp": (),
+           "set_refill_tables_dev": (), "episode_ring_dev": (0,), "episode_trace_set_dev": (0,)}
+
+    def __init__(self, solver, make, stream=None):
+        self._solver, self._make, self.stream, self._attached = solver, make, stream, []
+
+    def __enter__(self):
+        self.m = self._make() if self._solver is None else self._solver
+        return self
+
+    def attach(self, setter, *args, **kw):
+        """m.<setter>(*args, **kw), undone on exit by the setter's off call (a setter without one is a KeyError, and not called); the arguments -- tensors
+        the handle then points into -- are kept until then"""
+        off = self.OFF[setter]
+        getattr(self.m, setter)(*args, **kw)
+        self._attached.append((setter, off, args, kw))
+
+    def __exit__(self, exc_type, exc, tb):
+        steps = ([] if self.stream is None else [self.stream.synchronize]) + [lambda n=n, off=off: getattr(self.m, n)(*off) for n, off, _, _ in reversed(self._attached)]
+        first = exc
+        for step in steps + ([self.m.close] if self._solver is None else []):
+            try:
+                step()
+            except Exception as e:
+                first = e if first is None else first
+        if first is not exc:
+            raise first
+
+
+def step_flags(init_guess_when_error=True, bug_compat_alias=True, interpolate_init=False, margin_all=False):
+    """the fused control step's flag word (_lib.STEP_*) for the drivers' switches; margin_all counts only together with an obstacle mask"""
+    fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS | (_lib.STEP_MARGIN_ALL if margin_all else 0)
+    if init_guess_when_error:
+        fl |= _lib.STEP_RESET_ON_FAIL | (_lib.STEP_ALIAS_BUG if bug_compat_alias else 0) | (_lib.STEP_INTERP_GUESS if interpolate_init else 0)
+    return fl
+
+
+def refill_flags(bug_compat_alias=True, interpolate_init=False, random_move=True):
+    """the refill's flag word (_lib.REFILL_*) for the same switches"""
+    return (_lib.REFILL_ALIAS_BUG if bug_compat_alias else 0) | (_lib.REFILL_INTERP_GUESS if interpolate_init else 0) | (_lib.REFILL_DRAW_NOISE if random_move else 0)
+
+
+def _warn_interpolate_alias(interpolate_init, bug_compat_alias):
+    """the drivers' warning about interpolate_init together with bug_compat_alias, attributed to the driver's caller"""
+    if interpolate_init and bug_compat_alias:
+        warnings.warn("interpolate_init with bug_compat_alias=True: the straight-line guess is built from a plant state whose v, omega the aliasing defect has "
+                      "zeroed; the two recorded `interpolate_init` tables replay with bug_compat_alias=False (tests/test_gpu_replay.py)", stacklevel=3)
+
+
+def result_table(ep_flags, min_margin, x_last, goal, steps):
+    """the (rows, 6) table [hit, reached, min_margin, dist_to_goal, iters, out_of_bounds] from flag words, margins, last states, goals and step counts;
+    the solves behind it are table[:, 4] + table[:, 1]: every episode's control steps, plus the one that reached the goal"""
+    return np.column_stack([(ep_flags & 4) != 0, (ep_flags & 1) != 0, min_margin, np.linalg.norm(x_last[:, :2] - goal, axis=1), steps, (ep_flags & 2) != 0]).astype(np.float64)
+
+
+def _loop_arrays(torch, dev, rows, N, n_obst, flags0):
+    """what a fused control step of `rows` instances works on beside x0, goal and obst (the driver's to fill in): iterate, status words, episode bookkeeping;
+    with them the two kinds of array (.f64, .i32: keywords for torch's constructors) and the device generator's arrays, None until a driver makes them"""
+    f64 = dict(dtype=torch.float64, device=dev); i32 = dict(dtype=torch.int32, device=dev)
+    return SimpleNamespace(rows=rows, f64=f64, i32=i32, X=torch.zeros(rows, N + 1, 5, **f64), U=torch.zeros(rows, N, 2, **f64), status=torch.zeros(rows, **i32),
+                           iters=torch.zeros(rows, **i32), margin=torch.full((rows,), float("inf"), **f64), flags=torch.full((rows,), flags0, **i32),
+                           steps=torch.zeros(rows, **i32), gen_state=None, nbuf=None)
+
+
+def _fused_step(m, a, fl, noise, s, u0=None):
+    """one fused control step on the arrays `a`"""
+    m.closed_loop_step_dev(a.rows, a.x0, a.obst, a.goal, a.X, a.U, u0, None, a.status, a.iters, noise, flags=fl, min_margin=a.margin, ep_flags=a.flags, ep_steps=a.steps, stream=s)
+
+
+def _episode_noise(noise, scenario_name, seed, random_move, max_iter, B, n_obst):
+    """run_episodes' `noise` and `seed`, checked on the host before anything touches a device.  Returns the source of the normals: None (the obstacles do not
+    draw), "reference", "torch" or the float64 array (>= max_iter, B, n_obst, 2)."""
+    if scenario_name is not None and noise is None and random_move:
+        noise = "reference"
+        if seed != 0:
+            raise ValueError("`seed` selects torch's generator, which a scenario name does not use: the obstacle noise is the reference's own numpy stream "
+                             "per instance (first_seed + s).  Vary first_seed, or pass noise='torch' to draw from torch's generator with this seed")
+    noise = "torch" if noise is None else noise
+    if isinstance(noise, str):
+        if noise != "torch" and (noise != "reference" or scenario_name is None):
+            raise ValueError("noise='reference' continues the generator of a scenario draw: pass the scenario name as `obst`")
+    elif random_move:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+        if noise.shape[1:] != (B, n_obst, 2) or noise.shape[0] < max_iter:
+            raise ValueError(f"noise must be (>= {max_iter}, {B}, {n_obst}, 2), got {noise.shape}")
+    return noise if random_move else None
+
+
+def _noise_source(torch, m, a, noise, scenario_name, first_seed, seed, s):
+    """run_episodes' normals as a function of the control step k, over the batch `a` as it is at that step (compaction shrinks it); allocates what the
+    source needs (a.gen_state, a.nbuf: the device generator's states and its output)"""
+    n_obst = a.obst.shape[1]
+    if noise is None:
+        return lambda k: None
+    if isinstance(noise, np.ndarray):
+        dnoise = torch.from_numpy(noise).to(a.obst.device)
+        return lambda k: dnoise[k] if a.rows == dnoise.shape[1] else dnoise[k][a.ids]
+    if noise == "torch":
+        gen = torch.Generator(device=a.obst.device); gen.manual_seed(seed)
+        return lambda k: torch.randn(a.rows, n_obst, 2, generator=gen, **a.f64)
+    a.gen_state = m.noise_state(a.rows, scenario_name, seed0=first_seed, stream=s)
+    a.nbuf = torch.zeros(a.rows, n_obst, 2, **a.f64)
+
+    def draw(k):
+        m.noise_draw_dev(a.rows, a.gen_state, a.nbuf, ep_flags=a.flags, stream=s)
+        return a.nbuf
+    return draw
+
+
+_PARKED = ("margin", "flags", "steps", "x0")          # what compaction keeps of a finished episode
+
+
+def _compact(a, full):
+    """run_episodes' compaction step: once a quarter of the batch `a` has finished, the results of the finished episodes are parked in `full` under their
+    ids and the live ones move together (device-side gathers).  False: no episode is live."""
+    live = (a.flags & 1) == 0
+    n_live = int(live.sum().item())                 # (the one host read: at these batch sizes 25 control steps take tens of milliseconds)
+    if n_live == 0:
+        return False
+    if n_live <= 0.75 * a.rows:
+        park = a.ids[~live]
+        for n in _PARKED:
+            full[n][park] = getattr(a, n)[~live]
+        for n in ("ids", "x0", "goal", "obst", "X", "U", "status", "iters", "margin", "flags", "steps") + (("gen_state", "nbuf") if a.gen_state is not None else ()):
+            setattr(a, n, getattr(a, n)[live].contiguous())
+        a.rows = n_live
+    return True
+
+
+def _episode_loop(torch, m, a, draw, fl, max_iter, stream, log=None, rec=None, full=None):
+    """run_episodes' control steps: noise draw, fused step, the status log (torch ops on `log`), the clones of the record `rec`, the done-flag copy, the
+    compaction gathers (into `full`), until every episode has reached its goal or max_iter steps are spent.  Returns the steps launched."""
+    # "every instance has reached its goal" without stalling the queue: every 25 control steps the flag goes to pinned host memory behind an event,
+    # and is looked at only once that event has passed (so the loop runs at most ~25 steps longer than it has to -- on idle instances, which cost nothing)
+    done_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+    done_event = None
+    k = 0
+    while k < max_iter:
+        _fused_step(m, a, fl, draw(k), stream.cuda_stream)
+        if log is not None:      # (an episode that has reached its goal idles: its status word keeps the last solve's value and is not counted again)
+            live = (a.steps + (a.flags & 1)) > k
+            log.n2 += (live & (a.status == 2)).int(); log.n4 += (live & (a.status == 4)).int()
+            log.first_bad = torch.where(live & (a.status != 0) & (log.first_bad < 0), torch.full_like(log.first_bad, k), log.first_bad)
+        k += 1
+        if rec is not None:      # X holds the shifted prediction: stage j of the solve is X[j - 1], stage N is kept (:253-258)
+            rec.x.append(a.x0.clone()); rec.o.append(a.obst.clone()); rec.p.append(a.X.clone())
+        if done_event is not None and done_event.query():
+            if int(done_host[0]) == 1:
+                break
+            done_event = None
+        if full is not None and k % 25 == 0:
+            if not _compact(a, full):
+                break
+            continue
+        if k % 25 == 0 and done_event is None:
+            done_host.copy_((a.flags & 1).min().to(torch.int32).reshape(1), non_blocking=True)
+            done_event = torch.cuda.Event(); done_event.record(stream)
+    return k
 
 
 def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, init_guess_when_error=True,
@@ -47,153 +220,66 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
     episode b is solved inside its own actuator and speed limits.  Episodes with bounds of their own are not compacted.
     sqp: optional (max_iter, step_tol) (BatchedMpc.set_sqp): every control step runs up to max_iter SQP iterations in its one launch.  Compaction stays on:
     the setting is per handle, not per episode.
+    solver: a caller's handle to run on.  It leaves as it came whether the call returns or raises (_HandleLease): radii, mask, bounds and SQP setting of this
+    call are switched OFF again -- a setting of the same feature the caller had made before is not re-created.  The arguments that need no device (noise, seed)
+    are checked before the handle is touched.
     Returns dict(table (B,6), x_last (B,5), steps_run, solves)."""
-    import torch
     x0 = np.ascontiguousarray(x0, dtype=np.float64); B = x0.shape[0]
     scenario_name = obst if isinstance(obst, str) else None
-    if interpolate_init and bug_compat_alias:
-        import warnings
-        warnings.warn("interpolate_init with bug_compat_alias=True: the straight-line guess is built from a plant state whose v, omega the aliasing defect has "
-                      "zeroed; the two recorded `interpolate_init` tables replay with bug_compat_alias=False (tests/test_gpu_replay.py)", stacklevel=2)
+    if scenario_name is None:
+        obst = np.ascontiguousarray(obst, dtype=np.float64); n_obst = obst.shape[1]
+    _warn_interpolate_alias(interpolate_init, bug_compat_alias)
+    noise = _episode_noise(noise, scenario_name, seed, random_move, max_iter, B, n_obst)
+    import torch
     if scenario_name is not None:
-        if noise is None and random_move:
-            noise = "reference"
-            if seed != 0:
-                raise ValueError("`seed` selects torch's generator, which a scenario name does not use: the obstacle noise is the reference's own numpy stream "
-                                 "per instance (first_seed + s).  Vary first_seed, or pass noise='torch' to draw from torch's generator with this seed")
         with BatchedMpc(N, n_obst, Tf, max_batch=B, device=device) as g:
-            obst = g.generate_scenarios(obst, B, seed0=first_seed)
-    obst = np.ascontiguousarray(obst, dtype=np.float64); n_obst = obst.shape[1]
+            obst = np.ascontiguousarray(g.generate_scenarios(scenario_name, B, seed0=first_seed), dtype=np.float64)
     goal = np.ascontiguousarray(np.broadcast_to(goal, (B, 2)), dtype=np.float64)
     dev = torch.device("cuda", device)
-    m = solver or BatchedMpc(N, n_obst, Tf, max_batch=B, device=device, **cfg)
-    own_radii = r_safe is not None or r_hit is not None
-    if own_radii:
-        m.set_instance_params(r_safe=r_safe, r_hit=r_hit)
-    own_mask = active is not None
-    if own_mask:
-        m.set_obstacle_mask(np.asarray(active))
-    own_bounds = bounds is not None
-    if own_bounds:
-        m.set_instance_bounds(**bounds)
-    own_sqp = sqp is not None
-    if own_sqp:
-        m.set_sqp(*sqp)
-    stream = torch.cuda.Stream(device=dev)
-    with torch.cuda.stream(stream):
-        t = lambda a: torch.from_numpy(a.copy()).to(dev)
-        dx0, dgoal, dobst = t(x0), t(goal), t(obst)
-        if bug_compat_alias:                      # set_initial_guess() aliases self.x0 and zeroes v, omega (defect D2)
-            dx0[:, 3:] = 0.0
-        X = torch.zeros(B, N + 1, 5, dtype=torch.float64, device=dev); U = torch.zeros(B, N, 2, dtype=torch.float64, device=dev)
-        status = torch.zeros(B, dtype=torch.int32, device=dev); iters = torch.zeros(B, dtype=torch.int32, device=dev)
-        margin = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
-        flags = torch.zeros(B, dtype=torch.int32, device=dev); steps = torch.zeros(B, dtype=torch.int32, device=dev)
-        s = stream.cuda_stream
-        if interpolate_init:
-            m.reset_guess_interp_dev(B, dx0, dgoal, X, U, stream=s)
-        else:
-            m.reset_guess_dev(B, dx0, X, U, stream=s)        # set_initial_guess() at the start of step(), :180
-        fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS
-        if init_guess_when_error:
-            fl |= _lib.STEP_RESET_ON_FAIL | (_lib.STEP_ALIAS_BUG if bug_compat_alias else 0) | (_lib.STEP_INTERP_GUESS if interpolate_init else 0)
-        if own_mask and margin_all:
-            fl |= _lib.STEP_MARGIN_ALL
-        if status_log:
-            n2 = torch.zeros(B, dtype=torch.int32, device=dev); n4 = torch.zeros(B, dtype=torch.int32, device=dev)
-            first_bad = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        gen = torch.Generator(device=dev); gen.manual_seed(seed)
-        dnoise = None
-        gen_state, nbuf = None, None
-        if isinstance(noise, str) and noise == "torch":
-            noise = None
-        if isinstance(noise, str):
-            if noise != "reference" or scenario_name is None:
-                raise ValueError("noise='reference' continues the generator of a scenario draw: pass the scenario name as `obst`")
-            if random_move:
-                gen_state = m.noise_state(B, scenario_name, seed0=first_seed, stream=s)
-                nbuf = torch.zeros(B, n_obst, 2, dtype=torch.float64, device=dev)
-        elif noise is not None and random_move:
-            noise = np.ascontiguousarray(noise, dtype=np.float64)
-            if noise.shape[1:] != (B, n_obst, 2) or noise.shape[0] < max_iter:
-                raise ValueError(f"noise must be (>= {max_iter}, {B}, {n_obst}, 2), got {noise.shape}")
-            dnoise = torch.from_numpy(noise).to(dev)
-        k = 0
-        # compaction of finished episodes (compact_from): results of parked episodes live in full-size arrays, `ids` maps the live batch to them
-        compact = compact_from is not None and B >= compact_from and not record and not status_log and not own_radii and not own_mask and not own_bounds
-        B0 = B
-        if compact:
-            ids = torch.arange(B, device=dev)
-            full = dict(margin=margin.clone(), flags=flags.clone(), steps=steps.clone(), x=dx0.clone())
-        rec_x, rec_o, rec_p = [dx0.clone()], [dobst.clone()], []
-        # "every instance has reached its goal" without stalling the queue: every 25 control steps the flag goes to pinned host memory behind an event,
-        # and is looked at only once that event has passed (so the loop runs at most ~25 steps longer than it has to -- on idle instances, which cost nothing)
-        done_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        done_event = None
-        while k < max_iter:
-            if not random_move:
-                nz = None
-            elif gen_state is not None:
-                m.noise_draw_dev(B, gen_state, nbuf, ep_flags=flags, stream=s); nz = nbuf
-            elif dnoise is not None:
-                nz = dnoise[k] if B == B0 else dnoise[k][ids]
+    with _HandleLease(solver, lambda: BatchedMpc(N, n_obst, Tf, max_batch=B, device=device, **cfg)) as lease:
+        m = lease.m
+        own_features = False            # radii, mask or bounds per episode: such a batch is not compacted
+        if r_safe is not None or r_hit is not None:
+            lease.attach("set_instance_params", r_safe=r_safe, r_hit=r_hit); own_features = True
+        if active is not None:
+            lease.attach("set_obstacle_mask", np.asarray(active)); own_features = True
+        if bounds is not None:
+            lease.attach("set_instance_bounds", **bounds); own_features = True
+        if sqp is not None:
+            lease.attach("set_sqp", *sqp)
+        lease.stream = stream = torch.cuda.Stream(device=dev)
+        with torch.cuda.stream(stream):
+            t = lambda h: torch.from_numpy(h.copy()).to(dev)
+            a = _loop_arrays(torch, dev, B, N, n_obst, 0)
+            a.x0, a.goal, a.obst = t(x0), t(goal), t(obst)
+            if bug_compat_alias:                      # set_initial_guess() aliases self.x0 and zeroes v, omega (defect D2)
+                a.x0[:, 3:] = 0.0
+            s = stream.cuda_stream
+            if interpolate_init:
+                m.reset_guess_interp_dev(B, a.x0, a.goal, a.X, a.U, stream=s)
             else:
-                nz = torch.randn(B, n_obst, 2, dtype=torch.float64, device=dev, generator=gen)
-            m.closed_loop_step_dev(B, dx0, dobst, dgoal, X, U, None, None, status, iters, nz, flags=fl,
-                                   min_margin=margin, ep_flags=flags, ep_steps=steps, stream=s)
-            if status_log:      # (an episode that has reached its goal idles: its status word keeps the last solve's value and is not counted again)
-                live = (steps + (flags & 1)) > k
-                n2 += (live & (status == 2)).int(); n4 += (live & (status == 4)).int()
-                first_bad = torch.where(live & (status != 0) & (first_bad < 0), torch.full_like(first_bad, k), first_bad)
-            k += 1
-            if record:      # X holds the shifted prediction: stage j of the solve is X[j - 1], stage N is kept (:253-258)
-                rec_x.append(dx0.clone()); rec_o.append(dobst.clone()); rec_p.append(X.clone())
-            if done_event is not None and done_event.query():
-                if int(done_host[0]) == 1:
-                    break
-                done_event = None
-            if compact and k % 25 == 0:
-                live = (flags & 1) == 0
-                n_live = int(live.sum().item())                 # (the one host read: at these batch sizes 25 control steps take tens of milliseconds)
-                if n_live == 0:
-                    break
-                if n_live <= 0.75 * B:
-                    park = ids[~live]
-                    full["margin"][park] = margin[~live]; full["flags"][park] = flags[~live]; full["steps"][park] = steps[~live]; full["x"][park] = dx0[~live]
-                    take = lambda a: a[live].contiguous()
-                    ids, dx0, dgoal, dobst, X, U = take(ids), take(dx0), take(dgoal), take(dobst), take(X), take(U)
-                    status, iters, margin, flags, steps = take(status), take(iters), take(margin), take(flags), take(steps)
-                    if gen_state is not None:
-                        gen_state, nbuf = take(gen_state), take(nbuf)
-                    B = n_live
-                continue
-            if k % 25 == 0 and done_event is None:
-                done_host.copy_((flags & 1).min().to(torch.int32).reshape(1), non_blocking=True)
-                done_event = torch.cuda.Event(); done_event.record(stream)
-        stream.synchronize()
-        if compact:
-            full["margin"][ids] = margin; full["flags"][ids] = flags; full["steps"][ids] = steps; full["x"][ids] = dx0
-            margin, flags, steps, dx0 = full["margin"], full["flags"], full["steps"], full["x"]
-        fl_h = flags.cpu().numpy(); xl = dx0.cpu().numpy()
-        table = np.column_stack([(fl_h & 4) != 0, (fl_h & 1) != 0, margin.cpu().numpy(),
-                                 np.linalg.norm(xl[:, :2] - goal, axis=1), steps.cpu().numpy(), (fl_h & 2) != 0]).astype(np.float64)
-        extra = {}
-        if record:
-            extra = dict(simX=torch.stack(rec_x).cpu().numpy(), obst_traj=torch.stack(rec_o).cpu().numpy(), pred=torch.stack(rec_p).cpu().numpy())
-        if status_log:
-            extra.update(status2=n2.cpu().numpy(), status4=n4.cpu().numpy(), first_bad=first_bad.cpu().numpy())
-    if solver is None:
-        m.close()
-    else:                            # (a caller's solver leaves as it came)
-        if own_radii:
-            m.set_instance_params()
-        if own_mask:
-            m.set_obstacle_mask(None)
-        if own_bounds:
-            m.set_instance_bounds()
-        if own_sqp:
-            m.set_sqp()
-    return dict(table=table, x_last=xl, steps_run=k, solves=int(steps.sum().item()) + int((fl_h & 1).sum()), **extra)
+                m.reset_guess_dev(B, a.x0, a.X, a.U, stream=s)        # set_initial_guess() at the start of step(), :180
+            fl = step_flags(init_guess_when_error, bug_compat_alias, interpolate_init, margin_all and active is not None)
+            log = SimpleNamespace(n2=torch.zeros(B, **a.i32), n4=torch.zeros(B, **a.i32), first_bad=torch.full((B,), -1, **a.i32)) if status_log else None
+            draw = _noise_source(torch, m, a, noise, scenario_name, first_seed, seed, s)
+            # compaction of finished episodes (compact_from): results of parked episodes live in full-size arrays, `ids` maps the live batch to them
+            full = None
+            if compact_from is not None and B >= compact_from and not record and not status_log and not own_features:
+                a.ids = torch.arange(B, device=dev)
+                full = {n: getattr(a, n).clone() for n in _PARKED}
+            rec = SimpleNamespace(x=[a.x0.clone()], o=[a.obst.clone()], p=[]) if record else None
+            k = _episode_loop(torch, m, a, draw, fl, max_iter, stream, log=log, rec=rec, full=full)
+            stream.synchronize()
+            if full is not None:
+                for n in _PARKED:
+                    full[n][a.ids] = getattr(a, n)
+                a = SimpleNamespace(**full)
+            fl_h = a.flags.cpu().numpy(); xl = a.x0.cpu().numpy()
+            table = result_table(fl_h, a.margin.cpu().numpy(), xl, goal, a.steps.cpu().numpy())
+            extra = dict(simX=torch.stack(rec.x).cpu().numpy(), obst_traj=torch.stack(rec.o).cpu().numpy(), pred=torch.stack(rec.p).cpu().numpy()) if record else {}
+            if status_log:
+                extra.update(status2=log.n2.cpu().numpy(), status4=log.n4.cpu().numpy(), first_bad=log.first_bad.cpu().numpy())
+    return dict(table=table, x_last=xl, steps_run=k, solves=int(table[:, 4].sum() + table[:, 1].sum()), **extra)
 
 
 def refill_schedule(lengths, slots):
@@ -254,8 +340,7 @@ def _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every):
         if a.shape == (cols,) or a.shape == (1, cols):
             per.append(False)
         elif a.ndim == 2 and a.shape[1] == cols:
-            if a.shape[0] != count:
-                raise ValueError(f"per-seed {name} has {a.shape[0]} rows for {count} seeds")
+            _seed_rows(name, a, count)
             per.append(True)
         else:
             raise ValueError(f"{name} must be ({cols},) or (count, {cols}), got {a.shape}")
@@ -287,32 +372,29 @@ def ring_model(schedule_start, capacity, every):
     return (np.arange(start.size) < handed + int(capacity)).astype(np.int32)
 
 
+def _seed_rows(name, a, count):
+    """a per-seed array `a` holds one row per seed"""
+    if a.shape[0] != count:
+        raise ValueError(f"per-seed {name} has {a.shape[0]} rows for {count} seeds")
+    return a
+
+
 def _sweep_features(count, n_obst, handle_cfg, r_safe=None, r_hit=None, W=None, We=None, active=None, margin_all=False, bounds=None, status_log=False,
                     ring=None, ring_every=None, poll_every=25):
-    """run_seed_sweep's per-seed arguments, checked on the host by the setters' own rules before anything touches a device.  handle_cfg: an object with the
+    """run_seed_sweep's per-seed arguments, checked on the host before anything touches a device: shapes by the setters' own rules (solver.instance_rows,
+    mask_rows, pack_instance_bounds), values here, because the tables go to the _dev setters, which validate nothing.  handle_cfg: an object with the
     handle's bx_lo, bx_hi, bu_lo, bu_hi (an MpcConfig, or a dict over DEFAULT_BOUNDS).  Returns dict(W, We, r_safe, r_hit (float64 (count, .) or None),
     mask (int32 words (count,) or None), bounds (float64 (count, 12) or None), margin_all, status_log, ring (capacity or None), ring_every)."""
     out = dict(margin_all=bool(margin_all), status_log=bool(status_log))
-    for name, a, cols, low, open_ in (("W", W, 6, 0.0, False), ("We", We, 4, 0.0, False), ("r_safe", r_safe, n_obst, 0.0, True), ("r_hit", r_hit, n_obst, 0.0, True)):
+    for (name, cols), a in zip(INSTANCE_ROW, (W, We, r_safe, r_hit)):
         if a is not None:
-            a = np.asarray(a, dtype=np.float64)
-            if a.ndim == 1 and name in ("r_safe", "r_hit"):
-                a = np.repeat(a[:, None], n_obst, axis=1)
-            if a.ndim != 2 or a.shape[1] != cols:
-                raise ValueError(f"{name} must be (count, {cols})" + (" or (count,)" if name in ("r_safe", "r_hit") else "") + f", got {a.shape}")
-            if a.shape[0] != count:
-                raise ValueError(f"per-seed {name} has {a.shape[0]} rows for {count} seeds")
-            if not np.isfinite(a).all() or not ((a > low) if open_ else (a >= low)).all():
-                raise ValueError(f"per-seed {name} must be finite and " + ("> 0" if open_ else ">= 0"))
-            a = np.ascontiguousarray(a)
+            a = _seed_rows(name, instance_rows(name, a, cols, n_obst, rows="count"), count)
+            if not np.isfinite(a).all() or not ((a > 0.0) if cols is None else (a >= 0.0)).all():          # (cols None: a radius)
+                raise ValueError(f"per-seed {name} must be finite and " + ("> 0" if cols is None else ">= 0"))
         out[name] = a
     out["mask"] = None
     if active is not None:
-        a = np.asarray(active)
-        if a.ndim != 2 or a.shape[1] != n_obst:
-            raise ValueError(f"active must be (count, {n_obst}), got {a.shape}: a mask has no bit at or above n_obst")
-        if a.shape[0] != count:
-            raise ValueError(f"per-seed active has {a.shape[0]} rows for {count} seeds")
+        a = _seed_rows("active", mask_rows(active, n_obst, rows="count", why=": a mask has no bit at or above n_obst"), count)
         out["mask"] = pack_obstacle_mask(a).view(np.int32)
     out["bounds"] = None
     if bounds is not None:
@@ -323,13 +405,13 @@ def _sweep_features(count, n_obst, handle_cfg, r_safe=None, r_hit=None, W=None, 
             raise ValueError("bounds names no group")
         for n, v in given.items():
             v = np.asarray(v, dtype=np.float64)
-            if v.ndim == 2 and v.shape[0] != count:
-                raise ValueError(f"per-seed {n} has {v.shape[0]} rows for {count} seeds")
+            if v.ndim == 2:
+                _seed_rows(n, v, count)
             if not np.isfinite(v).all():
                 raise ValueError(f"bounds: {n} entries must be finite")
         get = (lambda n: handle_cfg[n]) if isinstance(handle_cfg, dict) else (lambda n: list(getattr(handle_cfg, n)))
         own = type("Cfg", (), {n: get(n) for n, _, _ in BOUNDS_ROW})
-        tab = pack_instance_bounds(own, count, **given)
+        tab = pack_instance_bounds(own, count, rows="count", **given)
         at = {n: (c0, c) for n, c0, c in BOUNDS_ROW}
         for lo, hi in (("bu_lo", "bu_hi"), ("bx_lo", "bx_hi")):
             if not (tab[:, at[lo][0]:at[lo][0] + at[lo][1]] < tab[:, at[hi][0]:at[hi][0] + at[hi][1]]).all():
@@ -386,6 +468,145 @@ def _sweep_trace(count, max_iter, N, n_obst, trace=None, trace_pred=True, trace_
     return dict(seeds=seeds, seed_row=seed_row, pred=bool(trace_pred), bytes=need)
 
 
+def _sweep_slots(torch, dev, m, S, count, start, goal, random_move):
+    """the sweep's device state: the start and goal rows, the per-slot arrays of mpc_episode_refill_dev for S slots, its cursor and the result rows of
+    `count` seeds"""
+    a = _loop_arrays(torch, dev, S, m.N, m.n_obst, 1)          # every slot "finished" and without a seed: the first refill fills them all
+    a.count = count
+    a.start_rows, a.goal_rows = torch.from_numpy(start).to(dev), torch.from_numpy(goal).to(dev)
+    a.x0 = torch.zeros(S, 5, **a.f64); a.goal = torch.zeros(S, 2, **a.f64); a.obst = torch.zeros(S, m.n_obst, 4, **a.f64)
+    a.slot_seed = torch.full((S,), -1, **a.i32); a.cursor = torch.zeros(2, **a.i32)
+    a.gen_state = torch.zeros(S, _lib.lib().mpc_noise_state_words(), **a.i32)
+    a.nbuf = torch.zeros(S, m.n_obst, 2, **a.f64) if random_move else None
+    a.res_f = torch.full((count, 6), float("nan"), **a.f64); a.res_i = torch.full((count, 2), -1, **a.i32)
+    return a
+
+
+def _attach_tables(lease, torch, a, ft):
+    """per-seed tables: the sources (count rows) and the per-slot arrays the solve reads in place (max_batch rows, preset with the handle's own values: a
+    slot that never gets a seed holds valid numbers), registered with the _dev setters; the refill copies row k into the slot that starts k.  With them the
+    status log's per-slot words and result rows.  Returns the tensors by their names in set_refill_tables_dev ({}: nothing to attach)."""
+    m, dev = lease.m, a.x0.device
+    MB, n_obst = m.max_batch, m.n_obst
+    tabs = {}
+    if any(ft[n] is not None for n, _ in INSTANCE_ROW):
+        r_hit_own = 1.0 + 0.2                               # o.r + R_ROBOT: the fused step's hit radius (mpc_closed_loop_step_dev)
+        preset = dict(W=list(m.cfg.W), We=list(m.cfg.We), r_safe=[m.cfg.r_safe] * n_obst, r_hit=[r_hit_own] * n_obst)
+        slot = {}
+        for name, _ in INSTANCE_ROW:
+            if ft[name] is not None:
+                tabs[name] = torch.from_numpy(ft[name]).to(dev)
+                slot[name] = tabs["slot_" + name] = torch.tensor(preset[name], **a.f64).repeat(MB, 1).contiguous()
+        lease.attach("set_instance_params", **slot)
+    if ft["mask"] is not None:
+        tabs["mask"] = torch.from_numpy(ft["mask"].copy()).to(dev)
+        tabs["slot_mask"] = torch.full((MB,), int(np.array([(1 << n_obst) - 1], dtype=np.uint32).view(np.int32)[0]), **a.i32)
+        lease.attach("set_obstacle_mask", tabs["slot_mask"])
+    if ft["bounds"] is not None:
+        tabs["bounds"] = torch.from_numpy(ft["bounds"]).to(dev)
+        tabs["slot_bounds"] = torch.from_numpy(pack_instance_bounds(m.cfg, MB)).to(dev)
+        lease.attach("set_instance_bounds_dev", tabs["slot_bounds"])
+    if ft["status_log"]:
+        tabs["log"] = torch.tensor([0, 0, -1, 0], **a.i32).repeat(a.rows, 1).contiguous()
+        tabs["res_log"] = torch.full((a.count, 3), -1, **a.i32)
+    if tabs:
+        lease.attach("set_refill_tables_dev", **tabs)
+    return tabs
+
+
+def _attach_ring(lease, torch, a, capacity):
+    """the ring of seeded episodes (mpc_episode_ring_dev) for the slots `a`.  Returns its tensors: dict(ring_state, ring_obst, ring_tag, seed_src)"""
+    ring = dict(ring_state=torch.zeros(capacity, a.gen_state.shape[1], **a.i32), ring_obst=torch.zeros(capacity, lease.m.n_obst, 4, **a.f64),
+                ring_tag=torch.full((capacity,), -1, **a.i32), seed_src=torch.full((a.count,), -1, **a.i32))
+    lease.attach("episode_ring_dev", capacity, **ring)
+    return ring
+
+
+def _attach_trace(lease, torch, a, tr, max_iter):
+    """the per-seed rows (mpc_episode_trace) for the slots `a`: row r belongs to seed index tr["seeds"][r].  Returns (the arrays by their names in
+    episode_trace_set_dev, the u* array (slots, 2) the fused step then writes)"""
+    R, N, n_obst, f64, i32 = tr["seeds"].size, lease.m.N, lease.m.n_obst, a.f64, a.i32
+    tarr = dict(seed_row=torch.from_numpy(tr["seed_row"]).to(a.x0.device), slot_state=torch.tensor([-1, 0], **i32).repeat(a.rows, 1).contiguous(),
+                len=torch.zeros(R, **i32), x=torch.zeros(R, max_iter + 1, 5, **f64), obst=torch.zeros(R, max_iter + 1, n_obst, 4, **f64),
+                u=torch.zeros(R, max_iter, 2, **f64), status=torch.zeros(R, max_iter, **i32), iters=torch.zeros(R, max_iter, **i32),
+                pred=torch.zeros(R, max_iter, N + 1, 5, **f64) if tr["pred"] else None)
+    u0 = torch.zeros(a.rows, 2, **f64)
+    lease.attach("episode_trace_set_dev", R, max_iter, **tarr)
+    return tarr, u0
+
+
+def _sweep_loop(torch, m, a, stream, scenario, first, per_seed, max_iter, poll_every, bound, fl, rf, ring_every=None, log=None, u0=None):
+    """the sweep's control steps, each one: ring fill (every ring_every steps; None: no ring), refill, poll copy, trace START (u0 given: a trace is attached),
+    fused step, status log (log given), trace STEP -- until the poll sees no live slot, or `bound` steps are spent whatever the device returns.
+    Returns (the fused steps launched, the schedule (count, 2) with poll_every = 1 or None)."""
+    s = stream.cuda_stream
+    schedule = np.full((a.count, 2), -1, dtype=np.int64) if poll_every == 1 else None
+    seen = np.full(a.rows, -1, dtype=np.int64)
+    live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
+    live_event = None
+    k = 0
+    while True:
+        if ring_every is not None and k % ring_every == 0:
+            m.episode_ring_fill_dev(scenario, first, a.count, a.cursor, stream=s)
+        m.episode_refill_dev(a.rows, scenario, first, a.count, max_iter, a.start_rows, a.goal_rows, per_seed, a.x0, a.obst, a.goal, a.X, a.U, a.margin, a.flags,
+                             a.steps, a.gen_state, a.nbuf, a.slot_seed, a.cursor, a.res_f, a.res_i, flags=rf, stream=s)
+        if poll_every == 1:
+            now = a.slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
+            new = (now != seen) & (now >= 0)
+            schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
+            seen = now
+            if int(a.cursor[1].item()) == 0:
+                break
+        elif k % poll_every == 0:
+            # the count of the poll before this one, which the device passed long ago: the host stays at most two polls ahead of the device (no idle
+            # steps by the hundred behind the end of the sweep) and the device always has a poll's worth of steps queued (it never waits for the host)
+            if live_event is not None:
+                live_event.synchronize()
+                if int(live_host[0]) == 0:
+                    break
+            live_host.copy_(a.cursor[1:2], non_blocking=True)
+            live_event = torch.cuda.Event(); live_event.record(stream)
+        if k >= bound:
+            break
+        if u0 is not None:           # the state every seed that has just started starts from: behind the refill, in front of the step
+            m.episode_trace_dev(a.rows, _lib.TRACE_START, a.slot_seed, a.x0, a.obst, ep_flags=a.flags, ep_steps=a.steps, stream=s)
+        _fused_step(m, a, fl, a.nbuf, s, u0=u0)
+        if log is not None:
+            m.episode_status_log_dev(a.rows, a.status, a.flags, a.steps, log, stream=s)
+        if u0 is not None:           # the step itself: the next refill overwrites a slot that has just finished
+            m.episode_trace_dev(a.rows, _lib.TRACE_STEP, a.slot_seed, a.x0, a.obst, a.X, u0, a.status, a.iters, a.flags, a.steps, stream=s)
+        k += 1
+    return k, schedule
+
+
+def _sweep_collect(a, goal, bound, tabs, seed_src, tarr, tr):
+    """the sweep's results on the host, once its stream has drained: table and x_last from the parked rows, the status log, seed_src (None: not recorded),
+    the traced rows cut to each seed's length -- held to the table's lengths.  Returns the result dict without steps_run and schedule."""
+    left = int(a.cursor[1].item())
+    ri = a.res_i.cpu().numpy(); rfh = a.res_f.cpu().numpy()
+    if left != 0 or (ri[:, 0] < 0).any():
+        raise _lib.MpcError(f"the sweep did not drain within {bound} control steps ({left} slots live, {int((ri[:, 0] < 0).sum())} rows not parked)")
+    xl = np.ascontiguousarray(rfh[:, 1:6])
+    table = result_table(ri[:, 0], rfh[:, 0], xl, np.ascontiguousarray(np.broadcast_to(goal, (a.count, 2)), dtype=np.float64), ri[:, 1])
+    out = dict(table=table, x_last=xl, solves=int(table[:, 4].sum() + table[:, 1].sum()))
+    if "res_log" in tabs:
+        rl = tabs["res_log"].cpu().numpy()
+        out.update(status2=rl[:, 0].copy(), status4=rl[:, 1].copy(), first_bad=rl[:, 2].copy())
+    if seed_src is not None:
+        out["seed_src"] = seed_src.cpu().numpy()
+    if tarr is not None:
+        th = {n: t.cpu().numpy() for n, t in tarr.items() if t is not None and n not in ("seed_row", "slot_state")}
+        if (th["len"] < 0).any():
+            raise _lib.MpcError(f"trace: seed indices {tr['seeds'][th['len'] < 0].tolist()} started without a START launch (mpc_episode_trace_dev)")
+        want = (table[tr["seeds"], 4] + table[tr["seeds"], 1]).astype(np.int64)
+        if not np.array_equal(th["len"], want):
+            bad = np.nonzero(th["len"] != want)[0]
+            raise _lib.MpcError(f"trace: seed index {int(tr['seeds'][bad[0]])} recorded {int(th['len'][bad[0]])} control steps, its table row says {int(want[bad[0]])}")
+        cut = dict(simX=("x", 1), obst_traj=("obst", 1), u=("u", 0), status=("status", 0), iters=("iters", 0), pred=("pred", 0))      # (array, rows beyond L)
+        out["trace"] = {ks: {n: th[src][r, :int(th["len"][r]) + more].copy() for n, (src, more) in cut.items() if src in th} for r, ks in enumerate(tr["seeds"].tolist())}
+    return out
+
+
 def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True, init_guess_when_error=True,
                    bug_compat_alias=True, interpolate_init=False, sqp=None, device=0, solver=None, poll_every=25, r_safe=None, r_hit=None, W=None, We=None,
                    active=None, margin_all=False, bounds=None, status_log=False, ring=None, ring_every=None, trace=None, trace_pred=True,
@@ -423,6 +644,9 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
     iterate behind each step as run_episodes records it.  sweep_record(result, k) puts one seed into run_episodes(record=True)'s layout for visualisation_inputs.
     The arrays take trace_bytes(rows, max_iter, N, n_obst, trace_pred) device bytes (90 kB per seed without pred and 426 kB with, at max_iter 400, N 20 and
     5 obstacles); above trace_max_bytes the call is refused on the host.  The rows are those of the sweep without a trace, bit for bit.
+    solver: a caller's handle (max_batch >= the slots) to run on.  It leaves as it came whether the call returns or raises (_HandleLease): SQP setting, per-seed
+    tables, ring and trace of this call are switched OFF again, and the handle keeps no pointer into this call's tensors -- a setting of the same feature the
+    caller had made before is not re-created.
     Not offered: `record` as an argument (trace= is the sweep's form of it: rows of unequal length per seed, not a batch), a per-seed stage reference, host
     noise, PipelinedMpc."""
     not_offered = sorted(set(cfg) & {"record", "noise", "seed", "first_seed", "compact_from"})
@@ -434,170 +658,28 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
                          margin_all=margin_all, bounds=bounds, status_log=status_log, ring=ring, ring_every=ring_every, poll_every=poll_every)
     tr = _sweep_trace(count, max_iter, solver.N if solver is not None else int(N), solver.n_obst if solver is not None else int(n_obst), trace=trace,
                       trace_pred=trace_pred, trace_max_bytes=trace_max_bytes)
+    _warn_interpolate_alias(interpolate_init, bug_compat_alias)
     import torch
     S = min(int(slots), count); max_iter = int(max_iter); poll_every = int(poll_every)
-    if interpolate_init and bug_compat_alias:
-        import warnings
-        warnings.warn("interpolate_init with bug_compat_alias=True: the straight-line guess is built from a plant state whose v, omega the aliasing defect has "
-                      "zeroed; the two recorded `interpolate_init` tables replay with bug_compat_alias=False (tests/test_gpu_replay.py)", stacklevel=2)
+    bound = -(-count // S) * max_iter + poll_every
+    fl = step_flags(init_guess_when_error, bug_compat_alias, interpolate_init, ft["margin_all"] and ft["mask"] is not None)
+    rf = refill_flags(bug_compat_alias, interpolate_init, random_move)
     dev = torch.device("cuda", device)
-    m = solver or BatchedMpc(N, n_obst, Tf, max_batch=S, device=device, **cfg)
-    N, n_obst = m.N, m.n_obst
-    if sqp is not None:
-        m.set_sqp(*sqp)
-    stream = torch.cuda.Stream(device=dev)
-    own_params = any(ft[n] is not None for n in ("W", "We", "r_safe", "r_hit"))
-    own_mask, own_bounds, own_tables, own_trace = ft["mask"] is not None, ft["bounds"] is not None, False, False
-    with torch.cuda.stream(stream):
-        f64 = dict(dtype=torch.float64, device=dev); i32 = dict(dtype=torch.int32, device=dev)
-        dstart, dgoal_rows = torch.from_numpy(start).to(dev), torch.from_numpy(goal).to(dev)
-        dx0 = torch.zeros(S, 5, **f64); dgoal = torch.zeros(S, 2, **f64); dobst = torch.zeros(S, n_obst, 4, **f64)
-        X = torch.zeros(S, N + 1, 5, **f64); U = torch.zeros(S, N, 2, **f64)
-        status = torch.zeros(S, **i32); iters = torch.zeros(S, **i32)
-        margin = torch.full((S,), float("inf"), **f64)
-        flags = torch.ones(S, **i32); steps = torch.zeros(S, **i32)          # every slot "finished" and without a seed: the first refill fills them all
-        slot_seed = torch.full((S,), -1, **i32); cursor = torch.zeros(2, **i32)
-        gen_state = torch.zeros(S, _lib.lib().mpc_noise_state_words(), **i32)
-        nbuf = torch.zeros(S, n_obst, 2, **f64) if random_move else None
-        res_f = torch.full((count, 6), float("nan"), **f64); res_i = torch.full((count, 2), -1, **i32)
-        s = stream.cuda_stream
-        fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS
-        if init_guess_when_error:
-            fl |= _lib.STEP_RESET_ON_FAIL | (_lib.STEP_ALIAS_BUG if bug_compat_alias else 0) | (_lib.STEP_INTERP_GUESS if interpolate_init else 0)
-        if own_mask and ft["margin_all"]:
-            fl |= _lib.STEP_MARGIN_ALL
-        rf = (_lib.REFILL_ALIAS_BUG if bug_compat_alias else 0) | (_lib.REFILL_INTERP_GUESS if interpolate_init else 0) | (_lib.REFILL_DRAW_NOISE if random_move else 0)
-        # per-seed tables: the sources (count rows) and the per-slot arrays the solve reads in place (max_batch rows, preset with the handle's own values: a
-        # slot that never gets a seed holds valid numbers), registered with the _dev setters; the refill copies row k into the slot that starts k
-        MB = m.max_batch
-        tabs = {}
-        if own_params:
-            r_hit_own = 1.0 + 0.2                               # o.r + R_ROBOT: the fused step's hit radius (mpc_closed_loop_step_dev)
-            preset = dict(W=list(m.cfg.W), We=list(m.cfg.We), r_safe=[m.cfg.r_safe] * n_obst, r_hit=[r_hit_own] * n_obst)
-            slot = {}
-            for name in ("W", "We", "r_safe", "r_hit"):
-                if ft[name] is not None:
-                    tabs[name] = torch.from_numpy(ft[name]).to(dev)
-                    slot[name] = tabs["slot_" + name] = torch.tensor(preset[name], **f64).repeat(MB, 1).contiguous()
-            m.set_instance_params(W=slot.get("W"), We=slot.get("We"), r_safe=slot.get("r_safe"), r_hit=slot.get("r_hit"))
-        if own_mask:
-            tabs["mask"] = torch.from_numpy(ft["mask"].copy()).to(dev)
-            tabs["slot_mask"] = torch.full((MB,), int(np.array([(1 << n_obst) - 1], dtype=np.uint32).view(np.int32)[0]), **i32)
-            m.set_obstacle_mask(tabs["slot_mask"])
-        if own_bounds:
-            tabs["bounds"] = torch.from_numpy(ft["bounds"]).to(dev)
-            tabs["slot_bounds"] = torch.from_numpy(pack_instance_bounds(m.cfg, MB)).to(dev)
-            m.set_instance_bounds_dev(tabs["slot_bounds"])
-        if ft["status_log"]:
-            tabs["log"] = torch.tensor([0, 0, -1, 0], **i32).repeat(S, 1).contiguous()
-            tabs["res_log"] = torch.full((count, 3), -1, **i32)
-        if tabs:
-            m.set_refill_tables_dev(**tabs); own_tables = True
-        ring_cap, ring_every = ft["ring"], ft["ring_every"]
-        seed_src = None
-        if ring_cap is not None:
-            ring_state = torch.zeros(ring_cap, gen_state.shape[1], **i32); ring_obst = torch.zeros(ring_cap, n_obst, 4, **f64)
-            ring_tag = torch.full((ring_cap,), -1, **i32); seed_src = torch.full((count,), -1, **i32)
-            m.episode_ring_dev(ring_cap, ring_state, ring_obst, ring_tag, seed_src)
-        tarr, u0 = None, None
-        if tr is not None:          # the per-seed rows (mpc_episode_trace): row r belongs to seed index tr["seeds"][r]
-            R = tr["seeds"].size
-            tarr = dict(seed_row=torch.from_numpy(tr["seed_row"]).to(dev), slot_state=torch.tensor([-1, 0], **i32).repeat(S, 1).contiguous(),
-                        len=torch.zeros(R, **i32), x=torch.zeros(R, max_iter + 1, 5, **f64), obst=torch.zeros(R, max_iter + 1, n_obst, 4, **f64),
-                        u=torch.zeros(R, max_iter, 2, **f64), status=torch.zeros(R, max_iter, **i32), iters=torch.zeros(R, max_iter, **i32),
-                        pred=torch.zeros(R, max_iter, N + 1, 5, **f64) if tr["pred"] else None)
-            u0 = torch.zeros(S, 2, **f64)
-            m.episode_trace_set_dev(R, max_iter, **tarr); own_trace = True
-        bound = -(-count // S) * max_iter + poll_every
-        schedule = np.full((count, 2), -1, dtype=np.int64) if poll_every == 1 else None
-        seen = np.full(S, -1, dtype=np.int64)
-        live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
-        live_event = None
-        k = 0
-        try:
-            while True:
-                if ring_cap is not None and k % ring_every == 0:
-                    m.episode_ring_fill_dev(scenario, first, count, cursor, stream=s)
-                m.episode_refill_dev(S, scenario, first, count, max_iter, dstart, dgoal_rows, per_seed, dx0, dobst, dgoal, X, U, margin, flags, steps,
-                                     gen_state, nbuf, slot_seed, cursor, res_f, res_i, flags=rf, stream=s)
-                if poll_every == 1:
-                    now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
-                    new = (now != seen) & (now >= 0)
-                    schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
-                    seen = now
-                    if int(cursor[1].item()) == 0:
-                        break
-                elif k % poll_every == 0:
-                    # the count of the poll before this one, which the device passed long ago: the host stays at most two polls ahead of the device (no idle
-                    # steps by the hundred behind the end of the sweep) and the device always has a poll's worth of steps queued (it never waits for the host)
-                    if live_event is not None:
-                        live_event.synchronize()
-                        if int(live_host[0]) == 0:
-                            break
-                    live_host.copy_(cursor[1:2], non_blocking=True)
-                    live_event = torch.cuda.Event(); live_event.record(stream)
-                if k >= bound:
-                    break
-                if own_trace:                # the state every seed that has just started starts from: behind the refill, in front of the step
-                    m.episode_trace_dev(S, _lib.TRACE_START, slot_seed, dx0, dobst, ep_flags=flags, ep_steps=steps, stream=s)
-                m.closed_loop_step_dev(S, dx0, dobst, dgoal, X, U, u0, None, status, iters, nbuf, flags=fl,
-                                       min_margin=margin, ep_flags=flags, ep_steps=steps, stream=s)
-                if ft["status_log"]:
-                    m.episode_status_log_dev(S, status, flags, steps, tabs["log"], stream=s)
-                if own_trace:                # the step itself: the next refill overwrites a slot that has just finished
-                    m.episode_trace_dev(S, _lib.TRACE_STEP, slot_seed, dx0, dobst, X, u0, status, iters, flags, steps, stream=s)
-                k += 1
+    with _HandleLease(solver, lambda: BatchedMpc(N, n_obst, Tf, max_batch=S, device=device, **cfg)) as lease:
+        m = lease.m
+        if sqp is not None:
+            lease.attach("set_sqp", *sqp)
+        lease.stream = stream = torch.cuda.Stream(device=dev)
+        with torch.cuda.stream(stream):
+            a = _sweep_slots(torch, dev, m, S, count, start, goal, random_move)
+            tabs = _attach_tables(lease, torch, a, ft)
+            ring = _attach_ring(lease, torch, a, ft["ring"]) if ft["ring"] is not None else None
+            tarr, u0 = _attach_trace(lease, torch, a, tr, max_iter) if tr is not None else (None, None)
+            k, schedule = _sweep_loop(torch, m, a, stream, scenario, first, per_seed, max_iter, poll_every, bound, fl, rf,
+                                      ring_every=ft["ring_every"] if ring is not None else None, log=tabs.get("log"), u0=u0)
             stream.synchronize()
-            left = int(cursor[1].item())
-            ri = res_i.cpu().numpy(); rfh = res_f.cpu().numpy()
-            extra = {}
-            if ft["status_log"]:
-                rl = tabs["res_log"].cpu().numpy()
-                extra.update(status2=rl[:, 0].copy(), status4=rl[:, 1].copy(), first_bad=rl[:, 2].copy())
-            if ring_cap is not None and poll_every == 1:
-                extra["seed_src"] = seed_src.cpu().numpy()
-            th = {n: a.cpu().numpy() for n, a in tarr.items() if a is not None and n not in ("seed_row", "slot_state")} if own_trace else None
-        finally:
-            stream.synchronize()
-            if solver is not None:           # (a caller's solver leaves as it came; the handle holds pointers into this call's tensors)
-                if own_trace:
-                    m.episode_trace_set_dev(0)
-                if own_tables:
-                    m.set_refill_tables_dev()
-                if ring_cap is not None:
-                    m.episode_ring_dev(0)
-                if own_params:
-                    m.set_instance_params()
-                if own_mask:
-                    m.set_obstacle_mask(None)
-                if own_bounds:
-                    m.set_instance_bounds_dev(None)
-                if sqp is not None:
-                    m.set_sqp()
-    if solver is None:
-        m.close()
-    if left != 0 or (ri[:, 0] < 0).any():
-        raise _lib.MpcError(f"the sweep did not drain within {bound} control steps ({left} slots live, {int((ri[:, 0] < 0).sum())} rows not parked)")
-    fl_h, st_h, xl = ri[:, 0], ri[:, 1], np.ascontiguousarray(rfh[:, 1:6])
-    goal_all = np.ascontiguousarray(np.broadcast_to(goal, (count, 2)), dtype=np.float64)
-    table = np.column_stack([(fl_h & 4) != 0, (fl_h & 1) != 0, rfh[:, 0],
-                             np.linalg.norm(xl[:, :2] - goal_all, axis=1), st_h, (fl_h & 2) != 0]).astype(np.float64)
-    if th is not None:
-        if (th["len"] < 0).any():
-            raise _lib.MpcError(f"trace: seed indices {tr['seeds'][th['len'] < 0].tolist()} started without a START launch (mpc_episode_trace_dev)")
-        want = (table[tr["seeds"], 4] + table[tr["seeds"], 1]).astype(np.int64)
-        if not np.array_equal(th["len"], want):
-            bad = np.nonzero(th["len"] != want)[0]
-            raise _lib.MpcError(f"trace: seed index {int(tr['seeds'][bad[0]])} recorded {int(th['len'][bad[0]])} control steps, its table row says {int(want[bad[0]])}")
-        out = {}
-        for r, ks in enumerate(tr["seeds"].tolist()):
-            L = int(th["len"][r])
-            out[ks] = dict(simX=th["x"][r, :L + 1].copy(), obst_traj=th["obst"][r, :L + 1].copy(), u=th["u"][r, :L].copy(), status=th["status"][r, :L].copy(),
-                           iters=th["iters"][r, :L].copy())
-            if tr["pred"]:
-                out[ks]["pred"] = th["pred"][r, :L].copy()
-        extra["trace"] = out
-    return dict(table=table, x_last=xl, steps_run=k, solves=int(st_h.sum()) + int((fl_h & 1).sum()), schedule=schedule, **extra)
+            out = _sweep_collect(a, goal, bound, tabs, ring["seed_src"] if ring is not None and poll_every == 1 else None, tarr, tr)
+    return dict(out, steps_run=k, schedule=schedule)
 
 
 def sweep_record(result, k):

@@ -41,6 +41,30 @@ def pack_obstacle_mask(active):
     return np.ascontiguousarray(w.astype(np.uint32))
 
 
+def mask_rows(active, n_obst, rows="B", why=""):
+    """a per-instance obstacle mask as an array (rows, n_obst), shape checked; `rows` is the caller's word for the row count and `why` ends its message"""
+    a = np.asarray(active)
+    if a.ndim != 2 or a.shape[1] != n_obst:
+        raise ValueError(f"active must be ({rows}, {n_obst}), got {a.shape}" + why)
+    return a
+
+
+# the per-instance arrays of mpc_set_instance_params in the order of the C prototype: (name, columns -- None: n_obst, and (rows,) means one radius per instance)
+INSTANCE_ROW = (("W", 6), ("We", 4), ("r_safe", None), ("r_hit", None))
+
+
+def instance_rows(name, a, cols, n_obst, rows="B"):
+    """one per-instance array of set_instance_params as contiguous float64 (rows, cols); a radius array (cols None) has n_obst columns and may be (rows,),
+    one radius per instance.  `rows` is the caller's word for the row count; values are not looked at."""
+    radius, cols = cols is None, n_obst if cols is None else cols
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 1 and radius:
+        a = np.repeat(a[:, None], n_obst, axis=1)
+    if a.ndim != 2 or a.shape[1] != cols:
+        raise ValueError(f"{name} must be ({rows}, {cols})" + (f" or ({rows},)" if radius else "") + f", got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
 def unpack_obstacle_mask(words, n_obst):
     """np.uint32 (B,) -> bool (B, n_obst): the inverse of pack_obstacle_mask"""
     w = np.asarray(words, dtype=np.uint32).astype(np.uint64)
@@ -52,29 +76,29 @@ BOUNDS_ROW = (("bu_lo", 0, 2), ("bu_hi", 2, 2), ("bx_lo", 4, 4), ("bx_hi", 8, 4)
 BOUNDS_COLS = 12
 
 
-def _bounds_group(name, a, cols, B=None):
-    """one group of instance bounds as a float64 (B, cols) array; a single row (cols,) is broadcast to B rows (B None: stays one row)"""
+def _bounds_group(name, a, cols, B=None, rows="B"):
+    """one group of instance bounds as a float64 (B, cols) array; a single row (cols,) is broadcast to B rows (B None: stays one row).  `rows` is the
+    caller's word for the row count."""
     a = np.asarray(a, dtype=np.float64)
-    if a.ndim == 1:
-        if a.shape != (cols,):
-            raise ValueError(f"{name} must be (B, {cols}) or ({cols},), got {a.shape}")
+    if a.ndim == 1 and a.shape == (cols,):
         a = np.tile(a[None, :], (1 if B is None else B, 1))
     if a.ndim != 2 or a.shape[1] != cols:
-        raise ValueError(f"{name} must be (B, {cols}) or ({cols},), got {a.shape}")
+        raise ValueError(f"{name} must be ({rows}, {cols}) or ({cols},), got {a.shape}")
     if B is not None and a.shape[0] != B:
         raise ValueError(f"{name} has {a.shape[0]} rows, expected {B}")
     return np.ascontiguousarray(a)
 
 
-def pack_instance_bounds(cfg, B, bx_lo=None, bx_hi=None, bu_lo=None, bu_hi=None):
+def pack_instance_bounds(cfg, B, bx_lo=None, bx_hi=None, bu_lo=None, bu_hi=None, rows="B"):
     """The packed table of mpc_set_instance_bounds_dev on the host: float64 (B, 12), a row being bu_lo[2], bu_hi[2], bx_lo[4], bx_hi[4] (bx in the
-    order of mpc_config: x, y, v, omega).  Each group is (B, cols) or one row (cols,) for every instance; None takes cfg's value (an MpcConfig)."""
+    order of mpc_config: x, y, v, omega).  Each group is (B, cols) or one row (cols,) for every instance; None takes cfg's value (an MpcConfig).
+    `rows` is the caller's word for B in a shape message."""
     B = int(B)
     given = dict(bx_lo=bx_lo, bx_hi=bx_hi, bu_lo=bu_lo, bu_hi=bu_hi)
     tab = np.empty((B, BOUNDS_COLS))
     for name, at, cols in BOUNDS_ROW:
         a = given[name]
-        tab[:, at:at + cols] = _bounds_group(name, list(getattr(cfg, name)) if a is None else a, cols, B)
+        tab[:, at:at + cols] = _bounds_group(name, list(getattr(cfg, name)) if a is None else a, cols, B, rows)
     return tab
 
 
@@ -240,14 +264,9 @@ class BatchedMpc:
         """host arrays of set_instance_params in the C layout: (B, 6), (B, 4), (B, n_obst), (B, n_obst); r_safe / r_hit of shape (B,) mean one radius
         per instance (every obstacle of it); all of one batch size.  None stays None."""
         out, B = [], None
-        for name, a, cols in (("W", W, 6), ("We", We, 4), ("r_safe", r_safe, self.n_obst), ("r_hit", r_hit, self.n_obst)):
+        for (name, cols), a in zip(INSTANCE_ROW, (W, We, r_safe, r_hit)):
             if a is not None:
-                a = np.asarray(a, dtype=np.float64)
-                if a.ndim == 1 and name in ("r_safe", "r_hit"):
-                    a = np.repeat(a[:, None], self.n_obst, axis=1)
-                a = _f64(a)
-                if a.ndim != 2 or a.shape[1] != cols:
-                    raise ValueError(f"{name} must be (B, {cols})" + (" or (B,)" if name in ("r_safe", "r_hit") else "") + f", got {a.shape}")
+                a = instance_rows(name, a, cols, self.n_obst)
                 if B is not None and a.shape[0] != B:
                     raise ValueError(f"{name} has {a.shape[0]} rows, the arrays before it {B}")
                 B = a.shape[0]
@@ -284,9 +303,7 @@ class BatchedMpc:
         if active is None:
             _lib.check(_lib.lib().mpc_set_obstacle_mask(self._h, 0, None))
         elif isinstance(active, (np.ndarray, list, tuple)):
-            a = np.asarray(active)
-            if a.ndim != 2 or a.shape[1] != self.n_obst:
-                raise ValueError(f"active must be (B, {self.n_obst}), got {a.shape}")
+            a = mask_rows(active, self.n_obst)
             if a.shape[0] < 1 or a.shape[0] > self.max_batch:
                 raise ValueError(f"active has {a.shape[0]} rows, the handle holds 1 .. {self.max_batch} instances")
             words = pack_obstacle_mask(a)

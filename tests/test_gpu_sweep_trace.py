@@ -171,6 +171,94 @@ def test_a_callers_solver_leaves_as_it_came(mapping):
         assert_same_trace(traced["trace"][k], full["trace"][k])
 
 
+def refuse(*a, **kw):
+    """stands in for a binding whose library call is refused: a Python exception, nothing is launched"""
+    from mpc_gpu import _lib
+    raise _lib.MpcError("injected refusal")
+
+
+def assert_detached(m, name0, batch):
+    """the handle runs the kernel it came with, and holds no trace"""
+    import torch
+    from mpc_gpu import _lib
+    assert m.kernel_name(batch) == name0
+    dev = torch.device("cuda", 0)
+    z = torch.zeros(4, 5 * 4, dtype=torch.float64, device=dev); w = torch.zeros(4, dtype=torch.int32, device=dev)
+    with pytest.raises(_lib.MpcError, match="no trace attached"):
+        m.episode_trace_dev(3, _lib.TRACE_START, w, z, z, ep_flags=w, ep_steps=w)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("fails_at", ["episode_trace_set_dev", "set_refill_tables_dev"])
+def test_a_failed_attach_leaves_a_callers_solver_as_it_came(mapping, fails_at):
+    """every feature of a sweep on a caller's handle, and the attach named fails (in Python, before any launch): the handle is at level 0 again, nothing is
+    attached, and the next plain sweep on it gives the batch harness's rows"""
+    from mpc_gpu import _lib
+    ref = sc.batch_reference(mapping, "RANDOM", *SEEDS)
+    f = fc.arrays(10)
+    during = []
+    with mapping.BatchedMpc(max_batch=4, **sc.PROBLEM) as m:
+        name0 = m.kernel_name(3)
+        setattr(m, fails_at, lambda *a, **kw: (during.append(m.kernel_name(3)), refuse())[1])
+        with pytest.raises(_lib.MpcError, match="injected refusal"):
+            mapping.run_seed_sweep(sc.START, sc.GOAL, "RANDOM", SEEDS, SLOTS, solver=m, r_safe=f["r_safe"], active=f["active"], bounds=f["bounds"],
+                                   status_log=True, ring=2, trace=[2, 7])
+        delattr(m, fails_at)                        # (the handle's own binding again)
+        assert len(during) == 1 and during[0] != name0, "the case itself: the features were on when the attach failed"
+        assert_detached(m, name0, 3)
+        again = mapping.run_seed_sweep(sc.START, sc.GOAL, "RANDOM", SEEDS, SLOTS, solver=m)
+    assert np.array_equal(again["table"], ref["table"]) and np.array_equal(again["x_last"], ref["x_last"])
+
+
+def test_a_failed_step_leaves_run_episodes_callers_solver_as_it_came(mapping):
+    """run_episodes with radii and bounds on a caller's handle, and the second fused step fails (in Python): level 0 again, and the next plain call on the
+    handle gives the reference table"""
+    from mpc_gpu import _lib
+    ref = sc.batch_reference(mapping, "RANDOM", *SEEDS)
+    f = fc.arrays(10)
+    x0, goal = np.tile(sc.START, (10, 1)), np.tile(sc.GOAL, (10, 1))
+    kw = dict(first_seed=SEEDS[0], compact_from=None, N=sc.PROBLEM["N"], Tf=sc.PROBLEM["Tf"], n_obst=sc.PROBLEM["n_obst"])
+    during = []
+    with mapping.BatchedMpc(max_batch=10, **sc.PROBLEM) as m:
+        name0 = m.kernel_name(10)
+        step = m.closed_loop_step_dev
+        m.closed_loop_step_dev = lambda *a, **k: refuse() if during else (during.append(m.kernel_name(10)), step(*a, **k))[1]
+        with pytest.raises(_lib.MpcError, match="injected refusal"):
+            mapping.run_episodes(x0, goal, "RANDOM", solver=m, r_safe=f["r_safe"], bounds=f["bounds"], **kw)
+        del m.closed_loop_step_dev
+        assert len(during) == 1 and during[0] != name0, "the case itself: the features were on when the step failed"
+        assert_detached(m, name0, 10)
+        again = mapping.run_episodes(x0, goal, "RANDOM", solver=m, **kw)
+    assert np.array_equal(again["table"], ref["table"]) and np.array_equal(again["x_last"], ref["x_last"])
+
+
+@pytest.mark.parametrize("driver", ["run_seed_sweep", "run_episodes"])
+def test_own_handles_are_closed_on_failure(mapping, monkeypatch, driver):
+    """the same failures without solver=: the handle the driver made is closed, once, before the exception leaves the call"""
+    from mpc_gpu import _lib
+    f = fc.arrays(10)
+    if driver == "run_episodes":
+        with mapping.BatchedMpc(max_batch=10, **sc.PROBLEM) as g:            # (explicit obstacle states: the driver then makes ONE handle, its own)
+            obst = g.generate_scenarios("RANDOM", 10, seed0=SEEDS[0])
+    closed, stepped = [], []
+    close, step = mapping.BatchedMpc.close, mapping.BatchedMpc.closed_loop_step_dev
+
+    def counting_close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            closed.append(id(self))
+        close(self)
+    monkeypatch.setattr(mapping.BatchedMpc, "close", counting_close)
+    with pytest.raises(_lib.MpcError, match="injected refusal") as e:
+        if driver == "run_seed_sweep":
+            monkeypatch.setattr(mapping.BatchedMpc, "episode_trace_set_dev", refuse)
+            sweep(mapping, "RANDOM", SEEDS, SLOTS, r_safe=f["r_safe"], status_log=True, ring=2, trace=[2, 7])
+        else:
+            monkeypatch.setattr(mapping.BatchedMpc, "closed_loop_step_dev", lambda self, *a, **k: refuse() if stepped else (stepped.append(1), step(self, *a, **k))[1])
+            mapping.run_episodes(np.tile(sc.START, (10, 1)), np.tile(sc.GOAL, (10, 1)), obst, r_safe=f["r_safe"], bounds=f["bounds"], random_move=False, **sc.PROBLEM)
+    assert len(closed) == 1          # (`e` still holds the call's frames, and with them the handle: it was closed by the driver, not by the collector)
+    del e
+
+
 def test_argument_refusals_and_a_skipped_start_through_the_c_abi(mapping):
     """MPC_ERR_ARG naming the field with nothing launched; then the protocol itself on two slots: a seed whose START launch was skipped shows len = -1 and not
     a wrong row 0, and the other rows are untouched"""
