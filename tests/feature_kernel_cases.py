@@ -1,7 +1,8 @@
 """Test infrastructure of the feature-level kernel sweep (test_feature_kernel_cases_host.py, test_gpu_every_feature_kernel.py): the 78 solve
 instantiations of csrc/solve_dispatch.hpp at feature levels 1 to 4 (REF, IPAR, OSEL, IBND), a handle that reaches each, and per case one batch of
 twelve instances in four groups of three whose feature values differ group by group, so that the oracle -- which knows one config -- can be asked
-about each group.  Imports without torch or a GPU; the oracle is passed in.
+about each group; `embed` puts those twelve into a batch that the instance scheduler deals (test_gpu_feature_scheduling.py).  Imports without torch or a
+GPU; the oracle is passed in.
 
 The matrix: levels 1 and 2 have, each, one lane per stage <3|5|10, 64, 3, false|true> (6), the stage split
 <3|5|10, 2|3> x {plain, two wavefronts per SIMD, run-time row count} (18) and the multi-wavefront kernel <20|32, 2, false|true> (4); levels 3 and 4
@@ -153,6 +154,78 @@ def inputs(orc, case):
                 r_safe=np.stack([np.where(g[k]["mask"], g[k]["r_safe"], g[k]["r_safe"] + DECOY_RADIUS) for k in group]),
                 mask=np.stack([g[k]["mask"] for k in group]),
                 bounds=per_instance([e["bounds"] for e in g], group), P=oracle_P(orc, base, obst))
+
+
+# ---------------------------------------------------------------------------------------------------------------- a scheduled batch around a case
+EMBEDDED = ("x0", "goal", "obst", "noise", "ep_flags", "yref", "offset", "W", "We", "r_safe", "mask")      # per-instance arrays (and bounds, alpha, P, X0, U0)
+FEATURE_ARRAYS = ("yref", "W", "We", "r_safe", "bounds", "alpha")      # every row its own: a neighbour's row is another problem
+
+
+def positions(Bs):
+    """where the twelve judged instances sit in a batch of Bs: case instance 0 at index 0, case instance 11 at Bs - 1, the others spread evenly"""
+    pos = np.round(np.linspace(0, Bs - 1, B)).astype(np.int64)
+    assert pos[0] == 0 and pos[-1] == Bs - 1 and len(set(pos.tolist())) == B
+    return pos
+
+
+def embed(orc, case_inputs, Bs, pos, alpha=None, with_P=False):
+    """The case's twelve instances inside a batch of Bs that the instance scheduler deals: rows pos[0 .. 11] of every
+    per-instance array are the case's own rows, bit for bit; the other Bs - 12 rows are fillers, random_batch(Bs, n_obst, seed) at rest, each with
+    feature values of its own from the ranges of `inputs`' groups -- weights IP times U(0.5, 3), radii in U(1.6, 3.0) (a decoy added where the
+    obstacle is absent), from level 3 on a mask that keeps one obstacle or more, a bound set of its own from draw_bounds' menu, an offset in 0 .. 3
+    with the decoy in front of it, a row of slack_schedule_cases.schedule where `alpha` (the case's (12, N + 1) schedule) is given.  About one filler
+    in a hundred starts idle.  with_P: the look-ahead of every row (the case's own at pos).  A slot index in place of the instance index
+    therefore reads a valid row of a valid array that is another problem.  Returns the case's dict with the arrays replaced, `pos`, `case`
+    (the inputs it came from) and `filler` (bool (Bs,))."""
+    inp = case_inputs
+    N, no, level, T = inp["N"], inp["no"], inp["level"], inp["T"]
+    pos = np.asarray(pos, dtype=np.int64)
+    assert pos.shape == (B,) and len(set(pos.tolist())) == B and pos.min() >= 0 and pos.max() < Bs
+    rng = np.random.default_rng([N, no, level, Bs, 7])
+    x0, goal, obst = random_batch(Bs, no, seed=[N, no, Bs, 6])
+    x0[:, 3:] = 0.0
+    filler = np.ones(Bs, bool); filler[pos] = False
+    out = dict(x0=x0, goal=goal, obst=obst, noise=rng.standard_normal((Bs, no, 2)), ep_flags=np.zeros(Bs, np.int32))
+    out["ep_flags"][rng.choice(np.nonzero(filler)[0], max(3, Bs // 100), replace=False)] = 1
+    out["offset"] = rng.integers(0, 4, Bs).astype(np.int32)
+    yref = np.zeros((Bs, T, 6))
+    yref[:, :, :2] = goal[:, None, :]
+    for b in range(Bs):
+        yref[b, :out["offset"][b], :2] += (5.0, -5.0)
+    out["yref"] = yref
+    out["W"] = np.array(IP["W"]) * rng.uniform(0.5, 3.0, (Bs, 6))
+    out["We"] = np.array(IP["We"]) * rng.uniform(0.5, 3.0, (Bs, 4))
+    mask = np.ones((Bs, no), bool)
+    if level >= 3:
+        mask = rng.uniform(size=(Bs, no)) < 0.6
+        mask[np.arange(Bs), rng.integers(0, no, Bs)] = True
+    out["mask"] = mask
+    r = rng.uniform(1.6, 3.0, (Bs, no))
+    out["r_safe"] = np.where(mask, r, r + DECOY_RADIUS)
+    menu, _ = draw_bounds(rng, Bs, Bs + 1)                # entry 0 is the handle's defaults, which the judged rows of group 0 hold
+    bounds = per_instance(menu, np.arange(1, Bs + 1))
+    if alpha is not None:
+        from slack_schedule_cases import BUILTIN_ROW, schedule
+        # the rows behind the schedule's special ones (the all-zero row, the terminal row, the built-in row: the case's own schedule has them)
+        out["alpha"] = schedule(N, Bs + BUILTIN_ROW + 1, 1000 * level + 9, builtin=np.ones(N + 1))[BUILTIN_ROW + 1:]
+        out["alpha"][pos] = alpha
+    for k in EMBEDDED:
+        out[k][pos] = inp[k]
+    for k in bounds:
+        bounds[k][pos] = inp["bounds"][k]
+    out["bounds"] = bounds
+    if with_P:
+        out["P"] = oracle_P(orc, orc.config(N, no, 0.1 * N), obst)
+        out["P"][pos] = inp["P"]
+    return dict(inp, **out, pos=pos, filler=filler, case=inp, Bs=Bs)
+
+
+def distinct_rows(emb, name):
+    """(rows of array `name`, as a 2-D array) of an embedded batch: what test_feature_kernel_cases_host.py asks to be pairwise different"""
+    a = emb[name]
+    if name == "bounds":
+        a = np.concatenate([a[k] for k in ("bx_lo", "bx_hi", "bu_lo", "bu_hi")], axis=1)
+    return np.ascontiguousarray(a.reshape(a.shape[0], -1))
 
 
 def group_problem(orc, inp, k):

@@ -35,10 +35,41 @@ def on_own_stream(fn, *args):
         torch.cuda.synchronize()
 
 
-def make(mpc_gpu, N, no, B, **cfg):
+def make(mpc_gpu, N, no, B, scheduling=False, **cfg):
+    """scheduling False: the launch order depends on nothing but the batch; True: the handle's default, instance scheduling on"""
     s = mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B, **cfg)
-    s.set_instance_scheduling(False)      # (the launch order then depends on nothing but the batch)
+    if not scheduling:
+        s.set_instance_scheduling(False)
     return s
+
+
+_SCHEDULED = {}
+SCHEDULED_LIMIT = 2048
+
+
+def smallest_scheduled_batch(mpc_gpu, N=20, no=3, configure=None, key=None, limit=SCHEDULED_LIMIT):
+    """the first batch size, in steps of half the device's compute-unit count (+ 13, so that the last wavefront is partly empty), after whose first
+    launch instance_order is not None: the scheduler deals batches beyond one wavefront per SIMD, and how many SIMDs the device has is the library's
+    knowledge, not the test's.  configure(s): the lane mapping of the handles asked (`key` names it); found once per (N, no, key) and session"""
+    import torch
+    from helpers import random_batch
+    if (N, no, key) not in _SCHEDULED:
+        step = max(1, torch.cuda.get_device_properties(0).multi_processor_count // 2)
+        x0, goal, obst = random_batch(limit, no, seed=100 + N + no)
+        found = None
+        for B in range(step + 13, limit + 1, step):
+            with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B) as s:
+                if configure is not None:
+                    configure(s)
+                s.set_instance_scheduling(True)
+                s.reset_guess(x0[:B])
+                s.solve(x0[:B], obst[:B], goal[:B])
+                if s.instance_order(B) is not None:
+                    found = B
+                    break
+        assert found is not None, f"no batch up to {limit} is dealt by the instance scheduler"
+        _SCHEDULED[N, no, key] = found
+    return _SCHEDULED[N, no, key]
 
 
 def run(s, x0, obst, goal, steps=3):
@@ -136,14 +167,15 @@ def _halves(v):
     return v if isinstance(v, tuple) else (v, None)
 
 
-def fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack, solver=None):
+def fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack, solver=None, handle=None):
     """`steps` fused steps, everything resident; the mask words and the packed bounds are device tensors, rewritten by a torch op halfway through
-    where the stack gives a pair.  `solver`: a PipelinedMpc, which takes everything as device tensors through its *_dev setters."""
+    where the stack gives a pair.  `solver`: a PipelinedMpc, which takes everything as device tensors through its *_dev setters.  `handle`: a
+    BatchedMpc of the caller's (its instance scheduling as the caller set it), which stays open; neither: a fresh unscheduled handle."""
     import torch
     L = mpc_gpu._lib
     dev = torch.device("cuda", 0)
     tt = lambda a: torch.tensor(np.ascontiguousarray(a), device=dev)
-    s = solver or make(mpc_gpu, N, no, B)
+    s = solver or handle or make(mpc_gpu, N, no, B)
     piped = solver is not None
     tx, to, tg = tt(x0), tt(obst), tt(goal)
     X = torch.zeros((B, N + 1, 5), dtype=torch.float64, device=dev); U = torch.zeros((B, N, 2), dtype=torch.float64, device=dev)
@@ -203,7 +235,7 @@ def fused_loop(mpc_gpu, N, no, B, steps, x0, goal, obst, stack, solver=None):
         us.append(u0.cpu().numpy().copy())
     res = dict(x=tx.cpu().numpy(), obst=to.cpu().numpy(), X=X.cpu().numpy(), U=U.cpu().numpy(), u0=np.array(us), mm=mm.cpu().numpy(),
                fl=fl.cpu().numpy(), ns=ns.cpu().numpy())
-    if solver is None:
+    if solver is None and handle is None:
         s.close()
     return res
 

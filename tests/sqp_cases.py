@@ -75,6 +75,38 @@ def inputs(orc, c):
     return _INPUTS[c["id"]]
 
 
+NAN_FILLER_AFTER = 3      # the filler with a NaN in x0 is the third filler behind the pick's NaN instance
+
+
+def embedded(orc, c, Bs, pos):
+    """The case's batch inside one of Bs instances that the instance scheduler deals (feature_kernel_cases.embed): the twelve picks at rows pos with
+    the handle's own feature values -- the goal as their reference at offset 0, the config's weights, radii and bounds, every obstacle present --
+    so that oracle_sequence stays their reference; the fillers with feature rows of their own (a level-5 kernel reads every per-instance table), one
+    of them with a NaN in x0.  X0, U0: the cold guess of every row.  Computed once per (case, Bs) and not to be written to"""
+    from feature_kernel_cases import B as FB, embed
+    from instance_bounds_cases import DEFAULTS, per_instance
+    key = ("embedded", c["id"], Bs)
+    if key not in _INPUTS:
+        assert FB == B
+        inp = inputs(orc, c)
+        N, no, cfg = inp["N"], inp["no"], inp["cfg"]
+        T = N + 6
+        yref = np.zeros((B, T, 6)); yref[:, :, :2] = inp["goal"][:, None, :]
+        own = dict(N=N, no=no, level=4, T=T, x0=inp["x0"], goal=inp["goal"], obst=inp["obst"], P=inp["P"], noise=np.zeros((B, no, 2)),
+                   ep_flags=np.zeros(B, np.int32), yref=yref, offset=np.zeros(B, np.int32),
+                   W=np.tile([cfg.W[k] for k in range(6)], (B, 1)), We=np.tile([cfg.We[k] for k in range(4)], (B, 1)),
+                   r_safe=np.full((B, no), float(cfg.r_safe)), mask=np.ones((B, no), bool), bounds=per_instance([DEFAULTS], np.zeros(B, int)))
+        e = embed(orc, own, Bs, pos, with_P=True)
+        e["ep_flags"] = np.zeros(Bs, np.int32)      # (a plain solve: nothing idles)
+        X0, U0 = zip(*[orc.initial_guess(cfg, x) for x in e["x0"]])
+        e["X0"], e["U0"] = np.stack(X0), np.stack(U0)
+        e["X0"][pos], e["U0"][pos] = inp["X0"], inp["U0"]
+        e["nan_filler"] = int(np.nonzero(e["filler"] & (np.arange(Bs) > pos[NAN_INSTANCE]))[0][NAN_FILLER_AFTER - 1])
+        e["x0"][e["nan_filler"], 1] = np.nan         # (behind the guess, as the pick's)
+        _INPUTS[key] = e
+    return _INPUTS[key]
+
+
 def step_norm(Xa, Ua, Xb, Ub):
     """max-norm of the step between two iterates of one instance"""
     return float(max(np.abs(Xb - Xa).max(), np.abs(Ub - Ua).max()))

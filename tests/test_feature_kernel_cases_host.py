@@ -60,6 +60,54 @@ def test_inputs_have_the_shape_the_sweep_relies_on(orc):
             assert (~inp["mask"][:, 0]).any()
 
 
+@pytest.mark.parametrize("Bs", [1037, 1165])
+def test_embedded_batch_keeps_the_case_and_every_filler_row_is_its_own(orc, Bs):
+    """feature_kernel_cases.embed (the scheduled sweeps' batch): the judged rows are the case's bit for bit; in every feature array no filler row
+    equals a judged row or another filler row, so a kernel that reads row `slot` for instance `inst` solves another problem; the arrays pass the
+    host side of the setters.  Exempt from "every row its own" are the arrays of small integers: the offsets (0 .. 3; the yref rows they select
+    differ) and the masks (n_obst bits, three values at two obstacles; the radii rows they go with differ), of which several values must occur"""
+    import mpc_gpu
+    import slack_schedule_cases as ss
+    from mpc_gpu import pack_instance_bounds, pack_obstacle_mask
+    pos = fk.positions(Bs)
+    for c in (fk.cases_of("split", 1)[0], fk.cases_of("one", 2)[1], fk.cases_of("wide", 3)[0], fk.cases_of("split", 4)[0]):
+        inp = fk.inputs(orc, c)
+        alpha = ss.feature_problem(orc, c, "own")["alpha"] if c["level"] == 4 else None
+        e = fk.embed(orc, inp, Bs, pos, alpha=alpha, with_P=c["level"] == 1)
+        N, no = c["N"], c["no"]
+        assert e["filler"].sum() == Bs - fk.B and not e["filler"][pos].any() and pos[0] == 0 and pos[-1] == Bs - 1
+        for k in fk.EMBEDDED + (("P",) if c["level"] == 1 else ()):
+            assert e[k].shape[0] == Bs and e[k].dtype == inp[k].dtype and np.array_equal(e[k][pos], inp[k]), k
+        for k in inp["bounds"]:
+            assert np.array_equal(e["bounds"][k][pos], inp["bounds"][k]), k
+        if alpha is not None:
+            assert np.array_equal(e["alpha"][pos], alpha) and np.isfinite(e["alpha"]).all() and (e["alpha"] >= 0).all() and (e["alpha"] <= 1e300).all()
+        for k in fk.FEATURE_ARRAYS + ("x0", "goal", "obst", "noise"):
+            if k == "alpha" and alpha is None:
+                continue
+            rows = fk.distinct_rows(e, k)
+            assert len(np.unique(rows, axis=0)) == Bs - (fk.B - len(np.unique(rows[pos], axis=0))), k      # (judged rows of one group may be equal)
+            assert not (rows[e["filler"]][:, None, :] == rows[pos][None, :, :]).all(axis=2).any(), k
+        fill = e["filler"]
+        assert set(e["offset"][fill].tolist()) == {0, 1, 2, 3}
+        for b in np.nonzero(fill)[0][:50]:      # the decoy in front of the offset, the goal at and behind it
+            o = e["offset"][b]
+            assert np.array_equal(e["yref"][b, o:, :2], np.tile(e["goal"][b], (e["T"] - o, 1))) and np.array_equal(e["yref"][b, :o, :2], np.tile(e["goal"][b] + (5.0, -5.0), (o, 1)))
+        idle = (e["ep_flags"] != 0) & fill
+        assert 3 <= idle.sum() <= Bs // 50 and set(e["ep_flags"].tolist()) == {0, 1} and (e["x0"][fill, 3:] == 0).all()
+        assert e["mask"].any(axis=1).all() and (e["mask"].all() if c["level"] < 3 else len(np.unique(e["mask"][fill], axis=0)) >= 3)
+        r = np.where(e["mask"], e["r_safe"], e["r_safe"] - fk.DECOY_RADIUS)[fill]
+        assert (r >= 1.6).all() and (r <= 3.0).all()
+        for k, base in (("W", fk.IP["W"]), ("We", fk.IP["We"])):
+            f = e[k][fill] / np.array(base)
+            assert (f >= 0.5).all() and (f <= 3.0).all(), k
+        # the host side of the setters: the packed words and table, every box with an interior
+        words = pack_obstacle_mask(e["mask"])
+        assert words.shape == (Bs,) and (words > 0).all() and (words < (1 << no)).all()
+        t = pack_instance_bounds(mpc_gpu.default_config(N, no, 0.1 * N), Bs, **e["bounds"])
+        assert t.shape == (Bs, 12) and np.isfinite(t).all() and (t[:, 0:2] < t[:, 2:4]).all() and (t[:, 4:8] < t[:, 8:12]).all()
+
+
 def test_oracle_takes_per_obstacle_radii(orc):
     """oracle.obstacle_radii: equal radii are the config's radius bit for bit, one changed radius changes the solve, and nothing stays set behind the block"""
     N, no = 20, 3

@@ -23,17 +23,22 @@ B = fk.B
 RANDOMNESS, VMAX = 0.1, 2.0      # the obstacle motion's noise scale and speed limit, as the fused step is given them
 
 
-def _launches(mpc_gpu, torch, case, inp, nan_absent_too, alpha=None):
+def _launches(mpc_gpu, torch, case, inp, nan_absent_too, alpha=None, scheduling=False, prime=False):
     """one fused step of the case's kernel on banded arrays -- and, nan_absent_too, the same step again on the same handle with NaN in the absent
-    obstacles' entries and everything else restored; per launch, everything it could have touched comes back as numpy.  alpha: an explicit slack
-    schedule (B, N + 1), one more banded device array the handle reads in place (set_slack_schedule's device form)"""
+    obstacles' entries and everything else restored; per launch, everything it could have touched comes back as numpy.  The batch is the rows of
+    `inp`'s arrays (feature_kernel_cases.inputs: twelve; feature_kernel_cases.embed: a batch the scheduler deals).  alpha: an explicit slack
+    schedule (rows, N + 1), one more banded device array the handle reads in place (set_slack_schedule's device form).  scheduling: the handle's
+    instance scheduling.  prime: in front of every measured launch one plain solve of the same batch through the fused entry without a step flag,
+    `iters` wired -- it exists so that the measured launch has an order -- behind which everything is restored; `order` of the result is the
+    permutation then in effect (None: the natural order)"""
     from mpc_gpu import _lib, pack_instance_bounds, pack_obstacle_mask
+    B = inp["x0"].shape[0]
     N, no, level = inp["N"], inp["no"], inp["level"]
     dev = torch.device("cuda:0")
     q = torch.cuda.current_stream().cuda_stream
     words = pack_obstacle_mask(inp["mask"]).view(np.int32)
     out = []
-    with make(mpc_gpu, N, no, B) as s:
+    with make(mpc_gpu, N, no, B, scheduling=scheduling) as s:
         fk.configure(s, case)
         W0, We0, r0 = cfg_values(s)
         g0 = inp["groups"][0]
@@ -76,18 +81,25 @@ def _launches(mpc_gpu, torch, case, inp, nan_absent_too, alpha=None):
             uploaded["slack schedule"] = (feat["alpha"], alpha)
         c = lambda a: a.cpu().numpy().copy()
         fl = _lib.STEP_SHIFT | _lib.STEP_PLANT | _lib.STEP_OBSTACLES | _lib.STEP_METRICS | _lib.STEP_RESET_ON_FAIL | _lib.STEP_ADVANCE_REF
-        for nan_absent in (False, True) if nan_absent_too else (False,):
-            obst = inp["obst"].copy()
-            if nan_absent:
-                obst[~inp["mask"]] = np.nan
+        def restore(obst):
             put(dx0, inp["x0"]); put(do, obst); put(flags, inp["ep_flags"]); put(feat["offset"], inp["offset"])
             u0.fill_(-5.0); cost.fill_(-5.0); margin.fill_(float("inf")); status.fill_(-9); iters.fill_(-9); steps.fill_(100); iacc.fill_(1000); sacc.fill_(0)
             s.reset_guess_dev(B, dx0, X, U, stream=q)
             torch.cuda.current_stream().synchronize()
+
+        for nan_absent in (False, True) if nan_absent_too else (False,):
+            obst = inp["obst"].copy()
+            if nan_absent:
+                obst[~inp["mask"]] = np.nan
+            restore(obst)
+            if prime:
+                s.closed_loop_step_dev(B, dx0, do, dg, X, U, u0, cost, status, iters, flags=0, ep_flags=flags, stream=q)
+                restore(obst)
+            order = s.instance_order(B) if prime else None      # (still there behind the restore: nothing but the scheduling switch or another batch size clears it)
             X0, U0 = c(X), c(U)
             s.closed_loop_step_dev(B, dx0, do, dg, X, U, u0, cost, status, iters, dn, RANDOMNESS, VMAX, flags=fl, min_margin=margin, ep_flags=flags, ep_steps=steps, stream=q)
             torch.cuda.current_stream().synchronize()
-            out.append(dict(name=name, X0=X0, U0=U0, obst_in=obst, x0=c(dx0), obst=c(do), X=c(X), U=c(U), u0=c(u0), cost=c(cost), margin=c(margin),
+            out.append(dict(name=name, order=order, X0=X0, U0=U0, obst_in=obst, x0=c(dx0), obst=c(do), X=c(X), U=c(U), u0=c(u0), cost=c(cost), margin=c(margin),
                             status=c(status), iters=c(iters), flags=c(flags), steps=c(steps), iacc=c(iacc), sacc=c(sacc), offset=c(feat["offset"]),
                             intact=bd.intact(), written=[k for k, (d, h) in uploaded.items() if not np.array_equal(c(d), h)]))
         s.set_accumulators(None, None)
@@ -177,6 +189,28 @@ def _bookkeeping(orc, inp, r, why):
     if not np.array_equal(r["steps"], ns): why.append(f"step counters {r['steps'].tolist()} vs {ns.tolist()}")
 
 
+def _nan_launch_is_the_first(inp, r, again, why, nan_ok=()):
+    """levels 3 and 4: the launch with NaN in the absent obstacles' entries (`again`) against the one without (`r`), over every row of the batch.
+    nan_ok: outputs in which a NaN of the first launch (a failed filler's) is one of the second"""
+    absent = ~inp["mask"]
+    assert absent.any()
+    for k in OUTPUTS:
+        if k == "obst":
+            # the absent obstacles move too.  Their positions stay NaN.  Their velocities go through the noise clamp fmin(fmax(v, -vmax), vmax),
+            # and IEEE fmax / fmin return the other operand of a NaN: fmax(NaN, -vmax) = -vmax, fmin(-vmax, vmax) = -vmax; the wall test then
+            # compares NaN, takes the plain arm and keeps the velocity.  So an absent row of an instance that stepped is exactly
+            # (NaN, NaN, -vmax, -vmax); the idle instance's rows are untouched, NaN throughout.
+            want = np.full(again[k].shape, np.nan)
+            want[..., 2:] = -VMAX
+            want[inp["ep_flags"] != 0] = np.nan
+            same = np.array_equal(again[k][~absent], r[k][~absent]) and np.array_equal(again[k][absent], want[absent], equal_nan=True)
+            if not same: why.append(f"absent rows after the step: {again[k][absent].tolist()[:4]}")
+        else:
+            same = np.array_equal(again[k], r[k], equal_nan=k in nan_ok)
+        if not same: why.append(f"NaN in the absent obstacles' entries changed {k}")
+    if not again["intact"] or again["written"]: why.append(f"second launch: bands {again['intact']}, written {again['written']}")
+
+
 def _body(mg, family, level, schedule_of=None):
     """schedule_of(orc, case): (inputs, alpha) -- the case's inputs in the schedule sweep's world and the explicit slack schedule (B, N + 1) layered
     on top of them (None: the case's own inputs, the built-in schedule)"""
@@ -195,23 +229,7 @@ def _body(mg, family, level, schedule_of=None):
         _against_oracle(orc, inp, r, why, rep, alpha)
         _bookkeeping(orc, inp, r, why)
         if again is not None:
-            absent = ~inp["mask"]
-            assert absent.any()
-            for k in OUTPUTS:
-                if k == "obst":
-                    # the absent obstacles move too.  Their positions stay NaN.  Their velocities go through the noise clamp fmin(fmax(v, -vmax), vmax),
-                    # and IEEE fmax / fmin return the other operand of a NaN: fmax(NaN, -vmax) = -vmax, fmin(-vmax, vmax) = -vmax; the wall test then
-                    # compares NaN, takes the plain arm and keeps the velocity.  So an absent row of an instance that stepped is exactly
-                    # (NaN, NaN, -vmax, -vmax); the idle instance's rows are untouched, NaN throughout.
-                    want = np.full(again[k].shape, np.nan)
-                    want[..., 2:] = -VMAX
-                    want[inp["ep_flags"] != 0] = np.nan
-                    same = np.array_equal(again[k][~absent], r[k][~absent]) and np.array_equal(again[k][absent], want[absent], equal_nan=True)
-                    if not same: why.append(f"absent rows after the step: {again[k][absent].tolist()[:4]}")
-                else:
-                    same = np.array_equal(again[k], r[k])
-                if not same: why.append(f"NaN in the absent obstacles' entries changed {k}")
-            if not again["intact"] or again["written"]: why.append(f"second launch: bands {again['intact']}, written {again['written']}")
+            _nan_launch_is_the_first(inp, r, again, why)
         print(f"{'FEATURE-KERNEL' if alpha is None else 'SLACK-SCHEDULE level ' + str(level)} {r['name']} N {case['N']} n_obst {case['no']}: converged {rep['converged']} of {B - 1} worst_gpu_oracle {rep['worst_gpu_oracle']:.3e} "
               f"adjudicated {rep['adjudicated']} worst_gpu_exact {rep['worst_gpu_exact']:.3e} status_borderline {rep['status_borderline']} "
               f"status {r['status'].tolist()} {'FAILED: ' + '; '.join(why) if why else 'ok'}")

@@ -15,7 +15,7 @@ import pytest
 
 import slack_schedule_cases as ss
 import sqp_cases as sc
-from feature_loop import Banded, assert_same, make, mg, on_own_stream
+from feature_loop import Banded, assert_same, make, mg, on_own_stream, smallest_scheduled_batch
 from helpers import fused_step_is_the_separate_calls, judge_against_oracle, oracle_reference
 from kernel_configs import apply, configs
 
@@ -242,31 +242,18 @@ def test_the_device_form_is_the_host_form(mg, family):
     on_own_stream(_device_form, mg, family)
 
 
-def _smallest_scheduled_batch(mpc_gpu, torch, pool, G):
-    """the first batch size, in steps of half the device's compute-unit count (+ 13, so that the last wavefront is partly empty), after whose first
-    launch instance_order is not None: the scheduler deals batches beyond one wavefront per SIMD, and how many SIMDs the device has is the library's
-    knowledge, not the test's"""
-    N, no = pool["N"], pool["no"]
-    P = pool["groups"][0]["P"]
-    step = max(1, torch.cuda.get_device_properties(0).multi_processor_count // 2)
-    for B in range(step + 13, ss.PACKED_POOL + 1, step):
-        with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B) as s:
-            s.set_lanes_per_stage(1); s.set_lanes_per_instance(G)
-            s.set_instance_scheduling(True)
-            s.reset_guess(pool["x0"][:B])
-            s.solve(pool["x0"][:B], P[:B], pool["goal"][:B])
-            if s.instance_order(B) is not None:
-                return B
-    raise AssertionError(f"no batch up to {ss.PACKED_POOL} is dealt by the instance scheduler")
+def _packed(G):
+    def configure(s):
+        s.set_lanes_per_stage(1); s.set_lanes_per_instance(G)
+    return configure
 
 
 def _packed_and_scheduled(mg, G):
-    import torch
     mpc_gpu, orc = mg
     pool = ss.packed_problem(orc)
     N, no = pool["N"], pool["no"]
     P = pool["groups"][0]["P"]
-    B = _smallest_scheduled_batch(mpc_gpu, torch, pool, G)
+    B = smallest_scheduled_batch(mpc_gpu, N, no, configure=_packed(G), key=("packed", G), limit=ss.PACKED_POOL)      # (raises if no batch of the pool is dealt)
     res = {}
     for on in (True, False):
         with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B) as s:

@@ -5,6 +5,8 @@ that of the same sequence of single-iteration launches stopped by the same rule 
      stop rule applied by the host between them: bit for bit, every case of sqp_cases, the iteration counts in a guard band;
   2. the same launch against the oracle's K-fold sequence (sqp_cases.oracle_sequence) within helpers.judge_against_oracle's tolerances (1e-6 on X,
      8e-6 on u), statuses and iteration counts equal, no adjudication (test_sqp_host.py holds what makes that fair);
+     and once more with the case's twelve instances embedded in a batch that the instance scheduler deals (sqp_cases.embedded: fillers with feature
+     rows of their own, DESIGN.md section 4g), scheduling on against off bit for bit over the whole batch, the iteration counts included;
   3. one level-5 iteration against the level-4 solve of the same handle with every lower feature set (feature_kernel_cases.inputs at level 4), by
      feature_loop.assert_same;
   4. the fused control step with three iterations against the separate calls, the idle instance, the reference offset;
@@ -14,7 +16,7 @@ import pytest
 
 import feature_kernel_cases as fk
 import sqp_cases as sc
-from feature_loop import Banded, assert_same, level_of, make, mg, on_own_stream, run
+from feature_loop import Banded, assert_same, level_of, make, mg, on_own_stream, run, smallest_scheduled_batch
 from helpers import fused_step_is_the_separate_calls, random_batch
 
 pytestmark = pytest.mark.gpu
@@ -110,15 +112,12 @@ def test_k_iterations_in_one_launch_are_k_launches_bit_for_bit(mg, cid):
     on_own_stream(_k_in_one_launch_is_k_launches, mg, cid)
 
 
-def _against_the_oracle(mg, cid):
-    mpc_gpu, orc = mg
-    c = sc.case(cid)
-    a = _one_launch(mg, c)
-    o = sc.oracle_sequence(orc, c)
+def _judge_against_the_sequence(a, o, c, tag):
+    """one launch's rows of the case's twelve instances (a) against the oracle's K-fold sequence (o)"""
     fin = sc.finite_instances()
     dX = np.abs(a["X"][fin] - o["X"][fin]).max(axis=(1, 2)); dU = np.abs(a["U"][fin] - o["U"][fin]).max(axis=(1, 2))
     du0 = np.abs(a["u0"][fin] - o["u0"][fin]).max(axis=1)
-    print(f"SQP-ORACLE {cid} {c['name']}: worst |dX| {dX.max():.3e} |dU| {dU.max():.3e} |du0| {du0.max():.3e}; iterations {a['sqp_iters'].tolist()} "
+    print(f"{tag} {c['id']} {c['name']}: worst |dX| {dX.max():.3e} |dU| {dU.max():.3e} |du0| {du0.max():.3e}; iterations {a['sqp_iters'].tolist()} "
           f"vs {o['sqp_iters'].tolist()}; interior-point iterations {a['iters'].tolist()} vs {o['iters'].tolist()}")
     assert np.array_equal(a["status"], o["status"]), (a["status"], o["status"])
     assert np.array_equal(a["sqp_iters"], o["sqp_iters"]), (a["sqp_iters"], o["sqp_iters"])
@@ -129,9 +128,97 @@ def _against_the_oracle(mg, cid):
     assert np.array_equal(a["X"][n], o["X"][n]) and np.array_equal(a["U"][n], o["U"][n])
 
 
+def _against_the_oracle(mg, cid):
+    mpc_gpu, orc = mg
+    c = sc.case(cid)
+    _judge_against_the_sequence(_one_launch(mg, c), sc.oracle_sequence(orc, c), c, "SQP-ORACLE")
+
+
 @pytest.mark.parametrize("cid", sc.IDS)
 def test_one_launch_against_the_oracle_sequence(mg, cid):
     on_own_stream(_against_the_oracle, mg, cid)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2b. the same launch in a batch the scheduler deals
+SCHEDULED_OUT = ("X", "U", "u0", "cost", "status", "iters", "sqp_iters")
+
+
+def _launch_embedded(mpc_gpu, torch, c, e, scheduling):
+    """the case's K iterations in one solve_dev of the embedded batch (sqp_cases.embedded) from the cold guess, on a fresh handle that reads every
+    per-instance table in its device form; in front of it a priming launch of the same batch -- so that the measured one has an order -- behind
+    which the iterate and every output sentinel are restored.  Every array in a guard band"""
+    from mpc_gpu import pack_instance_bounds, pack_obstacle_mask
+    N, no, Bs = e["N"], e["no"], e["Bs"]
+    dev = torch.device("cuda:0")
+    q = torch.cuda.current_stream().cuda_stream
+    with make(mpc_gpu, N, no, Bs, scheduling=scheduling, **c.get("cfg", {})) as s:
+        s.set_sqp(K, c["step_tol"])
+        bd = Banded(torch, dev)
+        put = lambda d, a: d.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
+        up = lambda a, mk=bd.f64: put(mk(*a.shape), a)
+        ins = dict(x0=e["x0"], P=e["P"], goal=e["goal"], yref=e["yref"], offset=e["offset"], W=e["W"], We=e["We"], r_safe=e["r_safe"],
+                   words=pack_obstacle_mask(e["mask"]).view(np.int32), table=pack_instance_bounds(s.cfg, Bs, **e["bounds"]))
+        d = {k: up(a, bd.i32 if a.dtype == np.int32 else bd.f64) for k, a in ins.items()}
+        s.set_reference(d["yref"], d["offset"])
+        s.set_instance_params(W=d["W"], We=d["We"], r_safe=d["r_safe"])
+        s.set_obstacle_mask(d["words"])
+        s.set_instance_bounds_dev(d["table"])
+        name = s.kernel_name(Bs, lookahead=False)
+        assert name == c["name"], (name, c["name"])      # before anything is launched
+        dX, dU = bd.f64(Bs, N + 1, 5), bd.f64(Bs, N, 2)
+        u0, cost = bd.f64(Bs, 2), bd.f64(Bs)
+        status, iters, nsqp = bd.i32(Bs), bd.i32(Bs), bd.i32(Bs)
+        s.set_sqp_iters_out(nsqp)
+
+        def restore():
+            put(dX, e["X0"]); put(dU, e["U0"])
+            u0.fill_(-5.0); cost.fill_(-5.0); status.fill_(-9); iters.fill_(-9); nsqp.fill_(-77)
+            torch.cuda.current_stream().synchronize()
+
+        restore()
+        s.solve_dev(Bs, d["x0"], d["P"], d["goal"], dX, dU, u0, cost, status, iters, stream=q)      # the priming launch
+        restore()
+        order = s.instance_order(Bs)
+        s.solve_dev(Bs, d["x0"], d["P"], d["goal"], dX, dU, u0, cost, status, iters, stream=q)
+        torch.cuda.current_stream().synchronize()
+        g = lambda a: a.cpu().numpy().copy()
+        return dict(X=g(dX), U=g(dU), u0=g(u0), cost=g(cost), status=g(status), iters=g(iters), sqp_iters=g(nsqp), order=order, intact=bd.intact(),
+                    inputs_kept=all(np.array_equal(g(d[k]), ins[k], equal_nan=True) for k in ins))
+
+
+def _scheduled(mg, cid):
+    import torch
+    from test_gpu_feature_scheduling import order_facts
+    mpc_gpu, orc = mg
+    c = sc.case(cid)
+    Bs = smallest_scheduled_batch(mpc_gpu)
+    pos = fk.positions(Bs)
+    e = sc.embedded(orc, c, Bs, pos)
+    runs = {}
+    for on in (True, False):
+        with torch.cuda.stream(torch.cuda.Stream()):
+            runs[on] = _launch_embedded(mpc_gpu, torch, c, e, on)
+    a, off = runs[True], runs[False]
+    live = pos[sc.finite_instances()]
+    why, moved, far = order_facts(a["order"], Bs, live)
+    print(f"SQP scheduled {cid} {c['name']} Bs {Bs}: moved {moved} of {len(live)} farthest {far}; fillers with status 0 / 2 / 4 "
+          f"{[int((a['status'][e['filler']] == v).sum()) for v in (0, 2, 4)]}, their iteration counts {np.bincount(a['sqp_iters'][e['filler']], minlength=K + 1).tolist()}")
+    assert not why, why
+    assert off["order"] is None
+    for r in (a, off):
+        assert r["intact"] and r["inputs_kept"]
+    for k in SCHEDULED_OUT:      # all Bs rows, scheduling on against off
+        assert np.array_equal(a[k], off[k], equal_nan=(k == "cost")), (k, np.nonzero((a[k] != off[k]).reshape(Bs, -1).any(axis=1))[0][:8])
+    _judge_against_the_sequence({k: a[k][pos] for k in SCHEDULED_OUT}, sc.oracle_sequence(orc, c), c, "SQP-ORACLE scheduled")
+    for n in (pos[sc.NAN_INSTANCE], e["nan_filler"]):      # a NaN in x0: status 4 at once, one iteration, the iterate untouched
+        assert a["status"][n] == 4 and a["sqp_iters"][n] == 1
+        assert np.array_equal(a["X"][n], e["X0"][n]) and np.array_equal(a["U"][n], e["U0"][n])
+    assert np.isin(a["status"], (0, 2, 4)).all() and ((a["sqp_iters"] >= 1) & (a["sqp_iters"] <= K)).all()
+
+
+@pytest.mark.parametrize("cid", sc.IDS)
+def test_one_launch_in_a_scheduled_batch_against_the_oracle_sequence(mg, cid):
+    on_own_stream(_scheduled, mg, cid)
 
 
 def _one_iteration_is_the_level_four_solve(mg, family):
