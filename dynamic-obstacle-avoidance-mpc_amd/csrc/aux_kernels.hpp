@@ -731,7 +731,7 @@ __global__ __launch_bounds__(64) void adjoint_check_kernel(KParams p, const doub
 }
 
 // ---- per-instance parameters (mpc_set_instance_params): the derived tables the IPAR kernels read ----
-// What a null group falls back to, and the handle's scalings (mpc_api.hip::ip_defaults)
+// What a null group falls back to, and the handle's scalings (mpc_api.hip::ip_from_config)
 struct IpDefaults {
     double cs, lm_stage, lm_term;      // as make_params: cost scale of the stages (dt or 1), LM term of the stages and of the terminal stage
     double W[6], We[4], r_safe;        // mpc_config

@@ -44,12 +44,20 @@ int fail(int code, const char *fmt, const char *a = "", const char *b = "")
 
 constexpr int kMaxEvents = 2048;   // solve launches timed per profiling window; later launches are not timed
 
+// A per-instance feature as the host sees it.  mode: 0 off, 1 host arrays (copied into a buffer of the handle's), 2 the caller's device arrays (used in
+// place); batch: the instances it covers -- those of the host arrays, max_batch for device arrays (a solve of more is refused).  feature_level, the coverage
+// refusals of attach_inputs and each feature's off path (one function, which its host setter and its _dev setter both call) go by this and nothing else
+struct feature { int mode, batch; };
+struct ip_tables { double *w, *r2, *rhit; };     // the derived tables the IPAR kernels read (KParams::ip_w, ip_r2, ip_rhit), max_batch rows each
+struct owned_buf { void *p; bool pinned; };      // one allocation of the handle's (own / disown below)
+
 }  // namespace
 
 struct mpc_handle {
     mpc_config cfg;
     int device, max_batch;
     hipStream_t stream;
+    std::vector<owned_buf> owned;     // every device / pinned buffer that belongs to the handle (own, disown); mpc_destroy releases what is recorded here
     double *dX, *dU;                  // handle-owned iterate
     double *d_x0, *d_P, *d_goal, *d_obst, *d_u0, *d_cost, *d_xa, *d_ua, *d_xb;   // staging for the host-pointer API
     int32_t *d_status, *d_iters;
@@ -68,8 +76,8 @@ struct mpc_handle {
     int32_t *d_order, *d_iters_sched; // ... the order for the next launch, and the iteration counts it is built from when the caller asks for none
     unsigned *d_sched_hist;           // ... per-block histograms of the counting sort [bins][blocks]
     int order_batch;                  // batch size d_order is a permutation of (0 = none yet)
-    double *d_alpha_own;              // handle-owned copy of a host slack schedule (mpc_set_slack_schedule)
-    int alpha_batch;                  // ... and the number of instances it was given for (a solve of more instances than that is refused)
+    feature alpha;                    // explicit slack schedule (mpc_set_slack_schedule[_dev])
+    double *d_alpha_own;              // ... handle-owned copy of a host schedule
     hipEvent_t sched_done;            // recorded behind the scheduling launches: a later launch on ANOTHER stream waits for it before it reads d_order
     hipStream_t sched_stream;         // the stream those launches ran on
     double *h_pack, *d_pack;          // small host-pointer batches (the reference's own scalar loop): inputs and outputs travel packed, one copy each way
@@ -83,22 +91,21 @@ struct mpc_handle {
     size_t gather_cap;                // ... and its capacity in doubles of d_gather_in
     const double *d_yref;             // per-stage reference in effect (mpc_set_reference[_dev]): d_yref_own or a caller's device array; null = the goal's
     int32_t *d_ref_off;               // ... its row offsets (d_ref_off_own, a caller's device array, or null = 0)
-    int ref_T, ref_batch;             // ... rows per instance, and the instances it covers (a solve of more is refused)
+    int ref_T;                        // ... rows per instance
+    feature ref;
     double *d_yref_own;               // handle-owned copies of a host reference (mpc_set_reference)
     int32_t *d_ref_off_own;
     size_t yref_own_cap;              // ... capacity of d_yref_own in doubles
-    int ip_mode;                      // per-instance parameters (mpc_set_instance_params[_dev]): 0 off, 1 host arrays (the tables below are final), 2 device arrays
-                                      // (used in place: the tables are derived again in front of every solve, on its stream)
-    int ip_batch;                     // ... the instances they cover (a solve of more is refused)
-    double *d_ip_w, *d_ip_r2, *d_ip_rhit;   // ... the derived tables the IPAR kernels read (KParams::ip_w, ip_r2, ip_rhit), max_batch rows, allocated on first use
+    feature ip;                       // per-instance parameters (mpc_set_instance_params[_dev]): mode 1, the tables below are final; mode 2, they are derived again from
+                                      // the caller's arrays in front of every solve, on its stream
+    ip_tables ip_own;                 // ... the tables of the caller's values, allocated on first use
     const double *ip_dev[4];          // ... mode 2: the caller's W, We, r_safe, r_hit (null = the handle's value)
-    bool ip_default;                  // ... the tables hold the handle's own mpc_config values in all max_batch rows (what an obstacle mask without instance parameters reads)
-    int om_mode;                      // per-instance obstacle masks (mpc_set_obstacle_mask[_dev]): 0 off, 1 host words (copied to d_omask_own), 2 device words (used in place)
-    int om_batch;                     // ... the instances they cover (a solve of more is refused)
+    ip_tables ip_cfg;                 // ... the tables of the handle's own mpc_config values in every row: what the kernels from the masks' level on read without
+                                      // instance parameters (ensure_companions; filled once, never written again)
+    feature om;                       // per-instance obstacle masks (mpc_set_obstacle_mask[_dev]): host words are copied to d_omask_own
     const uint32_t *d_omask;          // ... the words the OSEL kernels read (KParams::omask)
     uint32_t *d_omask_own;            // ... handle-owned copy of host words, max_batch, allocated on first use
-    int bd_mode;                      // per-instance box bounds (mpc_set_instance_bounds[_dev]): 0 off, 1 host arrays (packed into d_ip_b_own), 2 a device table (used in place)
-    int bd_batch;                     // ... the instances they cover (a solve of more is refused)
+    feature bd;                       // per-instance box bounds (mpc_set_instance_bounds[_dev]): host arrays are packed into d_ip_b_own
     const double *d_ip_b;             // ... the packed table the IBND kernels read (KParams::ip_b), [.][kIpB]
     double *d_ip_b_own;               // ... handle-owned table of the host form, max_batch rows, allocated on first use
     uint32_t *d_omask_full;           // ... every obstacle present in max_batch words: what the IBND kernels (built on the masks' code) read without a mask
@@ -127,6 +134,7 @@ constexpr int kMaxSplitN = 31;   // longest horizon of the two-lanes-per-stage m
 bool wide_rows(int n) { return n > 10; }
 constexpr int kPackBatch = 64;   // host-pointer solves of at most this many instances use the packed transfer (solve_common)
 bool partial_rows(const mpc_handle *h);
+int feature_level(const mpc_handle *h);
 
 mpc::KParams make_params(const mpc_config &c, int batch)
 {
@@ -179,6 +187,42 @@ int check_batch(mpc_handle *h, int batch)
 
 hipStream_t pick(mpc_handle *h, void *stream) { return stream ? (hipStream_t)stream : h->stream; }
 
+// One owner for the handle's memory.  own: `count` elements of device (or pinned host) memory on first use -- a pointer that is set already is left
+// alone -- recorded in the handle; disown: one of them given back early (a buffer that is regrown or switched off), its pointer nulled whatever the
+// runtime answers; mpc_destroy releases what is still recorded.  There is no list of pointers to keep beside these.
+template <class T> int own(mpc_handle *h, T **p, size_t count, bool pinned = false)
+{
+    if (*p) return MPC_OK;
+    void *q = nullptr;
+    h->owned.reserve(h->owned.size() + 1);
+    HIPCHK(pinned ? hipHostMalloc(&q, count * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, count * sizeof(T)));
+    h->owned.push_back({q, pinned});
+    *p = (T *)q;
+    return MPC_OK;
+}
+
+hipError_t release(const owned_buf &b) { return b.pinned ? hipHostFree(b.p) : hipFree(b.p); }
+
+template <class T> int disown(mpc_handle *h, T *&p)
+{
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; p && k < h->owned.size(); k++)
+        if (h->owned[k].p == (void *)p) { e = release(h->owned[k]); h->owned.erase(h->owned.begin() + k); break; }
+    p = nullptr;
+    return e == hipSuccess ? MPC_OK : fail(MPC_ERR_HIP, "hipFree: %s", hipGetErrorString(e));
+}
+
+// A host array into a buffer of the handle's (`cap` elements, allocated on first use), visible before the setter returns.  The wait in front of the
+// copy: an earlier solve may still read the buffer
+template <class T> int upload(mpc_handle *h, T **dst, size_t cap, const T *src, size_t n)
+{
+    int rc = own(h, dst, cap); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPC_OK;
+}
+
 // the kernel arguments of a solve: its inputs (the look-ahead P, or the obstacle states it is computed from inside the kernel) and outputs
 mpc::KParams solve_params(mpc_handle *h, int batch, const double *x0, const double *P, const double *obst, const double *goal, double *X, double *U,
                           double *u0, double *cost, int32_t *status, int32_t *iters)
@@ -195,7 +239,7 @@ mpc::KParams solve_params(mpc_handle *h, int batch, const double *x0, const doub
 // to this mapping; unless overridden.  Packing instances into one wavefront multiplies throughput for large batches.
 // (an obstacle mask is a run-time row count by nature: with one set, a handle whose count fills its capacity runs the run-time-count variants too;
 // the instance bounds are built on the masks' code, so they do the same)
-bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || h->om_mode != 0 || h->bd_mode != 0 || h->sqp_max > 1; }
+bool partial_rows(const mpc_handle *h) { return row_capacity(h->cfg.n_obst) != h->cfg.n_obst || feature_level(h) >= 3; }
 
 int pick_lanes(mpc_handle *h, int batch)
 {
@@ -289,7 +333,7 @@ int check_wide(const mpc_handle *h)
 // mask they read words of the handle's own that have every obstacle present
 // Several SQP iterations per launch (mpc_set_sqp), level 5: the IBND instantiations with one more flag -- the same mappings, plan and refusals; without
 // instance bounds they read a table of the handle's own bounds
-int feature_level(const mpc_handle *h) { return h->sqp_max > 1 ? 5 : h->bd_mode != 0 ? 4 : (h->om_mode != 0 ? 3 : (h->ip_mode != 0 ? 2 : (h->d_yref != nullptr ? 1 : 0))); }
+int feature_level(const mpc_handle *h) { return h->sqp_max > 1 ? 5 : (h->bd.mode ? 4 : (h->om.mode ? 3 : (h->ip.mode ? 2 : (h->ref.mode ? 1 : 0)))); }
 
 int check_feature_mapping(const mpc_handle *h)
 {
@@ -367,26 +411,19 @@ int create_resources(mpc_handle *h)
     h->simd_count = 4 * prop.multiProcessorCount;
     const size_t B = (size_t)h->max_batch, N = (size_t)h->cfg.N, no = (size_t)h->cfg.n_obst;
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc(&h->dX, B * (N + 1) * 5 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dU, B * N * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_x0, B * 5 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_P, B * (N + 1) * no * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_goal, B * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_obst, B * no * 4 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_u0, B * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_cost, B * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_xa, B * 5 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_ua, B * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_xb, B * 5 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_status, B * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&h->d_iters, B * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&h->d_order, B * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&h->d_iters_sched, B * sizeof(int32_t)));
     h->pack_in = 5 + 2 + (N + 1) * no * 2;      // x0 | goal | P (or the 4 n_obst obstacle states, which are fewer)
     h->pack_out = 2 + 1 + 1;                    // u0 | cost | status, iters (two int32 in one double's space)
-    HIPCHK(hipHostMalloc((void **)&h->h_pack, (size_t)kPackBatch * (h->pack_in + h->pack_out) * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipMalloc(&h->d_pack, (size_t)kPackBatch * (h->pack_in + h->pack_out) * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_sched_hist, (size_t)mpc::kSchedBins * ((B + mpc::kSchedChunk - 1) / mpc::kSchedChunk) * sizeof(unsigned)));
+    const size_t pack = (size_t)kPackBatch * (h->pack_in + h->pack_out);
+    int rc = MPC_OK;
+    auto get = [&](auto **p, size_t count, bool pinned = false) { if (!rc) rc = own(h, p, count, pinned); };      // (nothing more once one has failed)
+    get(&h->dX, B * (N + 1) * 5); get(&h->dU, B * N * 2);
+    get(&h->d_x0, B * 5); get(&h->d_P, B * (N + 1) * no * 2); get(&h->d_goal, B * 2); get(&h->d_obst, B * no * 4);
+    get(&h->d_u0, B * 2); get(&h->d_cost, B); get(&h->d_status, B); get(&h->d_iters, B);
+    get(&h->d_xa, B * 5); get(&h->d_ua, B * 2); get(&h->d_xb, B * 5);
+    get(&h->d_order, B); get(&h->d_iters_sched, B);
+    get(&h->d_sched_hist, (size_t)mpc::kSchedBins * ((B + mpc::kSchedChunk - 1) / mpc::kSchedChunk));
+    get(&h->h_pack, pack, true); get(&h->d_pack, pack);
+    if (rc) return rc;
     HIPCHK(hipMemsetAsync(h->d_iters_sched, 0, B * sizeof(int32_t), h->stream));
     HIPCHK(hipMemsetAsync(h->dX, 0, B * (N + 1) * 5 * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(h->dU, 0, B * N * 2 * sizeof(double), h->stream));
@@ -406,7 +443,7 @@ int launch_schedule(mpc_handle *h, int batch, const int32_t *d_iters, hipStream_
 // The derived per-instance tables (KParams::ip_w, ip_r2, ip_rhit) from the W, We, r_safe, r_hit in effect -- a null group takes the handle's mpc_config value.
 // ONE definition of every derived value for the host and the device (instance_params_kernel): each product and sum is a separately rounded operation,
 // as make_params forms Hd_stage, Hd_term, Wg, Weg and r2 on the host, so a batch that repeats the handle's own values reproduces the handle path bit for bit
-mpc::IpDefaults ip_defaults(const mpc_config &c)
+mpc::IpDefaults ip_from_config(const mpc_config &c)
 {
     mpc::IpDefaults d;
     const double dt = c.Tf / c.N;
@@ -421,78 +458,100 @@ mpc::IpDefaults ip_defaults(const mpc_config &c)
     return d;
 }
 
-int alloc_instance_tables(mpc_handle *h)
+// The derived tables of `rows` instances from host arrays (a null group: the handle's value) into one set of the handle's tables
+int upload_instance_tables(mpc_handle *h, ip_tables &t, int rows, const double *W, const double *We, const double *r_safe, const double *r_hit)
 {
-    const size_t B = (size_t)h->max_batch, no = (size_t)h->cfg.n_obst;
-    if (!h->d_ip_w) HIPCHK(hipMalloc(&h->d_ip_w, B * mpc::kIpW * sizeof(double)));
-    if (!h->d_ip_r2) HIPCHK(hipMalloc(&h->d_ip_r2, B * no * sizeof(double)));
-    if (!h->d_ip_rhit) HIPCHK(hipMalloc(&h->d_ip_rhit, B * no * sizeof(double)));
+    const size_t B = (size_t)h->max_batch, R = (size_t)rows, no = (size_t)h->cfg.n_obst;
+    const mpc::IpDefaults d = ip_from_config(h->cfg);
+    std::vector<double> tw(R * mpc::kIpW), t2(R * no), th(R * no);
+    for (int b = 0; b < rows; b++)
+        mpc::derive_instance_params(d, b, (int)no, W, We, r_safe, r_hit, tw.data(), t2.data(), th.data());
+    int rc = upload(h, &t.w, B * mpc::kIpW, tw.data(), tw.size());
+    if (!rc) rc = upload(h, &t.r2, B * no, t2.data(), t2.size());
+    if (!rc) rc = upload(h, &t.rhit, B * no, th.data(), th.size());
+    return rc;
+}
+
+uint32_t all_obstacles(const mpc_handle *h) { return h->cfg.n_obst >= 32 ? 0xffffffffu : ((1u << h->cfg.n_obst) - 1u); }
+
+// The packed bounds table of the IBND kernels, max_batch rows: the first `batch` from the host arrays (a null group: the handle's value), validated; the
+// rows behind them hold the handle's own values (no solve reads them).  batch 0: the handle's own bounds in every row
+int pack_bounds(const mpc_handle *h, int batch, const double *bx_lo, const double *bx_hi, const double *bu_lo, const double *bu_hi, std::vector<double> &tab)
+{
+    struct Group { const char *lo_name, *hi_name; const double *lo, *hi, *cfg_lo, *cfg_hi; int n, lo_at, hi_at; };
+    const Group groups[2] = {{"bu_lo", "bu_hi", bu_lo, bu_hi, h->cfg.bu_lo, h->cfg.bu_hi, 2, mpc::kIpBuLo, mpc::kIpBuHi},
+                             {"bx_lo", "bx_hi", bx_lo, bx_hi, h->cfg.bx_lo, h->cfg.bx_hi, 4, mpc::kIpBxLo, mpc::kIpBxHi}};
+    tab.resize((size_t)h->max_batch * mpc::kIpB);
+    for (const Group &g : groups) {
+        for (size_t k = 0; k < (size_t)batch * g.n; k++) {
+            if (g.lo && !(g.lo[k] >= -1e300 && g.lo[k] <= 1e300)) return fail(MPC_ERR_ARG, "instance bounds: %s entries must be finite", g.lo_name);
+            if (g.hi && !(g.hi[k] >= -1e300 && g.hi[k] <= 1e300)) return fail(MPC_ERR_ARG, "instance bounds: %s entries must be finite", g.hi_name);
+        }
+        for (int b = 0; b < h->max_batch; b++)
+            for (int k = 0; k < g.n; k++) {
+                const double lo = (g.lo && b < batch) ? g.lo[(size_t)b * g.n + k] : g.cfg_lo[k], hi = (g.hi && b < batch) ? g.hi[(size_t)b * g.n + k] : g.cfg_hi[k];
+                if (b < batch && !(lo < hi)) return fail(MPC_ERR_ARG, "instance bounds: %s must be below %s in every component", g.lo_name, g.hi_name);
+                tab[(size_t)b * mpc::kIpB + g.lo_at + k] = lo; tab[(size_t)b * mpc::kIpB + g.hi_at + k] = hi;
+            }
+    }
     return MPC_OK;
 }
 
-// the handle's own values in every row of the tables: what a solve with an obstacle mask and without instance parameters reads.  A host call (it
-// waits for the handle's stream); made where the mask or the instance bounds are set and where instance parameters are switched off under them, never in
-// front of a solve
-int fill_default_instance_tables(mpc_handle *h)
+// Companions: what the kernels of a feature level read for the features below it that the caller has not set -- from the masks' level (3) on the instance
+// tables of the handle's own values, from the bounds' (4) a mask with every obstacle present, at the SQP loop's (5) a table of the handle's own bounds.
+// Each lives in a buffer of its own, is filled once and never written again, so switching a feature below off needs no refill.  Host calls (they wait for
+// the handle's stream): made by the setters that raise the level (mask, bounds, SQP) in front of their state change, never in front of a solve
+int ensure_companions(mpc_handle *h, int level)
 {
-    if (h->ip_default) return MPC_OK;
-    int rc = alloc_instance_tables(h); if (rc) return rc;
-    const size_t B = (size_t)h->max_batch, no = (size_t)h->cfg.n_obst;
-    const mpc::IpDefaults d = ip_defaults(h->cfg);
-    std::vector<double> tw(B * mpc::kIpW), t2(B * no), th(B * no);
-    for (int b = 0; b < h->max_batch; b++)
-        mpc::derive_instance_params(d, b, (int)no, nullptr, nullptr, nullptr, nullptr, tw.data(), t2.data(), th.data());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ip_w, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ip_r2, t2.data(), t2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ip_rhit, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->ip_default = true;
-    return MPC_OK;
+    const size_t B = (size_t)h->max_batch;
+    int rc = MPC_OK;
+    if (level >= 3 && !h->ip_cfg.rhit) rc = upload_instance_tables(h, h->ip_cfg, h->max_batch, nullptr, nullptr, nullptr, nullptr);      // (rhit: the last it fills)
+    if (!rc && level >= 4 && !h->d_omask_full) {
+        const std::vector<uint32_t> full(B, all_obstacles(h));
+        rc = upload(h, &h->d_omask_full, B, full.data(), B);
+    }
+    if (!rc && level >= 5 && !h->d_ip_b_cfg) {
+        std::vector<double> tab;
+        rc = pack_bounds(h, 0, nullptr, nullptr, nullptr, nullptr, tab);
+        if (!rc) rc = upload(h, &h->d_ip_b_cfg, tab.size(), tab.data(), tab.size());
+    }
+    return rc;
 }
+
+// a feature that is on covers the batch, or the launch is refused with the feature's own sentence
+int check_covered(const feature &f, int batch, const char *refusal) { return f.mode && batch > f.batch ? fail(MPC_ERR_ARG, "%s", refusal) : MPC_OK; }
 
 // In front of a launch that reads them: the coverage checks and kernel arguments of the per-stage reference, the per-instance tables (derived here from
-// device arrays, mode 2) and, for a solve, the obstacle mask (with it the tables are attached whether or not instance parameters are set), the instance bounds
-// (which bring the tables and a mask with them) and the slack schedule
+// device arrays, mode 2) and, for a solve, of what its feature level reads beside them -- the caller's where a feature is set, the handle's companion
+// (ensure_companions) where it is not -- and the slack schedule
 enum AttachFor { kForSolve, kForLinearize };
 int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
 {
+    const bool solve = what == kForSolve;
+    const int level = solve ? feature_level(h) : 0;
     p.yref = h->d_yref; p.ref_off = h->d_ref_off; p.ref_T = h->ref_T;
-    if (h->d_yref && p.batch > h->ref_batch)
-        return fail(MPC_ERR_ARG, "the per-stage reference set by mpc_set_reference covers fewer instances than this %s", what == kForSolve ? "solve" : "call");
+    int rc = check_covered(h->ref, p.batch, solve ? "the per-stage reference set by mpc_set_reference covers fewer instances than this solve"
+                                                  : "the per-stage reference set by mpc_set_reference covers fewer instances than this call");
+    if (rc) return rc;
     if ((p.fused & MPC_STEP_ADVANCE_REF) && (!h->d_yref || !h->d_ref_off))
         return fail(MPC_ERR_ARG, "MPC_STEP_ADVANCE_REF needs a per-stage reference with offsets (mpc_set_reference[_dev])");
-    if (h->ip_mode) {
-        if (p.batch > h->ip_batch) return fail(MPC_ERR_ARG, "the per-instance parameters set by mpc_set_instance_params cover fewer instances than this solve");
-        if (h->ip_mode == 2) {
-            hipLaunchKernelGGL(mpc::instance_params_kernel, dim3((p.batch + 127) / 128), dim3(128), 0, s, ip_defaults(h->cfg), p.batch, h->cfg.n_obst,
-                               h->ip_dev[0], h->ip_dev[1], h->ip_dev[2], h->ip_dev[3], h->d_ip_w, h->d_ip_r2, h->d_ip_rhit);
-            HIPCHK(hipGetLastError());
-        }
-        p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
+    rc = check_covered(h->ip, p.batch, "the per-instance parameters set by mpc_set_instance_params cover fewer instances than this solve"); if (rc) return rc;
+    if (h->ip.mode == 2) {
+        hipLaunchKernelGGL(mpc::instance_params_kernel, dim3((p.batch + 127) / 128), dim3(128), 0, s, ip_from_config(h->cfg), p.batch, h->cfg.n_obst,
+                           h->ip_dev[0], h->ip_dev[1], h->ip_dev[2], h->ip_dev[3], h->ip_own.w, h->ip_own.r2, h->ip_own.rhit);
+        HIPCHK(hipGetLastError());
     }
-    if (what != kForSolve) return MPC_OK;
-    if (h->om_mode || h->bd_mode || h->sqp_max > 1) {
-        if (h->om_mode && p.batch > h->om_batch) return fail(MPC_ERR_ARG, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve");
-        if (!h->ip_mode) {
-            if (!h->ip_default) return fail(MPC_ERR_ARG, "internal: the default instance tables of the obstacle mask are not filled");
-            p.ip_w = h->d_ip_w; p.ip_r2 = h->d_ip_r2; p.ip_rhit = h->d_ip_rhit;
-        }
-        p.omask = h->om_mode ? h->d_omask : h->d_omask_full;
-    }
-    if (h->bd_mode) {
-        if (p.batch > h->bd_batch) return fail(MPC_ERR_ARG, "the instance bounds set by mpc_set_instance_bounds cover fewer instances than this solve");
-        p.ip_b = h->d_ip_b;
-    }
-    if (h->sqp_max > 1) {
-        if (!h->bd_mode) p.ip_b = h->d_ip_b_cfg;
-        p.sqp_max = h->sqp_max; p.sqp_tol = h->sqp_tol; p.sqp_iters = h->d_sqp_iters;
-    }
+    const ip_tables &t = h->ip.mode ? h->ip_own : h->ip_cfg;
+    if (h->ip.mode || level >= 3) { p.ip_w = t.w; p.ip_r2 = t.r2; p.ip_rhit = t.rhit; }
+    if (!solve) return MPC_OK;
+    rc = check_covered(h->om, p.batch, "the obstacle mask set by mpc_set_obstacle_mask covers fewer instances than this solve"); if (rc) return rc;
+    if (level >= 3) p.omask = h->om.mode ? h->d_omask : h->d_omask_full;
+    rc = check_covered(h->bd, p.batch, "the instance bounds set by mpc_set_instance_bounds cover fewer instances than this solve"); if (rc) return rc;
+    if (level >= 4) p.ip_b = h->bd.mode ? h->d_ip_b : h->d_ip_b_cfg;
+    if (level == 5) { p.sqp_max = h->sqp_max; p.sqp_tol = h->sqp_tol; p.sqp_iters = h->d_sqp_iters; }
     // an uploaded schedule covers the instances it was uploaded for: rows behind them were never written (the kernels index alpha[inst][i])
     p.alpha = h->d_alpha;
-    if (h->d_alpha && h->d_alpha == h->d_alpha_own && p.batch > h->alpha_batch)
-        return fail(MPC_ERR_ARG, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
-    return MPC_OK;
+    return check_covered(h->alpha, p.batch, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
 }
 
 int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
@@ -613,18 +672,11 @@ int mpc_destroy(mpc_handle *h)
     if (!h) return MPC_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *bufs[] = {h->dX, h->dU, h->d_x0, h->d_P, h->d_goal, h->d_obst, h->d_u0, h->d_cost, h->d_xa, h->d_ua, h->d_xb, h->d_status, h->d_iters,
-                    h->d_trace, h->d_alpha_own, h->d_order, h->d_iters_sched, h->d_sched_hist, h->d_yref_own, h->d_ref_off_own,
-                    h->d_ip_w, h->d_ip_r2, h->d_ip_rhit, h->d_omask_own, h->d_ip_b_own, h->d_omask_full, h->d_ip_b_cfg, h->d_refill_assign};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    if (h->d_pack) (void)hipFree(h->d_pack);
-    if (h->h_pack) (void)hipHostFree(h->h_pack);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->sched_done) (void)hipEventDestroy(h->sched_done);
     (void)mpc_comm_destroy(h);
-    if (h->d_gather_in) (void)hipFree(h->d_gather_in);
-    if (h->d_gather_out) (void)hipFree(h->d_gather_out);
+    for (const owned_buf &b : h->owned) (void)release(b);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MPC_OK;
@@ -1019,7 +1071,7 @@ int mpc_episode_refill_dev(mpc_handle *h, int slots, int scenario, unsigned seed
                                           memcmp(box, h->ring_box, sizeof(h->ring_box)) != 0))
         return fail(MPC_ERR_ARG, "mpc_episode_refill_dev: scenario, seed_first, seed_count or box differ from those of the ring's last fill (mpc_episode_ring_fill_dev)");
     HIPCHK(hipSetDevice(h->device));
-    if (!h->d_refill_assign) HIPCHK(hipMalloc(&h->d_refill_assign, (size_t)h->max_batch * sizeof(int32_t)));
+    int rc = own(h, &h->d_refill_assign, (size_t)h->max_batch); if (rc) return rc;
     hipStream_t s = pick(h, stream);
     hipLaunchKernelGGL(mpc::refill_decide_kernel, dim3(1), dim3(mpc::kRefillThreads), 0, s, slots, seed_count, max_steps, d_ep_flags, d_ep_steps,
                        h->d_refill_assign, d_cursor);
@@ -1230,8 +1282,7 @@ int mpc_comm_destroy(mpc_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     RCCLCHK(g_rccl.CommDestroy(h->comm));       // on failure the handle keeps the communicator: the caller may retry, nothing leaks silently
     h->comm = nullptr; h->comm_world = 0; h->comm_rank = 0;
-    if (h->d_gather_in) { (void)hipFree(h->d_gather_in); h->d_gather_in = nullptr; }          // sized for this communicator's world
-    if (h->d_gather_out) { (void)hipFree(h->d_gather_out); h->d_gather_out = nullptr; }
+    (void)disown(h, h->d_gather_in); (void)disown(h, h->d_gather_out);      // sized for this communicator's world
     h->gather_cap = 0;
     return MPC_OK;
 }
@@ -1257,11 +1308,11 @@ int mpc_allgather_cost(mpc_handle *h, int count, const double *cost, double *cos
     if (!cost || !cost_all) return fail(MPC_ERR_ARG, "null pointer");
     HIPCHK(hipSetDevice(h->device));
     if ((size_t)count > h->gather_cap) {
-        if (h->d_gather_in) { (void)hipFree(h->d_gather_in); h->d_gather_in = nullptr; }
-        if (h->d_gather_out) { (void)hipFree(h->d_gather_out); h->d_gather_out = nullptr; }
+        (void)disown(h, h->d_gather_in); (void)disown(h, h->d_gather_out);
         h->gather_cap = 0;
-        HIPCHK(hipMalloc(&h->d_gather_in, (size_t)count * sizeof(double)));
-        HIPCHK(hipMalloc(&h->d_gather_out, (size_t)count * h->comm_world * sizeof(double)));
+        int rc = own(h, &h->d_gather_in, (size_t)count);
+        if (!rc) rc = own(h, &h->d_gather_out, (size_t)count * h->comm_world);
+        if (rc) return rc;
         h->gather_cap = (size_t)count;
     }
     HIPCHK(hipMemcpyAsync(h->d_gather_in, cost, (size_t)count * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1273,36 +1324,38 @@ int mpc_allgather_cost(mpc_handle *h, int count, const double *cost, double *cos
 
 /* ------------------------------------------------- slack schedule -------------------------------------------------- */
 
+static int slack_schedule_off(mpc_handle *h) { h->alpha = {}; h->d_alpha = nullptr; return MPC_OK; }
+
 int mpc_set_slack_schedule_dev(mpc_handle *h, const double *d_alpha)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    h->d_alpha = d_alpha;
+    if (!d_alpha) return slack_schedule_off(h);
+    h->d_alpha = d_alpha; h->alpha = {2, h->max_batch};
     return MPC_OK;
 }
 
 int mpc_set_slack_schedule(mpc_handle *h, int batch, const double *alpha)
 {
     int rc = check_batch(h, batch); if (rc) return rc;
-    if (!alpha) { h->d_alpha = nullptr; return MPC_OK; }
+    if (!alpha) return slack_schedule_off(h);
     if (batch == 0) return fail(MPC_ERR_ARG, "a slack schedule needs batch >= 1");
     HIPCHK(hipSetDevice(h->device));
     const size_t row = (size_t)h->cfg.N + 1;
     for (size_t k = 0; k < (size_t)batch * row; k++)
         if (!(alpha[k] >= 0.0) || !(alpha[k] <= 1e300)) return fail(MPC_ERR_ARG, "slack weights must be finite and >= 0");
-    if (!h->d_alpha_own) HIPCHK(hipMalloc(&h->d_alpha_own, (size_t)h->max_batch * row * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(h->d_alpha_own, alpha, (size_t)batch * row * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->d_alpha = h->d_alpha_own;
-    h->alpha_batch = batch;
+    rc = upload(h, &h->d_alpha_own, (size_t)h->max_batch * row, alpha, (size_t)batch * row); if (rc) return rc;
+    h->d_alpha = h->d_alpha_own; h->alpha = {1, batch};
     return MPC_OK;
 }
 
 /* ------------------------------------------------ per-stage reference ------------------------------------------------ */
 
+static int reference_off(mpc_handle *h) { h->ref = {}; h->d_yref = nullptr; h->d_ref_off = nullptr; h->ref_T = 0; return MPC_OK; }
+
 int mpc_set_reference(mpc_handle *h, int batch, int T, const double *yref, const int32_t *offset)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!yref) { h->d_yref = nullptr; h->d_ref_off = nullptr; h->ref_T = 0; h->ref_batch = 0; return MPC_OK; }
+    if (!yref) return reference_off(h);
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "a per-stage reference needs batch in [1, max_batch]");
     if (T < 1) return fail(MPC_ERR_ARG, "a per-stage reference needs T >= 1 rows");
     const size_t n = (size_t)batch * T * 6;
@@ -1313,44 +1366,39 @@ int mpc_set_reference(mpc_handle *h, int batch, int T, const double *yref, const
             if (offset[b] < 0) return fail(MPC_ERR_ARG, "reference offsets must be >= 0");
     HIPCHK(hipSetDevice(h->device));
     const size_t cap = (size_t)h->max_batch * T * 6;
-    if (h->yref_own_cap < cap) {
+    if (h->yref_own_cap < cap) {      // the copy grows: the one place that switches a feature off before the call can still fail
         HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the old copy)
-        if (h->d_yref_own) HIPCHK(hipFree(h->d_yref_own));
-        h->d_yref_own = nullptr; h->yref_own_cap = 0; h->d_yref = nullptr;
-        HIPCHK(hipMalloc(&h->d_yref_own, cap * sizeof(double)));
+        reference_off(h); h->yref_own_cap = 0;
+        int rc = disown(h, h->d_yref_own); if (rc) return rc;
+        rc = own(h, &h->d_yref_own, cap); if (rc) return rc;
         h->yref_own_cap = cap;
     }
-    HIPCHK(hipMemcpyAsync(h->d_yref_own, yref, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (offset) {
-        if (!h->d_ref_off_own) HIPCHK(hipMalloc(&h->d_ref_off_own, (size_t)h->max_batch * sizeof(int32_t)));
-        HIPCHK(hipMemcpyAsync(h->d_ref_off_own, offset, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    int rc = upload(h, &h->d_yref_own, cap, yref, n);
+    if (!rc && offset) rc = upload(h, &h->d_ref_off_own, (size_t)h->max_batch, offset, (size_t)batch);
+    if (rc) return rc;
     h->d_yref = h->d_yref_own; h->d_ref_off = offset ? h->d_ref_off_own : nullptr;
-    h->ref_T = T; h->ref_batch = batch;
+    h->ref_T = T; h->ref = {1, batch};
     return MPC_OK;
 }
 
 int mpc_set_reference_dev(mpc_handle *h, int T, const double *d_yref, int32_t *d_offset)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!d_yref) { h->d_yref = nullptr; h->d_ref_off = nullptr; h->ref_T = 0; h->ref_batch = 0; return MPC_OK; }
+    if (!d_yref) return reference_off(h);
     if (T < 1) return fail(MPC_ERR_ARG, "a per-stage reference needs T >= 1 rows");
     h->d_yref = d_yref; h->d_ref_off = d_offset;
-    h->ref_T = T; h->ref_batch = h->max_batch;
+    h->ref_T = T; h->ref = {2, h->max_batch};
     return MPC_OK;
 }
 
 /* ---------------------------------------------- per-instance parameters ---------------------------------------------- */
 
+static int instance_params_off(mpc_handle *h) { h->ip = {}; return MPC_OK; }
+
 int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const double *We, const double *r_safe, const double *r_hit)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!W && !We && !r_safe && !r_hit) {
-        h->ip_mode = 0; h->ip_batch = 0;
-        if (h->om_mode || h->bd_mode || h->sqp_max > 1) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
-        return MPC_OK;
-    }
+    if (!W && !We && !r_safe && !r_hit) return instance_params_off(h);
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "per-instance parameters need batch in [1, max_batch]");
     const size_t B = (size_t)batch, no = (size_t)h->cfg.n_obst;
     auto all_in = [](const double *v, size_t n, double lo, bool open) {      // finite and >= lo (open: > lo); NaN fails every comparison
@@ -1362,122 +1410,81 @@ int mpc_set_instance_params(mpc_handle *h, int batch, const double *W, const dou
     if (!all_in(W, B * 6, 0.0, false) || !all_in(We, B * 4, 0.0, false)) return fail(MPC_ERR_ARG, "per-instance weights must be finite and >= 0");
     if (!all_in(r_safe, B * no, 0.0, true) || !all_in(r_hit, B * no, 0.0, true)) return fail(MPC_ERR_ARG, "per-instance radii must be finite and > 0");
     HIPCHK(hipSetDevice(h->device));
-    int rc = alloc_instance_tables(h); if (rc) return rc;
-    const mpc::IpDefaults d = ip_defaults(h->cfg);
-    std::vector<double> tw(B * mpc::kIpW), t2(B * no), th(B * no);
-    for (int b = 0; b < batch; b++)
-        mpc::derive_instance_params(d, b, (int)no, W, We, r_safe, r_hit, tw.data(), t2.data(), th.data());
-    HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the tables)
-    h->ip_default = false;
-    HIPCHK(hipMemcpyAsync(h->d_ip_w, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ip_r2, t2.data(), t2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ip_rhit, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->ip_mode = 1; h->ip_batch = batch;
+    int rc = upload_instance_tables(h, h->ip_own, batch, W, We, r_safe, r_hit); if (rc) return rc;
+    h->ip = {1, batch};
     return MPC_OK;
 }
 
 int mpc_set_instance_params_dev(mpc_handle *h, const double *d_W, const double *d_We, const double *d_r_safe, const double *d_r_hit)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!d_W && !d_We && !d_r_safe && !d_r_hit) {
-        h->ip_mode = 0; h->ip_batch = 0;
-        if (h->om_mode || h->bd_mode || h->sqp_max > 1) { HIPCHK(hipSetDevice(h->device)); return fill_default_instance_tables(h); }
-        return MPC_OK;
-    }
+    if (!d_W && !d_We && !d_r_safe && !d_r_hit) return instance_params_off(h);
     HIPCHK(hipSetDevice(h->device));
-    int rc = alloc_instance_tables(h); if (rc) return rc;
-    h->ip_default = false;
+    const size_t B = (size_t)h->max_batch, no = (size_t)h->cfg.n_obst;      // the tables attach_inputs derives into, in front of every solve
+    int rc = own(h, &h->ip_own.w, B * mpc::kIpW);
+    if (!rc) rc = own(h, &h->ip_own.r2, B * no);
+    if (!rc) rc = own(h, &h->ip_own.rhit, B * no);
+    if (rc) return rc;
     h->ip_dev[0] = d_W; h->ip_dev[1] = d_We; h->ip_dev[2] = d_r_safe; h->ip_dev[3] = d_r_hit;
-    h->ip_mode = 2; h->ip_batch = h->max_batch;
+    h->ip = {2, h->max_batch};
     return MPC_OK;
 }
 
 /* ---------------------------------------------- per-instance obstacle masks ---------------------------------------------- */
 
+static int obstacle_mask_off(mpc_handle *h) { h->om = {}; h->d_omask = nullptr; return MPC_OK; }
+
 int mpc_set_obstacle_mask(mpc_handle *h, int batch, const uint32_t *mask)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!mask) { h->om_mode = 0; h->om_batch = 0; h->d_omask = nullptr; return MPC_OK; }
+    if (!mask) return obstacle_mask_off(h);
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "an obstacle mask needs batch in [1, max_batch]");
-    const int no = h->cfg.n_obst;
-    const uint32_t legal = no >= 32 ? 0xffffffffu : ((1u << no) - 1u);
     for (int b = 0; b < batch; b++)
-        if (mask[b] & ~legal) return fail(MPC_ERR_ARG, "an obstacle mask word has a bit at or above n_obst");
+        if (mask[b] & ~all_obstacles(h)) return fail(MPC_ERR_ARG, "an obstacle mask word has a bit at or above n_obst");
     HIPCHK(hipSetDevice(h->device));
-    if (!h->d_omask_own) HIPCHK(hipMalloc(&h->d_omask_own, (size_t)h->max_batch * sizeof(uint32_t)));
-    if (!h->ip_mode) { int rc = fill_default_instance_tables(h); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the words)
-    HIPCHK(hipMemcpyAsync(h->d_omask_own, mask, (size_t)batch * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->d_omask = h->d_omask_own; h->om_mode = 1; h->om_batch = batch;
+    int rc = ensure_companions(h, 3);
+    if (!rc) rc = upload(h, &h->d_omask_own, (size_t)h->max_batch, mask, (size_t)batch);
+    if (rc) return rc;
+    h->d_omask = h->d_omask_own; h->om = {1, batch};
     return MPC_OK;
 }
 
 int mpc_set_obstacle_mask_dev(mpc_handle *h, const uint32_t *d_mask)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!d_mask) { h->om_mode = 0; h->om_batch = 0; h->d_omask = nullptr; return MPC_OK; }
+    if (!d_mask) return obstacle_mask_off(h);
     HIPCHK(hipSetDevice(h->device));
-    if (!h->ip_mode) { int rc = fill_default_instance_tables(h); if (rc) return rc; }
-    h->d_omask = d_mask; h->om_mode = 2; h->om_batch = h->max_batch;
+    int rc = ensure_companions(h, 3); if (rc) return rc;
+    h->d_omask = d_mask; h->om = {2, h->max_batch};
     return MPC_OK;
 }
 
 /* ---------------------------------------------- per-instance box bounds ---------------------------------------------- */
 
-// what the IBND kernels read beside the bounds when the caller has set neither: a mask with every obstacle present and the handle's own values in the
-// instance tables.  Host calls, made where the bounds are set
-static int bounds_companions(mpc_handle *h)
-{
-    if (!h->d_omask_full) {
-        const int no = h->cfg.n_obst;
-        const std::vector<uint32_t> full((size_t)h->max_batch, no >= 32 ? 0xffffffffu : ((1u << no) - 1u));
-        HIPCHK(hipMalloc(&h->d_omask_full, full.size() * sizeof(uint32_t)));
-        HIPCHK(hipMemcpyAsync(h->d_omask_full, full.data(), full.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return h->ip_mode ? MPC_OK : fill_default_instance_tables(h);
-}
+static int instance_bounds_off(mpc_handle *h) { h->bd = {}; h->d_ip_b = nullptr; return MPC_OK; }
 
 int mpc_set_instance_bounds(mpc_handle *h, int batch, const double *bx_lo, const double *bx_hi, const double *bu_lo, const double *bu_hi)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!bx_lo && !bx_hi && !bu_lo && !bu_hi) { h->bd_mode = 0; h->bd_batch = 0; h->d_ip_b = nullptr; return MPC_OK; }
+    if (!bx_lo && !bx_hi && !bu_lo && !bu_hi) return instance_bounds_off(h);
     if (batch < 1 || batch > h->max_batch) return fail(MPC_ERR_ARG, "instance bounds need batch in [1, max_batch]");
-    struct Group { const char *lo_name, *hi_name; const double *lo, *hi, *cfg_lo, *cfg_hi; int n, lo_at, hi_at; };
-    const Group groups[2] = {{"bu_lo", "bu_hi", bu_lo, bu_hi, h->cfg.bu_lo, h->cfg.bu_hi, 2, mpc::kIpBuLo, mpc::kIpBuHi},
-                             {"bx_lo", "bx_hi", bx_lo, bx_hi, h->cfg.bx_lo, h->cfg.bx_hi, 4, mpc::kIpBxLo, mpc::kIpBxHi}};
-    std::vector<double> tab((size_t)h->max_batch * mpc::kIpB);
-    for (const Group &g : groups) {
-        for (size_t k = 0; k < (size_t)batch * g.n; k++) {
-            if (g.lo && !(g.lo[k] >= -1e300 && g.lo[k] <= 1e300)) return fail(MPC_ERR_ARG, "instance bounds: %s entries must be finite", g.lo_name);
-            if (g.hi && !(g.hi[k] >= -1e300 && g.hi[k] <= 1e300)) return fail(MPC_ERR_ARG, "instance bounds: %s entries must be finite", g.hi_name);
-        }
-        for (int b = 0; b < h->max_batch; b++)
-            for (int k = 0; k < g.n; k++) {      // (rows behind `batch` hold the handle's own values; no solve reads them)
-                const double lo = (g.lo && b < batch) ? g.lo[(size_t)b * g.n + k] : g.cfg_lo[k], hi = (g.hi && b < batch) ? g.hi[(size_t)b * g.n + k] : g.cfg_hi[k];
-                if (b < batch && !(lo < hi)) return fail(MPC_ERR_ARG, "instance bounds: %s must be below %s in every component", g.lo_name, g.hi_name);
-                tab[(size_t)b * mpc::kIpB + g.lo_at + k] = lo; tab[(size_t)b * mpc::kIpB + g.hi_at + k] = hi;
-            }
-    }
+    std::vector<double> tab;
+    int rc = pack_bounds(h, batch, bx_lo, bx_hi, bu_lo, bu_hi, tab); if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    if (!h->d_ip_b_own) HIPCHK(hipMalloc(&h->d_ip_b_own, tab.size() * sizeof(double)));
-    int rc = bounds_companions(h); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));      // (an earlier solve may still read the table)
-    HIPCHK(hipMemcpyAsync(h->d_ip_b_own, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->d_ip_b = h->d_ip_b_own; h->bd_mode = 1; h->bd_batch = batch;
+    rc = ensure_companions(h, 4);
+    if (!rc) rc = upload(h, &h->d_ip_b_own, tab.size(), tab.data(), tab.size());
+    if (rc) return rc;
+    h->d_ip_b = h->d_ip_b_own; h->bd = {1, batch};
     return MPC_OK;
 }
 
 int mpc_set_instance_bounds_dev(mpc_handle *h, const double *d_bounds)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
-    if (!d_bounds) { h->bd_mode = 0; h->bd_batch = 0; h->d_ip_b = nullptr; return MPC_OK; }
+    if (!d_bounds) return instance_bounds_off(h);
     HIPCHK(hipSetDevice(h->device));
-    int rc = bounds_companions(h); if (rc) return rc;
-    h->d_ip_b = d_bounds; h->bd_mode = 2; h->bd_batch = h->max_batch;
+    int rc = ensure_companions(h, 4); if (rc) return rc;
+    h->d_ip_b = d_bounds; h->bd = {2, h->max_batch};
     return MPC_OK;
 }
 
@@ -1488,20 +1495,9 @@ int mpc_set_sqp(mpc_handle *h, int max_iter, double step_tol)
     if (!h) return fail(MPC_ERR_ARG, "null handle");
     if (max_iter < 1 || max_iter > MPC_MAX_SQP_ITER) return fail(MPC_ERR_ARG, "mpc_set_sqp: max_iter must be in [1, MPC_MAX_SQP_ITER]");
     if (!(step_tol >= 0.0)) return fail(MPC_ERR_ARG, "mpc_set_sqp: step_tol must be >= 0 (+inf is valid, NaN is not)");
-    if (max_iter > 1) {      // what the NSQP kernels read beside the features that are set: the bounds' companions and the handle's own bounds
+    if (max_iter > 1) {
         HIPCHK(hipSetDevice(h->device));
-        int rc = bounds_companions(h); if (rc) return rc;
-        if (!h->d_ip_b_cfg) {
-            std::vector<double> tab((size_t)h->max_batch * mpc::kIpB);
-            for (int b = 0; b < h->max_batch; b++) {
-                double *row = tab.data() + (size_t)b * mpc::kIpB;
-                for (int k = 0; k < 2; k++) { row[mpc::kIpBuLo + k] = h->cfg.bu_lo[k]; row[mpc::kIpBuHi + k] = h->cfg.bu_hi[k]; }
-                for (int k = 0; k < 4; k++) { row[mpc::kIpBxLo + k] = h->cfg.bx_lo[k]; row[mpc::kIpBxHi + k] = h->cfg.bx_hi[k]; }
-            }
-            HIPCHK(hipMalloc(&h->d_ip_b_cfg, tab.size() * sizeof(double)));
-            HIPCHK(hipMemcpyAsync(h->d_ip_b_cfg, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-        }
+        int rc = ensure_companions(h, 5); if (rc) return rc;
     }
     h->sqp_max = max_iter; h->sqp_tol = step_tol;
     return MPC_OK;
@@ -1560,14 +1556,13 @@ int mpc_debug_trace(mpc_handle *h, int enable, int batch, double *host_out)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    const size_t bytes = (size_t)h->max_batch * h->cfg.qp_iter_max * 4 * sizeof(double);
-    if (enable && !h->d_trace) { HIPCHK(hipMalloc(&h->d_trace, bytes)); HIPCHK(hipMemset(h->d_trace, 0, bytes)); }
+    const size_t count = (size_t)h->max_batch * h->cfg.qp_iter_max * 4;
+    if (enable && !h->d_trace) { int rc = own(h, &h->d_trace, count); if (rc) return rc; HIPCHK(hipMemset(h->d_trace, 0, count * sizeof(double))); }
     if (host_out && h->d_trace) {
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpy(host_out, h->d_trace, (size_t)batch * h->cfg.qp_iter_max * 4 * sizeof(double), hipMemcpyDeviceToHost));
     }
-    if (!enable && h->d_trace) { HIPCHK(hipFree(h->d_trace)); h->d_trace = nullptr; }
-    return MPC_OK;
+    return enable ? MPC_OK : disown(h, h->d_trace);
 }
 
 int mpc_set_lanes_per_instance(mpc_handle *h, int lanes)

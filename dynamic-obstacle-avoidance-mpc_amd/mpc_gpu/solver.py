@@ -28,6 +28,21 @@ def _ptr(a):
     return C.c_void_p(a.data_ptr())      # torch tensor (device or host)
 
 
+def _is_host(a):
+    """a numpy array or a (nested) list / tuple, which a setter validates and copies; anything else is a device tensor, used in place"""
+    return isinstance(a, (np.ndarray, list, tuple))
+
+
+def _check_device(message, t, shape, dtypes=None, contiguous=True):
+    """a device tensor that a setter uses in place (None: none given, nothing to check): its shape (None: any extent there), its dtype among `dtypes`
+    (torch's names; None: not looked at) and, unless switched off, contiguity -- or ValueError(message)"""
+    if t is None:
+        return
+    ok = len(t.shape) == len(shape) and all(want is None or have == want for have, want in zip(t.shape, shape))
+    if not ok or (dtypes is not None and str(t.dtype) not in dtypes) or (contiguous and not t.is_contiguous()):
+        raise ValueError(message)
+
+
 def pack_obstacle_mask(active):
     """bool (B, n_obst) -> np.uint32 (B,): bit j of word b set iff active[b, j] (the words of mpc_set_obstacle_mask; n_obst <= 32)"""
     a = np.asarray(active)
@@ -214,8 +229,7 @@ class BatchedMpc:
     def set_sqp_iters_out(self, out=None):
         """a contiguous int32 device tensor (max_batch,) that receives the SQP iterations each instance ran at every following solve (the word of an
         idle instance of the fused step is not written); None: off"""
-        if out is not None and (tuple(out.shape) != (self.max_batch,) or str(out.dtype) != "torch.int32" or not out.is_contiguous()):
-            raise ValueError(f"the SQP iteration counts need a contiguous int32 device tensor ({self.max_batch},)")
+        _check_device(f"the SQP iteration counts need a contiguous int32 device tensor ({self.max_batch},)", out, (self.max_batch,), ("torch.int32",))
         _lib.check(_lib.lib().mpc_set_sqp_iters_out_dev(self._h, _ptr(out)))
         self._sqp_out = out
         if out is not self._sqp_own:
@@ -224,16 +238,13 @@ class BatchedMpc:
     def set_slack_schedule(self, alpha):
         """parameterize_slack(), robot_ocp_problem.py:145-152: explicit zl_i = Zl_i = alpha[b, i] for the following solves
         (alpha (B, N+1), or a device tensor of shape (max_batch, N+1) used in place); None = the reference's schedule, in-kernel."""
-        if alpha is None:
-            _lib.check(_lib.lib().mpc_set_slack_schedule(self._h, 0, None))
-        elif isinstance(alpha, np.ndarray) or isinstance(alpha, (list, tuple)):
+        if _is_host(alpha):
             alpha = _f64(np.atleast_2d(alpha))
             if alpha.shape[1] != self.N + 1:
                 raise ValueError(f"alpha must be (B, {self.N + 1})")
             _lib.check(_lib.lib().mpc_set_slack_schedule(self._h, alpha.shape[0], _ptr(alpha)))
-        else:
-            if tuple(alpha.shape) != (self.max_batch, self.N + 1):
-                raise ValueError(f"a device schedule must be ({self.max_batch}, {self.N + 1})")
+        else:      # a device tensor, or None (the library's one off path)
+            _check_device(f"a device schedule must be ({self.max_batch}, {self.N + 1})", alpha, (self.max_batch, self.N + 1), contiguous=False)
             _lib.check(_lib.lib().mpc_set_slack_schedule_dev(self._h, _ptr(alpha)))
 
     def set_reference(self, yref, offset=None):
@@ -243,7 +254,7 @@ class BatchedMpc:
         device tensor (max_batch, T, 6) used in place with an optional int32 device tensor (max_batch,) of offsets.  None clears it."""
         if yref is None:
             _lib.check(_lib.lib().mpc_set_reference(self._h, 0, 0, None, None))
-        elif isinstance(yref, (np.ndarray, list, tuple)):
+        elif _is_host(yref):
             yref = _f64(yref)
             if yref.ndim != 3 or yref.shape[2] != 6:
                 raise ValueError(f"yref must be (B, T, 6), got {yref.shape}")
@@ -254,10 +265,8 @@ class BatchedMpc:
                     raise ValueError(f"offset must be ({yref.shape[0]},), got {off.shape}")
             _lib.check(_lib.lib().mpc_set_reference(self._h, yref.shape[0], yref.shape[1], _ptr(yref), _ptr(off)))
         else:
-            if len(yref.shape) != 3 or yref.shape[0] != self.max_batch or yref.shape[2] != 6 or not yref.is_contiguous():
-                raise ValueError(f"a device reference must be a contiguous ({self.max_batch}, T, 6) tensor")
-            if offset is not None and (tuple(offset.shape) != (self.max_batch,) or str(offset.dtype) != "torch.int32" or not offset.is_contiguous()):
-                raise ValueError(f"device offsets must be a contiguous int32 tensor ({self.max_batch},)")
+            _check_device(f"a device reference must be a contiguous ({self.max_batch}, T, 6) tensor", yref, (self.max_batch, None, 6))
+            _check_device(f"device offsets must be a contiguous int32 tensor ({self.max_batch},)", offset, (self.max_batch,), ("torch.int32",))
             _lib.check(_lib.lib().mpc_set_reference_dev(self._h, int(yref.shape[1]), _ptr(yref), _ptr(offset)))
 
     def _instance_arrays(self, W, We, r_safe, r_hit):
@@ -279,18 +288,13 @@ class BatchedMpc:
         r_hit[b, j] (default r_safe[b, j] - (cfg.r_safe - 1.2)).  A group left None keeps the handle's value; all None switches the feature off.
         numpy arrays (B, 6), (B, 4), (B, n_obst) -- r_safe and r_hit also (B,), one radius per instance -- are validated and copied; device tensors
         (max_batch, ...) of exactly the C shapes are used in place (the values they hold when a solve is launched).  Not both kinds in one call."""
-        given = [a for a in (W, We, r_safe, r_hit) if a is not None]
-        if not given:
-            _lib.check(_lib.lib().mpc_set_instance_params(self._h, 0, None, None, None, None))
-            return
-        host = [isinstance(a, (np.ndarray, list, tuple)) for a in given]
-        if all(host):
+        host = {_is_host(a) for a in (W, We, r_safe, r_hit) if a is not None}
+        if host == {True}:
             (W, We, r_safe, r_hit), B = self._instance_arrays(W, We, r_safe, r_hit)
             _lib.check(_lib.lib().mpc_set_instance_params(self._h, B, _ptr(W), _ptr(We), _ptr(r_safe), _ptr(r_hit)))
-        elif not any(host):
+        elif True not in host:      # device tensors, or nothing given (the library's one off path)
             for name, a, cols in (("W", W, 6), ("We", We, 4), ("r_safe", r_safe, self.n_obst), ("r_hit", r_hit, self.n_obst)):
-                if a is not None and (tuple(a.shape) != (self.max_batch, cols) or str(a.dtype) != "torch.float64" or not a.is_contiguous()):
-                    raise ValueError(f"a device {name} must be a contiguous float64 tensor ({self.max_batch}, {cols})")
+                _check_device(f"a device {name} must be a contiguous float64 tensor ({self.max_batch}, {cols})", a, (self.max_batch, cols), ("torch.float64",))
             _lib.check(_lib.lib().mpc_set_instance_params_dev(self._h, _ptr(W), _ptr(We), _ptr(r_safe), _ptr(r_hit)))
         else:
             raise ValueError("per-instance parameters: host arrays or device tensors, not both in one call")
@@ -300,17 +304,14 @@ class BatchedMpc:
         obstacle has no rows at any stage, no penalty in the reported cost and (unless STEP_MARGIN_ALL) no part in the fused step's margin; its entries
         in P / obst may hold anything.  A bool array (B, n_obst) is packed (pack_obstacle_mask), validated and copied; a device tensor (max_batch,) of
         int32 / uint32 words is used in place (the words it holds when a solve is launched; rewrite them on the device at will); None switches off."""
-        if active is None:
-            _lib.check(_lib.lib().mpc_set_obstacle_mask(self._h, 0, None))
-        elif isinstance(active, (np.ndarray, list, tuple)):
+        if _is_host(active):
             a = mask_rows(active, self.n_obst)
             if a.shape[0] < 1 or a.shape[0] > self.max_batch:
                 raise ValueError(f"active has {a.shape[0]} rows, the handle holds 1 .. {self.max_batch} instances")
             words = pack_obstacle_mask(a)
             _lib.check(_lib.lib().mpc_set_obstacle_mask(self._h, int(words.shape[0]), _ptr(words)))
-        else:
-            if tuple(active.shape) != (self.max_batch,) or str(active.dtype) not in ("torch.int32", "torch.uint32") or not active.is_contiguous():
-                raise ValueError(f"a device obstacle mask must be a contiguous int32 / uint32 tensor ({self.max_batch},)")
+        else:      # a device tensor, or None (the library's one off path)
+            _check_device(f"a device obstacle mask must be a contiguous int32 / uint32 tensor ({self.max_batch},)", active, (self.max_batch,), ("torch.int32", "torch.uint32"))
             _lib.check(_lib.lib().mpc_set_obstacle_mask_dev(self._h, _ptr(active)))
 
     def set_instance_bounds(self, bx_lo=None, bx_hi=None, bu_lo=None, bu_hi=None):
@@ -331,11 +332,7 @@ class BatchedMpc:
     def set_instance_bounds_dev(self, table):
         """The packed device form (mpc_set_instance_bounds_dev): a contiguous float64 device tensor (max_batch, 12) in the layout of pack_instance_bounds,
         used in place and not validated (the values it holds when a solve is launched; rewrite them on the device at will); None switches off."""
-        if table is None:
-            _lib.check(_lib.lib().mpc_set_instance_bounds_dev(self._h, None))
-            return
-        if tuple(table.shape) != (self.max_batch, BOUNDS_COLS) or str(table.dtype) != "torch.float64" or not table.is_contiguous():
-            raise ValueError(f"a device bounds table must be a contiguous float64 tensor ({self.max_batch}, {BOUNDS_COLS})")
+        _check_device(f"a device bounds table must be a contiguous float64 tensor ({self.max_batch}, {BOUNDS_COLS})", table, (self.max_batch, BOUNDS_COLS), ("torch.float64",))
         _lib.check(_lib.lib().mpc_set_instance_bounds_dev(self._h, _ptr(table)))
 
     def plant_step(self, x, u):

@@ -29,6 +29,17 @@ int main(void)
     if (mpc_solve_obst(NULL, 1, buf, buf, buf, buf, buf, ibuf, ibuf) != MPC_ERR_ARG) bad++;
     if (mpc_set_slack_schedule(NULL, 1, buf) != MPC_ERR_ARG) bad++;
     if (mpc_set_slack_schedule_dev(NULL, buf) != MPC_ERR_ARG) bad++;
+    uint32_t words[2] = {0};
+    if (mpc_set_reference(NULL, 1, 1, buf, ibuf) != MPC_ERR_ARG) bad++;
+    if (mpc_set_reference_dev(NULL, 1, buf, ibuf) != MPC_ERR_ARG) bad++;
+    if (mpc_set_instance_params(NULL, 1, buf, buf, buf, buf) != MPC_ERR_ARG) bad++;
+    if (mpc_set_instance_params_dev(NULL, buf, buf, buf, buf) != MPC_ERR_ARG) bad++;
+    if (mpc_set_obstacle_mask(NULL, 1, words) != MPC_ERR_ARG) bad++;
+    if (mpc_set_obstacle_mask_dev(NULL, words) != MPC_ERR_ARG) bad++;
+    if (mpc_set_instance_bounds(NULL, 1, buf, buf, buf, buf) != MPC_ERR_ARG) bad++;
+    if (mpc_set_instance_bounds_dev(NULL, buf) != MPC_ERR_ARG) bad++;
+    if (mpc_set_sqp(NULL, 2, 0.0) != MPC_ERR_ARG) bad++;
+    if (mpc_set_sqp_iters_out_dev(NULL, ibuf) != MPC_ERR_ARG) bad++;
     if (mpc_shift(NULL, 1) != MPC_ERR_ARG) bad++;
     if (mpc_reset_guess(NULL, 1, buf) != MPC_ERR_ARG) bad++;
     if (mpc_plant_step(NULL, 1, buf, buf, buf) != MPC_ERR_ARG) bad++;
