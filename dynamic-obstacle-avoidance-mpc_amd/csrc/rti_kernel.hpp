@@ -838,9 +838,18 @@ __device__ __forceinline__ void systolic_factor(int stage, int N, const StageLin
 // spread over lanes 0..7 of the first 16-lane row of the instance's lane group: lane j holds column j of P~, W~_t, H~aug_t,
 // T = P~ W~ and M~ = H~aug + W~' T.  A product A B then is one  v_fmac_f64_dpp acc_r, A_r(row_newbcast:k), B_k  per (r, k)
 // for ALL columns at once -- the DPP operand reads lane k's register, i.e. an element of the left factor, at full FP64 rate.
-// Per stage: 30 + 40 + 12 DPP FMAs and ~35 ordinary instructions, against ~330 for the one-lane systolic sweep.
+// Per stage: 25 + 12 + 10 DPP FMAs and ~35 ordinary instructions, against ~330 for the one-lane systolic sweep.
 //   * only upper-triangle entries of P~ are ever read (element (r, k), r <= k, is lane k's register r), so the cost-to-go
 //     stays symmetric by construction, exactly as in systolic_factor;
+//   * ROW 5 OF T, M~ AND P~ IS NOT COMPUTED.  The gradient q of the cost-to-go would exist twice, as column 5 (lane 5, registers 0..4) and as
+//     row 5 (register 5 of lanes 0..4); only the column is consumed.  Rows 0..4 of T read registers 0..4 alone (T[r] takes P~[min(r, k)] of lane
+//     max(r, k), k <= 4, plus its own Pc[r] * d5); T[5] would feed only M[5] (row 5 of W~ is e_5', so W~' T has a k = 5 term in row 5 alone); K~ and the
+//     L D L' factors take registers 6, 7 (the feed-forward: lane 5's own M[6], M[7]); P~+[r], r < 5, takes M[r], lane r's M[6], M[7] and K~; and
+//     only K~ (lanes 0..5) and the factors (lane 0) leave the sweep.  Register 5 of T, M~ and P~ is a closed loop in every lane (in lane 5: the
+//     constant term of the value function, unused as well): 14 instructions per stage -- 1 multiply + 5 DPP FMAs of T, 1 add + 5 DPP FMAs of M~,
+//     2 DPP FMAs of P~+ -- that rowpar_factor and its one-block twins do not issue.  Results are those of the six-row sweep bit for bit: every
+//     surviving accumulator keeps its terms in their order.  rowpar_factor_six_rows keeps the old text for the few instantiations that answer the
+//     shorter one with scratch; rowpar_factor2 (block-2, never dispatched by default) still carries the row: one of its instantiations did the same;
 //   * the per-stage operands come from LDS, staged there by the lanes that own the stages (W~ once per solve, its affine
 //     column and H~aug once per interior-point iteration) and fetched one stage ahead; K~, k and the LDL' factors return
 //     through LDS (they overlay rows 0, 1 of the consumed H~aug_t);
@@ -923,21 +932,20 @@ __device__ __forceinline__ uint32_t lds_address(const void *p) { return (uint32_
 //   kSweepTermsParent      the sweep before this change, bit for bit (copied column, terms in the order of the rows of W~): rti_wide_kernel, whose QPs with
 //                          hundreds of active rows amplify a last-bit difference to 1e-5.
 enum { kSweepTermsOutOfPlace = 0, kSweepTermsCopied = 1, kSweepTermsParent = 2 };
-template <class LT, int TERMS = (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace)>
-__device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool worker_row, double dt)
+
+// THE SIX-ROW FORM OF THE SWEEP (rowpar_factor<LT, TERMS, true>): row 5 of T, M~ and P~ -- register 5 of every lane, the gradient of the cost-to-go a second time and
+// in lane 5 the constant term of the value function -- carried along although nothing reads it (14 instructions per stage: see rowpar_factor below, which this is
+// the text of before that row was dropped, instruction for instruction).  Kept for the instantiations whose register allocation answers the five-row form with
+// MORE scratch (DESIGN.md section 4 names them); same results, bit for bit.
+template <class LT, int TERMS>
+__device__ __forceinline__ void rowpar_factor_six_rows(int lane, int N, const LT L, bool worker_row, double dt)
 {
     constexpr int WS = LT::WS, HS = LT::HS;
-    const int j = lane & 7, l15 = lane & 15;    // column; lanes 8..15 of a row mirror 0..7
+    const int j = lane & 7, l15 = lane & 15;
     const bool store = worker_row && l15 < 6, store0 = worker_row && l15 == 0;
-    const double d5 = (j == 5) ? 1.0 : 0.0;     // row 5 of W~ is e_5'
-    // Results overlay rows 0, 1 of the consumed H~aug_t: K~[0][j] at [j], K~[1][j] at [8 + j], 1/d0, l, 1/d1 at [6], [7], [14].
-    // Stores are unconditional: lanes with nothing to store write into dead parts of the same block ([16..63]).
-    // (two per-lane pointers, the rest are immediate offsets: K~[1][j] is 8 words behind K~[0][j], 1/d1 8 words behind 1/d0, and the
-    // dead words an idle lane hits instead -- 48, 56 resp. 50, 51, 58 -- lie in rows 6, 7 of the block, consumed one stage earlier)
+    const double d5 = (j == 5) ? 1.0 : 0.0;
     double *kp = L.R + (store ? j : LT::DEADK), *fp = L.R + (store0 ? 6 : LT::DEADF);
     const double *wp = L.W + j, *hp = L.H + j;
-    // compact layout only: rows 2..4 of W~ (lane 5: the stage's b[2..4], stride WS; other lanes: the wavefront's constant table, stride 0)
-    // and rows 6, 7 of H~aug through a per-lane base
     const double *bp = nullptr, *h6p = nullptr;
     int bstride = 0;
     if constexpr (LT::COMPACT) {
@@ -960,10 +968,9 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
             for (int i = 0; i < 8; i++) Hc[i] = hp[HS * t + i * 8];
         }
     };
-    // first half of a stage: T = P~ W~ from the previous stage's P~ (the upper-left 6 x 6 of its M registers)
     auto stepT = [&](const double Wc[5], const double Pc[8], double T[6]) {
 #pragma unroll
-        for (int r = 0; r < 6; r++) T[r] = Pc[r] * d5;                 // k = 5 term of T = P~ W~
+        for (int r = 0; r < 6; r++) T[r] = Pc[r] * d5;
         asm volatile(
             "s_nop 1\n"
             "v_fmac_f64_dpp %0, %6, %12 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
@@ -999,21 +1006,9 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
             : "+v"(T[0]), "+v"(T[1]), "+v"(T[2]), "+v"(T[3]), "+v"(T[4]), "+v"(T[5])
             : "v"(Pc[0]), "v"(Pc[1]), "v"(Pc[2]), "v"(Pc[3]), "v"(Pc[4]), "v"(Pc[5]), "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]));
     };
-    // second half: M~ (accumulated onto the H~aug column in M), L D L' of Muu, column j of K~, P~+ in M[0..5]
     auto stepM = [&](int t, const double Wc[5], const double Hc[8], const double T[6], double M[8]) {
-        // M~ = H~aug + W~' T over the structural non-zeros of W~ (A = I + E, B: 24 of 40 products, 7 of them with a constant), rows 6, 7 (the input block) first;
-        // then Muu = M~[6..7][6..7] -> L D L' (backward stable, see systolic_factor) and column j of K~ = -Muu^-1 M~[u, :],
-        // computed in every lane and hand-interleaved with the remaining rows of M~ so that the serial reciprocal / Newton
-        // chain (~15 dependent instructions) hides behind independent FMAs
         double K0, K1, i00, l, i11, m67;
         if constexpr (TERMS == kSweepTermsOutOfPlace) {
-            // every accumulator's FIRST term is an out-of-place instruction that reads the fetched H~aug word as its addend: the term of W~' T whose
-            // factor all lanes know -- W~[i][i] = 1 (A = I + E) for M[0..4], row 5 of W~ = e_5' for M[5], W~[3][6] = W~[4][7] = dt for M[6], M[7].
-            // No copy of the column, and no DPP FMA that multiplies by a broadcast 1.0 or dt.  (Accumulating IN PLACE into registers that a
-            // ds_read2_b64 delivers makes the compiler copy them out right behind the request, a stall: DESIGN.md section 4.)  Those of M[2..4]
-            // are issued inside the block, as fillers of the reciprocal chain; the chain's temporaries live in its result registers
-            // (e, r in K0, K1; m66, m77 in i00, i11 until the reciprocals replace them), so the block holds no more registers than it did.
-            // (asm, not C++: the compiler turns fma(dt, T, Hc) into an in-place v_fmac on the fetched register -- and copies the next request out again)
             asm volatile("v_fma_f64 %3, %10, %8, %13\nv_fma_f64 %4, %10, %9, %14\nv_add_f64 %0, %11, %5\nv_add_f64 %1, %12, %6\nv_add_f64 %2, %15, %7\n"
                          : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
                          : "v"(T[0]), "v"(T[1]), "v"(T[5]), "v"(T[3]), "v"(T[4]), "s"(dt), "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[6]), "v"(Hc[7]), "v"(Hc[5]));
@@ -1063,7 +1058,6 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
                 : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]),
                   "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]));
         } else if constexpr (TERMS == kSweepTermsParent) {
-            // the sweep as it was before the out-of-place first terms, bit for bit: copies of the column, the terms in the order of the rows of W~, T[5] last
             asm volatile("v_mov_b64_e32 %0, %8\nv_mov_b64_e32 %1, %9\nv_mov_b64_e32 %2, %10\nv_mov_b64_e32 %3, %11\n"
                          "v_mov_b64_e32 %4, %12\nv_mov_b64_e32 %5, %13\nv_mov_b64_e32 %6, %14\nv_mov_b64_e32 %7, %15\n"
                          : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
@@ -1119,8 +1113,6 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
                 : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]));
             M[5] += T[5];                                                  // r = 5 term of W~' T
         } else {
-            // the accumulators start as copies of the H~aug column made HERE, after the operands have arrived; the terms
-            // with a constant factor come first, as above
             asm volatile("v_mov_b64_e32 %0, %8\nv_mov_b64_e32 %1, %9\nv_mov_b64_e32 %2, %10\nv_mov_b64_e32 %3, %11\n"
                          "v_mov_b64_e32 %4, %12\nv_mov_b64_e32 %5, %13\nv_mov_b64_e32 %6, %14\nv_mov_b64_e32 %7, %15\n"
                          : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])
@@ -1178,7 +1170,6 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
         }
         kp[HS * t] = K0; kp[HS * t + 8] = K1;
         fp[HS * t] = i00; fp[HS * t + 1] = l; fp[HS * t + 8] = i11;
-        // P~+ = M~[0..5][0..5] + M~[0..5][u] K~   (M~[i][6] = M~[6][i] is lane i's register 6)
         asm volatile(
             "s_nop 1\n"
             "v_fmac_f64_dpp %0, %6, %8 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
@@ -1196,12 +1187,285 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
             : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[5])
             : "v"(M[6]), "v"(M[7]), "v"(K0), "v"(K1));
     };
+    double Wa[5], Ha[8], Wb[5], Hb[8], Pa[8], Pb[8], T[6];
+#pragma unroll
+    for (int r = 0; r < 6; r++) Pb[r] = hp[HS * N + r * 8];
+    fetch(N - 1, Wa, Ha);
+    asm volatile("s_nop 4");
+    int t = N - 1;
+    for (; t >= 1; t -= 2) {
+        stepT(Wa, Pb, T); fetch(t - 1, Wb, Hb); stepM(t, Wa, Ha, T, Pa);
+        stepT(Wb, Pa, T); fetch(t - 2, Wa, Ha); stepM(t - 1, Wb, Hb, T, Pb);
+    }
+    if (t == 0) { stepT(Wa, Pb, T); stepM(0, Wa, Ha, T, Pa); }
+}
+
+// SIX: the six-row form above (the instantiations that answer the five-row form with more scratch), else rows 0..4 only
+template <class LT, int TERMS = (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), bool SIX = false>
+__device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool worker_row, double dt)
+{
+    if constexpr (SIX) {
+        rowpar_factor_six_rows<LT, TERMS>(lane, N, L, worker_row, dt);
+        return;
+    }
+    constexpr int WS = LT::WS, HS = LT::HS;
+    const int j = lane & 7, l15 = lane & 15;    // column; lanes 8..15 of a row mirror 0..7
+    const bool store = worker_row && l15 < 6, store0 = worker_row && l15 == 0;
+    const double d5 = (j == 5) ? 1.0 : 0.0;     // row 5 of W~ is e_5'
+    // Results overlay rows 0, 1 of the consumed H~aug_t: K~[0][j] at [j], K~[1][j] at [8 + j], 1/d0, l, 1/d1 at [6], [7], [14].
+    // Stores are unconditional: lanes with nothing to store write into dead parts of the same block ([16..63]).
+    // (two per-lane pointers, the rest are immediate offsets: K~[1][j] is 8 words behind K~[0][j], 1/d1 8 words behind 1/d0, and the
+    // dead words an idle lane hits instead -- 48, 56 resp. 50, 51, 58 -- lie in rows 6, 7 of the block, consumed one stage earlier)
+    double *kp = L.R + (store ? j : LT::DEADK), *fp = L.R + (store0 ? 6 : LT::DEADF);
+    const double *wp = L.W + j, *hp = L.H + j;
+    // compact layout only: rows 2..4 of W~ (lane 5: the stage's b[2..4], stride WS; other lanes: the wavefront's constant table, stride 0)
+    // and rows 6, 7 of H~aug through a per-lane base
+    const double *bp = nullptr, *h6p = nullptr;
+    int bstride = 0;
+    if constexpr (LT::COMPACT) {
+        bp = (j == 5) ? L.W + 16 : L.C + 3 * j;
+        bstride = (j == 5) ? WS : 0;
+        h6p = L.H + (j < 5 ? 49 : (j == 5 ? 46 : (j == 6 ? 48 : 50)));
+    }
+    auto fetch = [&](int t, double Wc[5], double Hc[8]) {
+        if constexpr (LT::COMPACT) {
+            Wc[0] = wp[WS * t]; Wc[1] = wp[WS * t + 8];
+#pragma unroll
+            for (int m = 0; m < 3; m++) Wc[2 + m] = bp[bstride * t + m];
+#pragma unroll
+            for (int i = 0; i < 5; i++) Hc[i] = hp[HS * t + i * 8];
+            Hc[6] = h6p[HS * t]; Hc[7] = h6p[HS * t + 1];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; k++) Wc[k] = wp[WS * t + k * 8];
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if (i != 5) Hc[i] = hp[HS * t + i * 8];               // row 5 of H~aug feeds the dead row of M~ only: not fetched
+        }
+    };
+    // first half of a stage: T = P~ W~ from the previous stage's P~ (the upper-left 6 x 6 of its M registers)
+    // (rows 0..4: the symmetric P~ is read as its upper triangle, P~[r][k] = register min(r, k) of lane max(r, k), so no term reads register 5 of any lane)
+    auto stepT = [&](const double Wc[5], const double Pc[8], double T[5]) {
+#pragma unroll
+        for (int r = 0; r < 5; r++) T[r] = Pc[r] * d5;                 // k = 5 term of T = P~ W~
+        asm volatile(
+            "s_nop 1\n"
+            "v_fmac_f64_dpp %0, %5, %10 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %5, %10 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %5, %10 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %5, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %5, %10 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %0, %5, %11 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %6, %11 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %6, %11 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %6, %11 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %6, %11 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %0, %5, %12 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %6, %12 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %7, %12 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %7, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %7, %12 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %0, %5, %13 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %6, %13 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %7, %13 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %8, %13 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %8, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %0, %5, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %6, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %7, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %8, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %9, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            : "+v"(T[0]), "+v"(T[1]), "+v"(T[2]), "+v"(T[3]), "+v"(T[4])
+            : "v"(Pc[0]), "v"(Pc[1]), "v"(Pc[2]), "v"(Pc[3]), "v"(Pc[4]), "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]));
+    };
+    // second half: M~ (accumulated onto the H~aug column in M), L D L' of Muu, column j of K~, P~+ in M[0..4]
+    auto stepM = [&](int t, const double Wc[5], const double Hc[8], const double T[5], double M[8]) {
+        // M~ = H~aug + W~' T over the structural non-zeros of W~ (A = I + E, B: 24 of 40 products, 7 of them with a constant), rows 6, 7 (the input block) first;
+        // then Muu = M~[6..7][6..7] -> L D L' (backward stable, see systolic_factor) and column j of K~ = -Muu^-1 M~[u, :],
+        // computed in every lane and hand-interleaved with the remaining rows of M~ so that the serial reciprocal / Newton
+        // chain (~15 dependent instructions) hides behind independent FMAs
+        double K0, K1, i00, l, i11, m67;
+        if constexpr (TERMS == kSweepTermsOutOfPlace) {
+            // every accumulator's FIRST term is an out-of-place instruction that reads the fetched H~aug word as its addend: the term of W~' T whose
+            // factor all lanes know -- W~[i][i] = 1 (A = I + E) for M[0..4], W~[3][6] = W~[4][7] = dt for M[6], M[7] (M[5], the dead row, is not formed).
+            // No copy of the column, and no DPP FMA that multiplies by a broadcast 1.0 or dt.  (Accumulating IN PLACE into registers that a
+            // ds_read2_b64 delivers makes the compiler copy them out right behind the request, a stall: DESIGN.md section 4.)  Those of M[2..4]
+            // are issued inside the block, as fillers of the reciprocal chain; the chain's temporaries live in its result registers
+            // (e, r in K0, K1; m66, m77 in i00, i11 until the reciprocals replace them), so the block holds no more registers than it did.
+            // (asm, not C++: the compiler turns fma(dt, T, Hc) into an in-place v_fmac on the fetched register -- and copies the next request out again)
+            asm volatile("v_fma_f64 %2, %8, %6, %11\nv_fma_f64 %3, %8, %7, %12\nv_add_f64 %0, %9, %4\nv_add_f64 %1, %10, %5\n"
+                         : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[6]), "=&v"(M[7])
+                         : "v"(T[0]), "v"(T[1]), "v"(T[3]), "v"(T[4]), "s"(dt), "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[6]), "v"(Hc[7]));
+            // fillers of the chain, one per gap from the first reciprocal on: the first terms of M[2], M[3], then the DPP FMAs of M[2..4], each accumulator's
+            // in its own order (nine for the eleven gaps in front of 1/d1: the last two Newton steps run back to back)
+            asm volatile(
+                "s_nop 1\n"
+                "v_fmac_f64_dpp %4, %11, %16 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %4, %12, %17 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %4, %13, %18 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %3, %11, %16 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %3, %12, %17 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_add_f64 %2, %23, %20\n"
+                "v_mov_b64_dpp %9, %4 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %7, %3 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %10, %3 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %6, %7\n"
+                "v_add_f64 %0, %21, %18\n"
+                "v_fma_f64 %5, -%7, %6, 1.0\n"
+                "v_add_f64 %1, %22, %19\n"
+                "v_fma_f64 %6, %5, %6, %6\n"
+                "v_fmac_f64_dpp %2, %11, %16 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %5, -%7, %6, 1.0\n"
+                "v_fmac_f64_dpp %0, %11, %16 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %7, %5, %6, %6\n"
+                "v_fmac_f64_dpp %1, %11, %16 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %8, %10, %7\n"
+                "v_fmac_f64_dpp %2, %12, %17 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %9, -%8, %10, %9\n"
+                "v_fmac_f64_dpp %0, %12, %17 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %6, %9\n"
+                "v_fmac_f64_dpp %1, %12, %17 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %5, -%9, %6, 1.0\n"
+                "v_fmac_f64_dpp %2, %13, %18 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %6, %5, %6, %6\n"
+                "v_fma_f64 %5, -%9, %6, 1.0\n"
+                "v_fma_f64 %9, %5, %6, %6\n"
+                "v_fma_f64 %5, %8, %3, -%4\n"
+                "v_mul_f64 %6, %5, %9\n"
+                "v_mul_f64 %5, %3, %7\n"
+                "v_fma_f64 %5, -%8, %6, -%5\n"
+                : "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "+v"(M[6]), "+v"(M[7]),
+                  "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m67)
+                : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]),
+                  "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]));
+        } else if constexpr (TERMS == kSweepTermsParent) {
+            // the sweep as it was before the out-of-place first terms, bit for bit: copies of the column, the terms in the order of the rows of W~
+            // (fillers of the chain: one DPP FMA of M[1..4] per gap up to the last Newton step of 1/d1, each accumulator's in its own order)
+            asm volatile("v_mov_b64_e32 %0, %7\nv_mov_b64_e32 %1, %8\nv_mov_b64_e32 %2, %9\nv_mov_b64_e32 %3, %10\n"
+                         "v_mov_b64_e32 %4, %11\nv_mov_b64_e32 %5, %12\nv_mov_b64_e32 %6, %13\n"
+                         : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[6]), "=&v"(M[7])
+                         : "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]), "v"(Hc[6]), "v"(Hc[7]));
+            double m66, m77, e_, r_;
+            asm volatile(
+                "s_nop 1\n"
+                "v_fmac_f64_dpp %5, %17, %22 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %17, %22 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %5, %18, %23 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %18, %23 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %19, %24 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %5, %20, %25 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %21, %26 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %17, %22 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %12, %5 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %13, %5 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %14, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %16, %12\n"
+                "v_fmac_f64_dpp %3, %17, %22 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%12, %16, 1.0\n"
+                "v_fmac_f64_dpp %4, %17, %22 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, %15, %16, %16\n"
+                "v_fmac_f64_dpp %2, %17, %22 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%12, %16, 1.0\n"
+                "v_fmac_f64_dpp %1, %18, %23 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %9, %15, %16, %16\n"
+                "v_fmac_f64_dpp %2, %18, %23 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %10, %13, %9\n"
+                "v_fmac_f64_dpp %3, %18, %23 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %14, -%10, %13, %14\n"
+                "v_fmac_f64_dpp %4, %18, %23 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %16, %14\n"
+                "v_fmac_f64_dpp %2, %19, %24 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%14, %16, 1.0\n"
+                "v_fmac_f64_dpp %4, %19, %24 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, %15, %16, %16\n"
+                "v_fmac_f64_dpp %3, %20, %25 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%14, %16, 1.0\n"
+                "v_fmac_f64_dpp %4, %21, %26 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %11, %15, %16, %16\n"
+                "v_fma_f64 %15, %10, %5, -%6\n"
+                "v_mul_f64 %8, %15, %11\n"
+                "v_mul_f64 %15, %5, %9\n"
+                "v_fma_f64 %7, -%10, %8, -%15\n"
+                : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[6]), "+v"(M[7]),
+                  "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m66), "=&v"(m67), "=&v"(m77), "=&v"(e_), "=&v"(r_)
+                : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]));
+        } else {
+            // the accumulators start as copies of the H~aug column made HERE, after the operands have arrived; the terms
+            // with a constant factor come first, as above
+            asm volatile("v_mov_b64_e32 %0, %7\nv_mov_b64_e32 %1, %8\nv_mov_b64_e32 %2, %9\nv_mov_b64_e32 %3, %10\n"
+                         "v_mov_b64_e32 %4, %11\nv_mov_b64_e32 %5, %12\nv_mov_b64_e32 %6, %13\n"
+                         : "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[6]), "=&v"(M[7])
+                         : "v"(Hc[0]), "v"(Hc[1]), "v"(Hc[2]), "v"(Hc[3]), "v"(Hc[4]), "v"(Hc[6]), "v"(Hc[7]));
+            double m66, m77, e_, r_;
+            asm volatile(
+                "s_nop 1\n"
+                "v_fmac_f64_dpp %5, %20, %25 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %21, %26 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %5, %17, %22 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %17, %22 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %5, %18, %23 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %18, %23 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %19, %24 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %17, %22 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %12, %5 row_newbcast:6 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %13, %5 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_mov_b64_dpp %14, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %16, %12\n"
+                "v_fmac_f64_dpp %3, %20, %25 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%12, %16, 1.0\n"
+                "v_fmac_f64_dpp %4, %21, %26 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, %15, %16, %16\n"
+                "v_fmac_f64_dpp %2, %19, %24 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%12, %16, 1.0\n"
+                "v_fmac_f64_dpp %1, %18, %23 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %9, %15, %16, %16\n"
+                "v_fmac_f64_dpp %2, %17, %22 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_mul_f64 %10, %13, %9\n"
+                "v_fmac_f64_dpp %3, %17, %22 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %14, -%10, %13, %14\n"
+                "v_fmac_f64_dpp %4, %17, %22 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_rcp_f64_e32 %16, %14\n"
+                "v_fmac_f64_dpp %2, %18, %23 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%14, %16, 1.0\n"
+                "v_fmac_f64_dpp %3, %18, %23 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %16, %15, %16, %16\n"
+                "v_fmac_f64_dpp %4, %18, %23 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %15, -%14, %16, 1.0\n"
+                "v_fmac_f64_dpp %4, %19, %24 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+                "v_fma_f64 %11, %15, %16, %16\n"
+                "v_fma_f64 %15, %10, %5, -%6\n"
+                "v_mul_f64 %8, %15, %11\n"
+                "v_mul_f64 %15, %5, %9\n"
+                "v_fma_f64 %7, -%10, %8, -%15\n"
+                : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[6]), "+v"(M[7]),
+                  "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m66), "=&v"(m67), "=&v"(m77), "=&v"(e_), "=&v"(r_)
+                : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]));
+        }
+        kp[HS * t] = K0; kp[HS * t + 8] = K1;
+        fp[HS * t] = i00; fp[HS * t + 1] = l; fp[HS * t + 8] = i11;
+        // P~+ = M~[0..4][0..5] + M~[0..4][u] K~   (M~[i][6] = M~[6][i] is lane i's register 6)
+        asm volatile(
+            "s_nop 1\n"
+            "v_fmac_f64_dpp %0, %5, %7 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %5, %7 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %5, %7 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %5, %7 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %5, %7 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %0, %6, %8 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %1, %6, %8 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %2, %6, %8 row_newbcast:2 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %3, %6, %8 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+            "v_fmac_f64_dpp %4, %6, %8 row_newbcast:4 row_mask:0xf bank_mask:0xf\n"
+            : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4])
+            : "v"(M[6]), "v"(M[7]), "v"(K0), "v"(K1));
+    };
     // Two operand sets (W, H) and two result sets (P) alternate: while stage t runs on (Wa, Ha) with P~ taken from Pb and its
     // result going to Pa, the operands of stage t-1 are requested into (Wb, Hb) right after the T block -- a stage is ~600
     // cycles of arithmetic, far more than the LDS latency of a lone wavefront.  No register copies between stages.
-    double Wa[5], Ha[8], Wb[5], Hb[8], Pa[8], Pb[8], T[6];
+    // (Pa, Pb, Ha, Hb are indexed by the row of M~ / H~aug: element 5, the dead row, is never written or read and owns no register)
+    double Wa[5], Ha[8], Wb[5], Hb[8], Pa[8], Pb[8], T[5];
 #pragma unroll
-    for (int r = 0; r < 6; r++) Pb[r] = hp[HS * N + r * 8];           // P~_N = H~aug_N[0..5][0..5]
+    for (int r = 0; r < 5; r++) Pb[r] = hp[HS * N + r * 8];           // P~_N = H~aug_N[0..4][0..5]
     fetch(N - 1, Wa, Ha);
     // DPP hazards: 5 wait states after an EXEC write (the branches in front of this sweep), covered once here; inside the loop nothing
     // writes EXEC (stores are unconditional), and the 2 wait states after a VALU write of a DPP source are the s_nop 1 at the head of
@@ -1437,6 +1701,9 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
 // (s_waitcnt lgkmcnt(7) before a T block: the 4 accumulator requests and 3 stores younger than its W~ operands; lgkmcnt(10) before an M
 // block: 3 stores and the 7 requests of the next stage).  Two stages per loop pass (register sets a / b), the operands of a stage are
 // requested right after the T block of the stage before; an odd horizon ends with a single stage.  Fixed registers v100..v183.
+// Rows 0..4 only, as in rowpar_factor: nothing writes T[5] (v[142:143]) or accumulates into M[5] (v[110:111] / v[126:127], which the pair request of
+// H~aug rows 4, 5 -- and of the terminal block -- still fills: the requests and the lgkmcnt counts are those of the six-row text); the fillers of the
+// reciprocal chain that belonged to M[5] are gone, the others stand where they stood.
 // per-layout pieces of the text below: MPC_FACTOR_ASM_T(FAD) = dense blocks (RowLds), MPC_FACTOR_ASM_T(FAC) = compact blocks (RowLdsC)
 #define FAD_D5 "%5"
 #define FAD_HN "%6"
@@ -1498,38 +1765,32 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_mul_f64 v[136:137], v[120:121], " V##_D5 "\n" \
         "v_mul_f64 v[138:139], v[122:123], " V##_D5 "\n" \
         "v_mul_f64 v[140:141], v[124:125], " V##_D5 "\n" \
-        "v_mul_f64 v[142:143], v[126:127], " V##_D5 "\n" \
         "s_nop 1\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[144:145] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[116:117], v[144:145] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[116:117], v[144:145] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[116:117], v[144:145] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[116:117], v[144:145] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[116:117], v[144:145] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[146:147] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[146:147] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[118:119], v[146:147] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[118:119], v[146:147] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[118:119], v[146:147] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[118:119], v[146:147] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[148:149] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[148:149] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[120:121], v[148:149] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[120:121], v[148:149] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[120:121], v[148:149] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[120:121], v[148:149] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[120:121], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[122:123], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[122:123], v[150:151] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[122:123], v[150:151] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[120:121], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[122:123], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[124:125], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[124:125], v[152:153] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_read2_b64 v[154:157], %0 offset0:0 offset1:8\n" \
         "ds_read2_b64 v[158:161], " V##_W_L23 "\n" \
         "ds_read_b64 v[162:163], " V##_W_L4 "\n" \
@@ -1555,7 +1816,6 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_rcp_f64_e32 v[182:183], v[174:175]\n" \
         "v_fmac_f64_dpp v[108:109], v[152:153], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_add_f64 v[110:111], v[110:111], v[142:143]\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
         "v_fmac_f64_dpp v[102:103], v[146:147], v[134:135] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
@@ -1565,24 +1825,19 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_mul_f64 v[170:171], v[176:177], v[168:169]\n" \
         "v_fmac_f64_dpp v[108:109], v[144:145], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[178:179], -v[170:171], v[176:177], v[178:179]\n" \
-        "v_fmac_f64_dpp v[110:111], v[144:145], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[178:179]\n" \
         "v_fmac_f64_dpp v[104:105], v[146:147], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
         "v_fmac_f64_dpp v[108:109], v[146:147], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[146:147], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
         "v_fmac_f64_dpp v[106:107], v[146:147], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[172:173], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[148:149], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], v[170:171], v[112:113], -v[114:115]\n" \
         "v_fmac_f64_dpp v[108:109], v[148:149], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[166:167], v[180:181], v[172:173]\n" \
         "v_mul_f64 v[180:181], v[112:113], v[168:169]\n" \
-        "v_fmac_f64_dpp v[110:111], v[150:151], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[164:165], -v[170:171], v[166:167], -v[180:181]\n" \
-        "v_fmac_f64_dpp v[110:111], v[152:153], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_write2_b64 %2, v[164:165], v[166:167] " V##_K_U "\n" \
         "ds_write2_b64 %3, v[168:169], v[170:171] " V##_F_U "\n" \
         "ds_write_b64 %3, v[172:173] " V##_F_U8 "\n" \
@@ -1592,51 +1847,43 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_fmac_f64_dpp v[104:105], v[112:113], v[164:165] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[106:107], v[112:113], v[164:165] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[108:109], v[112:113], v[164:165] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[110:111], v[112:113], v[164:165] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[100:101], v[114:115], v[166:167] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[102:103], v[114:115], v[166:167] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[104:105], v[114:115], v[166:167] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[106:107], v[114:115], v[166:167] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[108:109], v[114:115], v[166:167] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[110:111], v[114:115], v[166:167] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "s_waitcnt lgkmcnt(7)\n" \
         "v_mul_f64 v[132:133], v[100:101], " V##_D5 "\n" \
         "v_mul_f64 v[134:135], v[102:103], " V##_D5 "\n" \
         "v_mul_f64 v[136:137], v[104:105], " V##_D5 "\n" \
         "v_mul_f64 v[138:139], v[106:107], " V##_D5 "\n" \
         "v_mul_f64 v[140:141], v[108:109], " V##_D5 "\n" \
-        "v_mul_f64 v[142:143], v[110:111], " V##_D5 "\n" \
         "s_nop 1\n" \
         "v_fmac_f64_dpp v[132:133], v[100:101], v[154:155] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[100:101], v[154:155] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[100:101], v[154:155] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[100:101], v[154:155] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[100:101], v[154:155] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[100:101], v[154:155] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[100:101], v[156:157] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[102:103], v[156:157] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[102:103], v[156:157] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[102:103], v[156:157] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[102:103], v[156:157] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[102:103], v[156:157] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[100:101], v[158:159] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[102:103], v[158:159] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[104:105], v[158:159] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[104:105], v[158:159] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[104:105], v[158:159] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[104:105], v[158:159] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[100:101], v[160:161] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[102:103], v[160:161] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[104:105], v[160:161] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[106:107], v[160:161] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[106:107], v[160:161] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[106:107], v[160:161] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[100:101], v[162:163] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[102:103], v[162:163] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[104:105], v[162:163] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[106:107], v[162:163] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[108:109], v[162:163] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[108:109], v[162:163] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_add_u32_e32 %0, " V##_W_DEC ", %0\n" \
         "v_add_u32_e32 %1, " V##_H_DEC ", %1\n" V##_MORE_DEC \
         "ds_read2_b64 v[144:147], " V##_W_U01 "\n" \
@@ -1664,7 +1911,6 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_rcp_f64_e32 v[182:183], v[174:175]\n" \
         "v_fmac_f64_dpp v[124:125], v[162:163], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_add_f64 v[126:127], v[126:127], v[142:143]\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
         "v_fmac_f64_dpp v[118:119], v[156:157], v[134:135] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
@@ -1674,24 +1920,19 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_mul_f64 v[170:171], v[176:177], v[168:169]\n" \
         "v_fmac_f64_dpp v[124:125], v[154:155], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[178:179], -v[170:171], v[176:177], v[178:179]\n" \
-        "v_fmac_f64_dpp v[126:127], v[154:155], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[178:179]\n" \
         "v_fmac_f64_dpp v[120:121], v[156:157], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
         "v_fmac_f64_dpp v[124:125], v[156:157], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[126:127], v[156:157], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
         "v_fmac_f64_dpp v[122:123], v[156:157], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[172:173], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[126:127], v[158:159], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], v[170:171], v[128:129], -v[130:131]\n" \
         "v_fmac_f64_dpp v[124:125], v[158:159], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[166:167], v[180:181], v[172:173]\n" \
         "v_mul_f64 v[180:181], v[128:129], v[168:169]\n" \
-        "v_fmac_f64_dpp v[126:127], v[160:161], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[164:165], -v[170:171], v[166:167], -v[180:181]\n" \
-        "v_fmac_f64_dpp v[126:127], v[162:163], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_write2_b64 %2, v[164:165], v[166:167] offset0:0 offset1:8\n" \
         "ds_write2_b64 %3, v[168:169], v[170:171] offset0:0 offset1:1\n" \
         "ds_write_b64 %3, v[172:173] offset:64\n" \
@@ -1703,13 +1944,11 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_fmac_f64_dpp v[120:121], v[128:129], v[164:165] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[122:123], v[128:129], v[164:165] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[124:125], v[128:129], v[164:165] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[126:127], v[128:129], v[164:165] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[116:117], v[130:131], v[166:167] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[118:119], v[130:131], v[166:167] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[120:121], v[130:131], v[166:167] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[122:123], v[130:131], v[166:167] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[124:125], v[130:131], v[166:167] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[126:127], v[130:131], v[166:167] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "s_sub_u32 %4, %4, 1\n" \
         "s_cmp_lg_u32 %4, 0\n" \
         "s_cbranch_scc1 1b\n" \
@@ -1722,38 +1961,32 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_mul_f64 v[136:137], v[120:121], " V##_D5 "\n" \
         "v_mul_f64 v[138:139], v[122:123], " V##_D5 "\n" \
         "v_mul_f64 v[140:141], v[124:125], " V##_D5 "\n" \
-        "v_mul_f64 v[142:143], v[126:127], " V##_D5 "\n" \
         "s_nop 1\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[144:145] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[116:117], v[144:145] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[116:117], v[144:145] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[116:117], v[144:145] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[116:117], v[144:145] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[116:117], v[144:145] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[146:147] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[146:147] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[118:119], v[146:147] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[118:119], v[146:147] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[118:119], v[146:147] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[118:119], v[146:147] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[148:149] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[148:149] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[120:121], v[148:149] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[120:121], v[148:149] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[120:121], v[148:149] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[120:121], v[148:149] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[120:121], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[122:123], v[150:151] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[122:123], v[150:151] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[122:123], v[150:151] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[132:133], v[116:117], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[134:135], v[118:119], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[136:137], v[120:121], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[138:139], v[122:123], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[140:141], v[124:125], v[152:153] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[142:143], v[124:125], v[152:153] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "s_waitcnt lgkmcnt(3)\n" \
         "s_nop 1\n" \
         "v_fmac_f64_dpp v[112:113], v[150:151], v[138:139] row_newbcast:6 row_mask:0xf bank_mask:0xf\n" \
@@ -1772,7 +2005,6 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_rcp_f64_e32 v[182:183], v[174:175]\n" \
         "v_fmac_f64_dpp v[108:109], v[152:153], v[140:141] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
-        "v_add_f64 v[110:111], v[110:111], v[142:143]\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
         "v_fmac_f64_dpp v[102:103], v[146:147], v[134:135] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[174:175], v[182:183], 1.0\n" \
@@ -1782,24 +2014,19 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_mul_f64 v[170:171], v[176:177], v[168:169]\n" \
         "v_fmac_f64_dpp v[108:109], v[144:145], v[132:133] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[178:179], -v[170:171], v[176:177], v[178:179]\n" \
-        "v_fmac_f64_dpp v[110:111], v[144:145], v[132:133] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_rcp_f64_e32 v[182:183], v[178:179]\n" \
         "v_fmac_f64_dpp v[104:105], v[146:147], v[134:135] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
         "v_fmac_f64_dpp v[108:109], v[146:147], v[134:135] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[182:183], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[146:147], v[134:135] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], -v[178:179], v[182:183], 1.0\n" \
         "v_fmac_f64_dpp v[106:107], v[146:147], v[134:135] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[172:173], v[180:181], v[182:183], v[182:183]\n" \
-        "v_fmac_f64_dpp v[110:111], v[148:149], v[136:137] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[180:181], v[170:171], v[112:113], -v[114:115]\n" \
         "v_fmac_f64_dpp v[108:109], v[148:149], v[136:137] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
         "v_mul_f64 v[166:167], v[180:181], v[172:173]\n" \
         "v_mul_f64 v[180:181], v[112:113], v[168:169]\n" \
-        "v_fmac_f64_dpp v[110:111], v[150:151], v[138:139] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fma_f64 v[164:165], -v[170:171], v[166:167], -v[180:181]\n" \
-        "v_fmac_f64_dpp v[110:111], v[152:153], v[140:141] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "ds_write2_b64 %2, v[164:165], v[166:167] " V##_K_U "\n" \
         "ds_write2_b64 %3, v[168:169], v[170:171] " V##_F_U "\n" \
         "ds_write_b64 %3, v[172:173] " V##_F_U8 "\n" \
@@ -1809,13 +2036,11 @@ __device__ __forceinline__ void rowpar_factor2(int lane, int M, const Blk2Lds L,
         "v_fmac_f64_dpp v[104:105], v[112:113], v[164:165] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[106:107], v[112:113], v[164:165] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[108:109], v[112:113], v[164:165] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[110:111], v[112:113], v[164:165] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[100:101], v[114:115], v[166:167] row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[102:103], v[114:115], v[166:167] row_newbcast:1 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[104:105], v[114:115], v[166:167] row_newbcast:2 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[106:107], v[114:115], v[166:167] row_newbcast:3 row_mask:0xf bank_mask:0xf\n" \
         "v_fmac_f64_dpp v[108:109], v[114:115], v[166:167] row_newbcast:4 row_mask:0xf bank_mask:0xf\n" \
-        "v_fmac_f64_dpp v[110:111], v[114:115], v[166:167] row_newbcast:5 row_mask:0xf bank_mask:0xf\n" \
         "3:\n" \
         "s_waitcnt lgkmcnt(0)\n"
 

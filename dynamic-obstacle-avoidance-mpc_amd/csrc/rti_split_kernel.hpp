@@ -821,7 +821,13 @@ sqp_again: ;
 #ifdef MPC_MFMA4
         if constexpr (!W2) mfma4_factor(lane, N, RL); else
 #endif
-        rowpar_factor(lane, N, RL, lane < 16, dt);
+        {
+            // rows 0..4 of the sweep only (rti_kernel.hpp) -- except where the register allocation answers the shorter sweep with MORE scratch: the 256-register
+            // kernels (W2: they spill as they are, and a changed live range moves their scratch by 8..24 bytes either way) and one 512-register
+            // instantiation, <10, 2> with REF and IPAR alone (160 -> 176 bytes); these keep the six-row form, instruction for instruction
+            constexpr bool kSixRows = W2 || (NOBST == 10 && LPS == 2 && !MASKED && REF && IPAR && !OSEL);
+            rowpar_factor<LT, (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), kSixRows>(lane, N, RL, lane < 16, dt);
+        }
         wave_sync();
         if (has_u) {
             const double *ko = RL.R + LT::HS * i;

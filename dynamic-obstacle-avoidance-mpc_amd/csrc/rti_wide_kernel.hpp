@@ -531,7 +531,10 @@ sqp_again: ;
                 }
             }
             wave_sync();
-            rowpar_factor<RowLds, kSweepTermsParent>(lane, N, RL, lane < 16, dt);      // (the sweep's term order of every earlier build: rti_kernel.hpp)
+            // (the sweep's term order of every earlier build: rti_kernel.hpp; rows 0..4 only, except in the one instantiation that answers the shorter sweep with
+            //  more scratch, 224 -> 240 bytes: <20, 2> with REF and IPAR alone keeps the six-row form -- DESIGN.md section 4)
+            constexpr bool kSixRows = CAP == 20 && LPS == 2 && !MASKED && REF && IPAR && !OSEL && !IBND && !NSQP;
+            rowpar_factor<RowLds, kSweepTermsParent, kSixRows>(lane, N, RL, lane < 16, dt);
             wave_sync();
             if (has_u) {
                 const double *ko = RL.R + RowLds::HS * i;

@@ -58,7 +58,9 @@ def dependency_floor(body, passes=8, lat_valu=8.4, lat_lds=64.0):
 
 def sweeps(kernel, text=False):
     """loop bodies of the factor sweep (two stages per pass: the innermost loop with ~100 DPP multiply-adds) and of the vector sweeps (four stages per pass, 20 of them)"""
-    a = next(i for (s, i), n in zip(syms, names) if kernel in n)
+    # the library's kernel name drops trailing `false` template arguments (solve_dispatch.hpp::format_kernel_name); the listing's symbol has them all
+    pat = re.compile(re.escape(kernel[:-1]) + r"(, false)*>")
+    a = next(i for (s, i), n in zip(syms, names) if pat.search(n))
     b = next(i for i in range(a, len(lst)) if lst[i].strip().startswith("s_endpgm"))
     labels = {m.group(1): i for i in range(a, b) for m in [re.match(r"^(\.LBB\w+):", lst[i])] if m}
     bodies = [code(labels[m.group(1)], i + 1) for i in range(a, b) for m in [re.match(r"\s+s_cbranch_\w+\s+(\.LBB\w+)", lst[i])]
