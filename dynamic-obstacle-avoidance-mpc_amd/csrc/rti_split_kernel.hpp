@@ -16,6 +16,8 @@
 // (v_mov_b32_dpp wave_shl:1, once for the neighbour's value and twice for the next lane's) twice per interior-point iteration;
 // the sums are formed in a fixed order, so the result is deterministic.  Everything a lane needs of the stage's Newton step it
 // reads from the stage's LDS block (same address in the LPS lanes: a broadcast).
+// On the dense blocks the predictor's staging is shared out as well (kStagingDealt, kAclDealt below): every part stores the H~aug words of the box variables it
+// holds, so only the five obstacle sums travel (to the part that holds x, y), and every part forms two columns of the closed-loop block [Acl c].
 #pragma once
 #include "rti_kernel.hpp"
 #include <type_traits>
@@ -45,6 +47,101 @@ __device__ __forceinline__ double nth_of_six(double a0, double a1, double a2, do
 {
     if constexpr (K == 0) return a0; else if constexpr (K == 1) return a1; else if constexpr (K == 2) return a2;
     else if constexpr (K == 3) return a3; else if constexpr (K == 4) return a4; else return a5;
+}
+
+// dyn_step (rti_kernel.hpp) with the sincos of its four quadrature nodes DEALT TO LANES: a sincos is about 155 VALU instructions that dyn_step walks four
+// times in a row, and in this kernel several lanes walk them on the same state.  Every lane still forms tau, w, vj, pj of all four nodes and accumulates the
+// sums in node order 0..3 by dyn_step's own expressions; only the lane that evaluates sincos(pj) changes, so every bit of the result is dyn_step's.
+//
+// Plant step (x, u the same in EVERY lane; called with all 64 lanes active): lane & 3 evaluates node lane & 3, the four (sin, cos) pairs reach the lanes of
+// the quad by quad_perm [k,k,k,k] broadcasts.  One sincos instead of four.
+__device__ __forceinline__ void dyn_step_quad(const double x[5], const double u[2], double dt, int lane, double xn[5])
+{
+    const double psi = x[2], v = x[3], om = x[4], a = u[0], al = u[1];
+    double vj[4], pj[4], w[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double tau = kGLC[j] * dt;
+        w[j] = kGLB[j] * dt;
+        vj[j] = v + a * tau;
+        pj[j] = psi + om * tau + 0.5 * al * tau * tau;
+    }
+    const int k = lane & 3;
+    double arg = pj[0];
+    arg = (k == 1) ? pj[1] : arg; arg = (k == 2) ? pj[2] : arg; arg = (k == 3) ? pj[3] : arg;
+    double sk, ck;
+    sincos(arg, &sk, &ck);
+    const double sn[4] = {dpp_f64<0x00>(sk), dpp_f64<0x55>(sk), dpp_f64<0xAA>(sk), dpp_f64<0xFF>(sk)};      // quad_perm [0,0,0,0] .. [3,3,3,3]
+    const double cn[4] = {dpp_f64<0x00>(ck), dpp_f64<0x55>(ck), dpp_f64<0xAA>(ck), dpp_f64<0xFF>(ck)};
+    double sx = 0, sy = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double wvc = w[j] * vj[j] * cn[j], wvs = w[j] * vj[j] * sn[j];
+        sx += wvc; sy += wvs;
+    }
+    xn[0] = x[0] + sx; xn[1] = x[1] + sy;
+    xn[2] = psi + om * dt + 0.5 * al * dt * dt;
+    xn[3] = v + a * dt;
+    xn[4] = om + al * dt;
+}
+// Linearisation (x, u the same in the LPS lanes of a stage, lane = LPS * stage + part; called by whole stages): two sincos instead of four.  LPS = 3: part h
+// evaluates node h, and every part node 3; LPS = 2: part h evaluates nodes h and 2 + h.  The siblings' pairs travel by one-lane wave shifts (from_right /
+// from_left, rti_kernel.hpp) and are picked by the part flags, which the caller keeps opaque to the optimiser.
+template <int LPS>
+__device__ __forceinline__ void dyn_step_parts(const double x[5], const double u[2], double dt, int is_part1, int is_part2, double xn[5], double ae[6], double be[4])
+{
+    const double psi = x[2], v = x[3], om = x[4], a = u[0], al = u[1];
+    double pj[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double tau = kGLC[j] * dt;
+        pj[j] = psi + om * tau + 0.5 * al * tau * tau;
+    }
+    double sn[4], cn[4];
+    if constexpr (LPS == 3) {
+        double arg = pj[0];
+        arg = is_part1 ? pj[1] : arg; arg = is_part2 ? pj[2] : arg;
+        double sh, ch;
+        sincos(arg, &sh, &ch);
+        sincos(pj[3], &sn[3], &cn[3]);
+        const double sr = from_right(sh), cr = from_right(ch), sl = from_left(sh), cl = from_left(ch);
+        const double srr = from_right(sr), crr = from_right(cr), sll = from_left(sl), cll = from_left(cl);
+        sn[0] = is_part2 ? sll : (is_part1 ? sl : sh); cn[0] = is_part2 ? cll : (is_part1 ? cl : ch);
+        sn[1] = is_part2 ? sl : (is_part1 ? sh : sr);  cn[1] = is_part2 ? cl : (is_part1 ? ch : cr);
+        sn[2] = is_part2 ? sh : (is_part1 ? sr : srr); cn[2] = is_part2 ? ch : (is_part1 ? cr : crr);
+    } else {
+        double sa, ca, sb, cb;
+        sincos(is_part1 ? pj[1] : pj[0], &sa, &ca);
+        sincos(is_part1 ? pj[3] : pj[2], &sb, &cb);
+        // (the shifts stand outside the selects: inside an arm they would run with the sibling's lane disabled and read 0)
+        const double sal = from_left(sa), cal = from_left(ca), sar = from_right(sa), car = from_right(ca);
+        const double sbl = from_left(sb), cbl = from_left(cb), sbr = from_right(sb), cbr = from_right(cb);
+        sn[0] = is_part1 ? sal : sa; cn[0] = is_part1 ? cal : ca;
+        sn[1] = is_part1 ? sa : sar; cn[1] = is_part1 ? ca : car;
+        sn[2] = is_part1 ? sbl : sb; cn[2] = is_part1 ? cbl : cb;
+        sn[3] = is_part1 ? sb : sbr; cn[3] = is_part1 ? cb : cbr;
+    }
+    double sx = 0, sy = 0, xpsi = 0, xv = 0, xom = 0, xa = 0, xal = 0, ypsi = 0, yv = 0, yom = 0, ya = 0, yal = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double tau = kGLC[j] * dt, w = kGLB[j] * dt;
+        const double vj = v + a * tau;
+        const double sj = sn[j], cj = cn[j];
+        const double wvc = w * vj * cj, wvs = w * vj * sj;
+        sx += wvc; sy += wvs;
+        const double ht2 = 0.5 * tau * tau;
+        xpsi -= wvs;        ypsi += wvc;
+        xv += w * cj;       yv += w * sj;
+        xom -= wvs * tau;   yom += wvc * tau;
+        xa += w * tau * cj; ya += w * tau * sj;
+        xal -= wvs * ht2;   yal += wvc * ht2;
+    }
+    xn[0] = x[0] + sx; xn[1] = x[1] + sy;
+    xn[2] = psi + om * dt + 0.5 * al * dt * dt;
+    xn[3] = v + a * dt;
+    xn[4] = om + al * dt;
+    ae[0] = xpsi; ae[1] = xv; ae[2] = xom; ae[3] = ypsi; ae[4] = yv; ae[5] = yom;
+    be[0] = xa; be[1] = xal; be[2] = ya; be[3] = yal;
 }
 
 // Diagnostic build only (-DMPC_FORCE_WAVES2, scripts/waves2_experiment.py): the register allocator is told to fit TWO wavefronts per SIMD
@@ -178,6 +275,24 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     //   BLK2, an evidence path.
     // These keep the order they had (same arithmetic either way: the outputs are bit for bit the same, tests/test_gpu_parity.py, test_gpu_split_fixed_cost.py).
     constexpr bool FX = !W2 && !BLK2 && !(LPS == 2 && NOBST > 5);
+    // the quadrature nodes of the linearisation dealt to the parts of a stage (dyn_step_parts above; DESIGN.md section 4 names the instantiations that keep
+    // dyn_step's four calls: the dealt text costs them scratch).  This and the three flags below are off for the SQP loop's instantiations (NSQP), which sit at
+    // 256 + 256 registers with scratch and answered each of these texts with 16 to 128 bytes more: their listings are the parent's
+    constexpr bool kNodesDealt = !W2 && !NSQP && !(NOBST == 10 && LPS == 2 && !MASKED && REF && IPAR && !OSEL);
+    // the factor sweep in its six-row form (rowpar_factor_six_rows, rti_kernel.hpp): the instantiations that answer the five-row form with more scratch
+    constexpr bool kSixRows = W2 || (NOBST == 10 && LPS == 2 && !MASKED && REF && IPAR && !OSEL);
+    // per-iteration staging of H~aug_t and the affine column of W~_t by the parts of a stage (dense blocks with a result region of their own, whose H~aug words
+    // nothing overwrites); row 5 of H~aug_t is staged where a sweep fetches it: the six-row form and the matrix-core variant
+#ifdef MPC_MFMA4
+    constexpr bool kRow5Staged = true;
+#else
+    constexpr bool kRow5Staged = kSixRows;
+#endif
+    constexpr bool kStagingDealt = !W2 && !BLK2 && !NSQP;
+    // Acl = A + B K and c of the affine sweep formed and stored by the parts, two columns each (LPS = 3, dense blocks)
+    constexpr bool kAclDealt = LPS == 3 && !W2 && !BLK2 && !NSQP;
+    // the plant step of the fused epilogue with one quadrature node's sincos per lane of a quad (dyn_step_quad above)
+    constexpr bool kPlantDealt = FX && !NSQP;
     const bool obst_step = p.obst && (p.fused & (kFusePlant | kFuseObstacles | kFuseMetrics)) && lane < nact;
     double og[4] = {0, 0, 0, 0}, onz[2] = {0, 0};
     if constexpr (FX) {
@@ -286,7 +401,8 @@ sqp_again: ;
     double bb[5] = {0, 0, 0, 0, 0};
     if (has_u) {
         double xn[5], ae[6], be[4];
-        dyn_step<true>(xi, ui, dt, xn, ae, be);
+        if constexpr (kNodesDealt) dyn_step_parts<LPS>(xi, ui, dt, is_part1, is_part2, xn, ae, be);
+        else dyn_step<true>(xi, ui, dt, xn, ae, be);
         S.a02 = ae[0]; S.a03 = ae[1]; S.a04 = ae[2]; S.a12 = ae[3]; S.a13 = ae[4]; S.a14 = ae[5];
         S.b00 = be[0]; S.b01 = be[1]; S.b10 = be[2]; S.b11 = be[3];
 #pragma unroll
@@ -438,6 +554,9 @@ sqp_again: ;
     if constexpr (IPAR) hd_psi_ = has_u ? ipw[kIpHs + 4] : ipw[kIpHt + 2];
     else hd_psi_ = has_u ? p.Hd_stage[4] : p.Hd_term[2];
     const double hd_psi = hd_psi_;
+    if constexpr (kStagingDealt) {      // the constant psi diagonal of H~aug_t, once per solve, behind the zeros the owner wrote above
+        if (own && act) RL.H[LT::HS * i + 18] = hd_psi;
+    }
     // ---- this lane's obstacle rows (slot s <-> obstacle j = s * LPS + part): rho1 = h + a'dx + s >= 0 (lam1, t1), rho2 = s >= 0
     //      (lam2, t2); robot_model.py:60-65 ----
     bool sp[NSL];
@@ -590,6 +709,53 @@ sqp_again: ;
         double bbr[5], x_init[5];
 #pragma unroll
         for (int c = 0; c < 5; c++) { bbr[c] = rhoPi * bb[c]; x_init[c] = rhoPi * d0[c]; }
+        if constexpr (kStagingDealt) {
+            // H~aug_t (dense 8 x 8, z~ order x0..x4, 1, ua, ual) staged by the parts: each stores the diagonal and gradient words of the box variables it holds, so
+            // only the five sums travel -- to the part that holds x (and y), added there in the order part 0 + part 1 (+ part 2) the owner used.  The structural
+            // zeros and the constant psi diagonal were written once per solve; row 5 is staged only for a sweep that fetches it (kRow5Staged)
+            double *hc = RL.H + LT::HS * i;
+            const double gpsi = hd_psi * z[4];
+            if constexpr (LPS == 3) {       // part 0: ua, ual (and the affine column of W~_t); part 1: x, y; part 2: v, om (and psi's gradient)
+                double Sm[5];
+#pragma unroll
+                for (int e = 0; e < 5; e++) { const double l = from_left(ssum[e]), r = from_right(ssum[e]); Sm[e] = (l + ssum[e]) + r; }
+                if (act) {
+                    if (h == 1) {
+                        const double gx = g_[0] + Sm[3], gy = g_[1] + Sm[4];
+                        hc[0] = hdiag_[0] + Sm[0]; hc[1] = Sm[2]; hc[8] = Sm[2]; hc[9] = hdiag_[1] + Sm[1]; hc[5] = gx; hc[13] = gy;
+                        if constexpr (kRow5Staged) { hc[40] = gx; hc[41] = gy; }
+                    } else if (h == 2) {
+                        hc[27] = hdiag_[0]; hc[36] = hdiag_[1]; hc[21] = gpsi; hc[29] = g_[0]; hc[37] = g_[1];
+                        if constexpr (kRow5Staged) { hc[42] = gpsi; hc[43] = g_[0]; hc[44] = g_[1]; }
+                    } else {
+                        hc[54] = hdiag_[0]; hc[63] = hdiag_[1]; hc[53] = g_[0]; hc[61] = g_[1];
+                        if constexpr (kRow5Staged) { hc[46] = g_[0]; hc[47] = g_[1]; }
+                        if (has_u) {
+#pragma unroll
+                            for (int k = 0; k < 5; k++) RL.W[LT::WS * i + k * 8 + 5] = bbr[k];
+                        }
+                    }
+                }
+            } else {                        // part 0: ua, ual, x; part 1: y, v, om (psi's gradient and the affine column of W~_t)
+                const double Sxx = ssum[0] + from_right(ssum[0]), Sxy = ssum[2] + from_right(ssum[2]), Sgx = ssum[3] + from_right(ssum[3]);
+                const double Syy = from_left(ssum[1]) + ssum[1], Sgy = from_left(ssum[4]) + ssum[4];
+                if (act) {
+                    if (h == 1) {
+                        const double gy = g_[0] + Sgy;
+                        hc[9] = hdiag_[0] + Syy; hc[27] = hdiag_[1]; hc[36] = hdiag_[2]; hc[13] = gy; hc[21] = gpsi; hc[29] = g_[1]; hc[37] = g_[2];
+                        if constexpr (kRow5Staged) { hc[41] = gy; hc[42] = gpsi; hc[43] = g_[1]; hc[44] = g_[2]; }
+                        if (has_u) {
+#pragma unroll
+                            for (int k = 0; k < 5; k++) RL.W[LT::WS * i + k * 8 + 5] = bbr[k];
+                        }
+                    } else {
+                        const double gx = g_[2] + Sgx;
+                        hc[54] = hdiag_[0]; hc[63] = hdiag_[1]; hc[0] = hdiag_[2] + Sxx; hc[1] = Sxy; hc[8] = Sxy; hc[53] = g_[0]; hc[61] = g_[1]; hc[5] = gx;
+                        if constexpr (kRow5Staged) { hc[46] = g_[0]; hc[47] = g_[1]; hc[40] = gx; }
+                    }
+                }
+            }
+        } else
         {   // the stage's values and sums in the owner lane, in a fixed order.  All first shifts, then all second shifts: a DPP read needs
             // two wait states after the VALU write of its source, which the other values' moves fill
             double Hk[6], gk[6], Ssum[5], sh_h[NBL], sh_g[NBL], sh_s[5];
@@ -824,8 +990,8 @@ sqp_again: ;
         {
             // rows 0..4 of the sweep only (rti_kernel.hpp) -- except where the register allocation answers the shorter sweep with MORE scratch: the 256-register
             // kernels (W2: they spill as they are, and a changed live range moves their scratch by 8..24 bytes either way) and one 512-register
-            // instantiation, <10, 2> with REF and IPAR alone (160 -> 176 bytes); these keep the six-row form, instruction for instruction
-            constexpr bool kSixRows = W2 || (NOBST == 10 && LPS == 2 && !MASKED && REF && IPAR && !OSEL);
+            // instantiation, <10, 2> with REF and IPAR alone (160 -> 176 bytes); these keep the six-row form, instruction for instruction:
+            // kSixRows, defined at the top of the kernel
             rowpar_factor<LT, (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), kSixRows>(lane, N, RL, lane < 16, dt);
         }
         wave_sync();
@@ -837,6 +1003,25 @@ sqp_again: ;
         }
         // the parts of a stage must all have read the factors before the owner overwrites the block: LDS operations of one
         // wavefront complete in order, so no barrier is needed
+        if constexpr (kAclDealt) {
+            // Acl = A + B K and c_t = r_b + B k by the parts: part h forms and stores columns h and h + 3 of the 5 x 6 block [Acl c] (column 5 = c, whose "A" entries
+            // are r_b and whose gain entries are k), element for element by the owner's expressions below.  The gain words of a lane's columns come from the
+            // stage's block by a per-lane address (K~ rows at [j], [8 + j]: k0, k1 are their column 5); requested before any lane of the stage overwrites them
+            if (has_u) {
+                const double *ko = RL.R + LT::HS * i + h;
+                const double Ka0 = ko[0], Kb0 = ko[3], Ka1 = ko[8], Kb1 = ko[11];
+                // column h of A (h = 0, 1, 2) and column h + 3 of [A r_b] (3, 4, or r_b), rows 0..4
+                const double Aa[5] = {is_part2 ? S.a02 : (is_part1 ? 0.0 : 1.0), is_part2 ? S.a12 : (is_part1 ? 1.0 : 0.0), is_part2 ? 1.0 : 0.0, 0.0, 0.0};
+                const double Ab[5] = {is_part2 ? bbr[0] : (is_part1 ? S.a04 : S.a03), is_part2 ? bbr[1] : (is_part1 ? S.a14 : S.a13),
+                                      is_part2 ? bbr[2] : (is_part1 ? dt : 0.0), is_part2 ? bbr[3] : (is_part1 ? 0.0 : 1.0), is_part2 ? bbr[4] : (is_part1 ? 1.0 : 0.0)};
+                double *acl = RL.R + LT::HS * i + RowVec::ACL + h;
+                acl[0 * RowVec::RS] = Aa[0] + S.b00 * Ka0 + S.b01 * Ka1; acl[0 * RowVec::RS + 3] = Ab[0] + S.b00 * Kb0 + S.b01 * Kb1;
+                acl[1 * RowVec::RS] = Aa[1] + S.b10 * Ka0 + S.b11 * Ka1; acl[1 * RowVec::RS + 3] = Ab[1] + S.b10 * Kb0 + S.b11 * Kb1;
+                acl[2 * RowVec::RS] = Aa[2] + h2 * Ka1;                  acl[2 * RowVec::RS + 3] = Ab[2] + h2 * Kb1;
+                acl[3 * RowVec::RS] = Aa[3] + dt * Ka0;                  acl[3 * RowVec::RS + 3] = Ab[3] + dt * Kb0;
+                acl[4 * RowVec::RS] = Aa[4] + dt * Ka1;                  acl[4 * RowVec::RS + 3] = Ab[4] + dt * Kb1;
+            }
+        } else
         if (own && has_u) {     // closed-loop matrix Acl = A + B K, row-major, and c_t = r_b + B k, for the row-parallel vector recursions
             double *acl = RL.R + LT::HS * i + RowVec::ACL;
             const double Ar[2][5] = {{1.0, 0.0, S.a02, S.a03, S.a04}, {0.0, 1.0, S.a12, S.a13, S.a14}};
@@ -1213,7 +1398,10 @@ sqp_again: ;
             if ((p.fused & kFuseAliasBug) && (p.fused & kFuseResetOnFail) && status == 4) { xp[3] = 0.0; xp[4] = 0.0; }
 #pragma unroll
             for (int c = 0; c < 5; c++) xnew[c] = xp[c];
-            if (p.fused & kFusePlant) dyn_step<false>(xp, u_apply, dt, xnew, nullptr, nullptr);     // every lane, same value
+            if (p.fused & kFusePlant) {     // every lane, same value (kPlantDealt: one quadrature node's sincos per lane of a quad)
+                if constexpr (kPlantDealt) dyn_step_quad(xp, u_apply, dt, lane, xnew);
+                else dyn_step<false>(xp, u_apply, dt, xnew, nullptr, nullptr);
+            }
             double margin = INFINITY;
             if (obst_step) {                                     // obstacle j = lane, where the prologue moved it
                 const double ddx = xnew[0] - ox, ddy = xnew[1] - oy;
