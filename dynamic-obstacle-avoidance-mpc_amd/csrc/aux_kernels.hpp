@@ -362,6 +362,119 @@ __global__ void reset_guess_kernel(int batch, int N, const double *__restrict__ 
     if (i < N) { double *Ui = U + ((size_t)inst * N + i) * 2; Ui[0] = 0.0; Ui[1] = 0.0; }
 }
 
+// MULTI-START (mpc_seed_guesses_dev, mpc_select_best_dev): a batch of `groups` scenarios with K candidate iterates each -- member k of group g is instance
+// g K + k, and every member of a group is given the same x0, obstacles and goal.  The solve between the two launches is the ordinary one on groups * K
+// instances; these two kernels stand beside it.  (No reference counterpart: robot_ocp_problem.py:286-306 starts every solve from one guess.)
+//
+// seed_guesses_kernel: the iterate of member k is the straight line from x0 to the goal bent sideways by a half sine of amplitude a = offsets[k] metres --
+// with d = goal - x0[0:2], L = |d|, t = d / L, n = (-t_y, t_x), s_i = i / N:
+//   position  X[i][0:2] = x0[0:2] + s_i d + a sin(pi s_i) n,
+//   heading   X[i][2]   = psi0 + wrap(atan2(tau_y, tau_x) - psi0) along the path tangent tau = d + a pi cos(pi s_i) n, wrap(e) = e - 2 pi rint(e / 2 pi)
+//             (the heading nearest to psi0 modulo a turn: an unwrapped jump of 2 pi would be a spin in the model),
+//   X[i][3:5] = 0 for i >= 1, X[0] = x0 (all five), U = 0.
+// L < 1e-9: the plain guess of reset_guess_kernel (a robot on its goal has no direction to bend).  keep_first: member 0 of every group is left alone (the
+// closed loop's shifted warm start).  Non-finite inputs propagate into the iterate; the solve then reports status 4 as for any such warm start.
+// One wavefront per instance, a stage per lane (N + 1 <= 63), four instances per workgroup; every word written belongs to the wavefront's own instance.
+constexpr int kGroupThreads = 256, kGroupWaves = kGroupThreads / 64;
+constexpr double kPi = 3.14159265358979323846;
+
+__global__ __launch_bounds__(kGroupThreads) void seed_guesses_kernel(int groups, int K, int N, int keep_first, const double *__restrict__ x0,
+                                                                     const double *__restrict__ goal, const double *__restrict__ offsets,
+                                                                     double *__restrict__ X, double *__restrict__ U)
+{
+    const int i = threadIdx.x & 63;
+    const int inst = blockIdx.x * kGroupWaves + (threadIdx.x >> 6);
+    if (inst >= groups * K) return;
+    const int g = inst / K, k = inst - g * K;
+    if ((keep_first && k == 0) || i > N) return;
+    const double *x = x0 + (size_t)g * 5;
+    const double px = x[0], py = x[1], psi = x[2];
+    const double dx = goal[(size_t)g * 2] - px, dy = goal[(size_t)g * 2 + 1] - py;
+    const double L = sqrt(dx * dx + dy * dy);
+    double xi[5] = {px, py, psi, 0.0, 0.0};
+    if (!(L < 1e-9)) {                                          // (a NaN length takes this branch and propagates)
+        if (i == 0) {
+            xi[3] = x[3]; xi[4] = x[4];
+        } else {
+            const double a = offsets[k], nx = -dy / L, ny = dx / L, s = (double)i / (double)N;
+            const double sn = sin(kPi * s), cs = cos(kPi * s);
+            xi[0] = px + s * dx + a * sn * nx;
+            xi[1] = py + s * dy + a * sn * ny;
+            const double e = atan2(dy + a * kPi * cs * ny, dx + a * kPi * cs * nx) - psi;
+            xi[2] = psi + (e - 2.0 * kPi * rint(e / (2.0 * kPi)));
+        }
+    }
+    double *Xi = X + ((size_t)inst * (N + 1) + i) * 5;
+#pragma unroll
+    for (int c = 0; c < 5; c++) Xi[c] = xi[c];
+    if (i < N) { double *Ui = U + ((size_t)inst * N + i) * 2; Ui[0] = 0.0; Ui[1] = 0.0; }
+}
+
+// select_best_kernel: per group, the eligible member (status 0 or 2, finite cost) of least cost, ties to the lowest member index; with margin m > 0 an
+// eligible member 0 stays the winner unless the challenger costs less than (1 - m) cost[0] (hysteresis: the closed loop keeps member 0 = the shifted
+// winner of the last step).  No eligible member: winner -1, best_cost +inf, best_u0 (0, 0), nothing copied.
+// One wavefront per group, four groups per workgroup.  Lane k < K holds (cost, k); lanes without an eligible member hold (+inf, 64 + lane), which sorts
+// behind every eligible pair.  The argmin is a butterfly of six cross-lane exchanges (distances 32 .. 1) with a lexicographic compare -- min is associative and
+// commutative on a total order, so every lane ends with the same pair whatever the order: no atomics, no dependence on which workgroup runs when.
+// kSelectBroadcast: the winner's row of X (5 (N + 1) doubles) and of U (2 N) is read ONCE into registers, the lanes striding over it (consecutive lanes,
+// consecutive doubles: 512 contiguous bytes per load), and stored to the K - 1 other rows of the group the same way -- never onto itself, so no word is
+// both read and written in one launch.  Row lengths need not be multiples of 64: the last round is partly masked.
+constexpr int kSelectBroadcast = 1;                             // MPC_SELECT_BROADCAST
+constexpr int kSelectXRounds = 5, kSelectURounds = 2;           // 64 x 5 >= 5 (N + 1), 64 x 2 >= 2 N for N <= 62
+
+__global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, int K, int N, double margin, int flags, const double *__restrict__ cost,
+                                                                    const int32_t *__restrict__ status, double *X, double *U,
+                                                                    int32_t *__restrict__ winner, double *__restrict__ best_cost,
+                                                                    double *__restrict__ best_u0, const double *__restrict__ u0)
+{
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kGroupWaves + (threadIdx.x >> 6);
+    if (g >= groups) return;
+    const size_t base = (size_t)g * K;
+    double c = INFINITY;
+    int idx = 64 + lane;
+    if (lane < K) {
+        const double cc = cost[base + lane];
+        const int st = status[base + lane];
+        if ((st == 0 || st == 2) && isfinite(cc)) { c = cc; idx = lane; }
+    }
+    const double c0 = __shfl(c, 0);
+    const bool keep0 = __shfl(idx, 0) == 0;                     // member 0 is eligible
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double oc = __shfl_xor(c, m);
+        const int oi = __shfl_xor(idx, m);
+        if (oc < c || (oc == c && oi < idx)) { c = oc; idx = oi; }
+    }
+    if (margin > 0.0 && keep0 && idx != 0 && !(c < (1.0 - margin) * c0)) { c = c0; idx = 0; }
+    const int w = idx < 64 ? idx : -1;
+    if (lane == 0) {
+        winner[g] = w;
+        if (best_cost) best_cost[g] = w >= 0 ? c : INFINITY;
+    }
+    if (best_u0 && lane < 2) {                                  // the solve's own u* words where given, else U[0] of the winner's row (the same value)
+        double v = 0.0;
+        if (w >= 0) v = u0 ? u0[(base + w) * 2 + lane] : U[(base + w) * (size_t)(2 * N) + lane];
+        best_u0[(size_t)g * 2 + lane] = v;
+    }
+    if (!(flags & kSelectBroadcast) || w < 0 || K < 2) return;
+    const int LX = 5 * (N + 1), LU = 2 * N;
+    double xr[kSelectXRounds], ur[kSelectURounds];
+    const double *xs = X + (base + w) * (size_t)LX, *us = U + (base + w) * (size_t)LU;
+#pragma unroll
+    for (int r = 0; r < kSelectXRounds; r++) { const int j = lane + 64 * r; xr[r] = j < LX ? xs[j] : 0.0; }
+#pragma unroll
+    for (int r = 0; r < kSelectURounds; r++) { const int j = lane + 64 * r; ur[r] = j < LU ? us[j] : 0.0; }
+    for (int k = 0; k < K; k++) {
+        if (k == w) continue;
+        double *xd = X + (base + k) * (size_t)LX, *ud = U + (base + k) * (size_t)LU;
+#pragma unroll
+        for (int r = 0; r < kSelectXRounds; r++) { const int j = lane + 64 * r; if (j < LX) xd[j] = xr[r]; }
+#pragma unroll
+        for (int r = 0; r < kSelectURounds; r++) { const int j = lane + 64 * r; if (j < LU) ud[j] = ur[r]; }
+    }
+}
+
 // EPISODE REFILL (mpc_episode_refill_dev): a sweep over more seeds than there are slots streams the seeds through the slots -- in front of every
 // fused control step, a slot whose episode has ended (ep_flags bit 0: goal reached, robot_ocp_problem.py:247-250; or ep_steps >= max_steps: the budget of
 // experiments.py:20-36) parks its result row under its seed index and starts the next seed that has not been started yet.  Two launches:

@@ -771,6 +771,47 @@ int mpc_reset_guess_interp_dev(mpc_handle *h, int batch, const double *d_x0, con
     return reset_guess_launch(h, batch, d_x0, d_goal, d_X, d_U, stream);
 }
 
+// the group layout of the two multi-start entry points: `groups` scenarios of K members, member k of group g = instance g K + k
+static_assert(mpc::kSelectBroadcast == MPC_SELECT_BROADCAST, "the kernel's flag is the header's");
+static int check_groups(mpc_handle *h, int groups, int K)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (K < 1 || K > 64) return fail(MPC_ERR_ARG, "K must be in [1, 64] (one member per lane of the group's wavefront)");
+    if (groups < 0 || (long long)groups * K > h->max_batch) return fail(MPC_ERR_ARG, "groups * K outside [0, max_batch]");
+    return MPC_OK;
+}
+
+int mpc_seed_guesses_dev(mpc_handle *h, int groups, int K, const double *d_x0, const double *d_goal, const double *d_offsets, int keep_first,
+                         double *d_X, double *d_U, void *stream)
+{
+    int rc = check_groups(h, groups, K); if (rc) return rc;
+    if (groups == 0) return MPC_OK;
+    if (!d_x0 || !d_goal || !d_offsets || !d_X || !d_U) return fail(MPC_ERR_ARG, "null device pointer");
+    HIPCHK(hipSetDevice(h->device));
+    const int count = groups * K;
+    hipLaunchKernelGGL(mpc::seed_guesses_kernel, dim3((count + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, pick(h, stream),
+                       groups, K, h->cfg.N, keep_first ? 1 : 0, d_x0, d_goal, d_offsets, d_X, d_U);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, const int32_t *d_status, double incumbent_margin, int flags,
+                        double *d_X, double *d_U, int32_t *d_winner, double *d_best_cost, double *d_best_u0, const double *d_u0, void *stream)
+{
+    int rc = check_groups(h, groups, K); if (rc) return rc;
+    if (!(incumbent_margin >= 0.0) || !(incumbent_margin < 1.0)) return fail(MPC_ERR_ARG, "incumbent_margin must be in [0, 1)");
+    if (flags & ~MPC_SELECT_BROADCAST) return fail(MPC_ERR_ARG, "unknown flags (MPC_SELECT_BROADCAST is the only one)");
+    if (groups == 0) return MPC_OK;
+    if (!d_cost || !d_status || !d_winner) return fail(MPC_ERR_ARG, "null device pointer (d_cost, d_status and d_winner are mandatory)");
+    if ((flags & MPC_SELECT_BROADCAST) && (!d_X || !d_U)) return fail(MPC_ERR_ARG, "MPC_SELECT_BROADCAST needs d_X and d_U");
+    if (d_best_u0 && !d_u0 && !d_U) return fail(MPC_ERR_ARG, "d_best_u0 needs d_u0 or d_U");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(mpc::select_best_kernel, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, pick(h, stream),
+                       groups, K, h->cfg.N, incumbent_margin, flags, d_cost, d_status, d_X, d_U, d_winner, d_best_cost, d_best_u0, d_u0);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 int mpc_plant_step_dev(mpc_handle *h, int batch, const double *d_x, const double *d_u, double *d_xnext, void *stream)
 {
     int rc = check_batch(h, batch); if (rc) return rc;

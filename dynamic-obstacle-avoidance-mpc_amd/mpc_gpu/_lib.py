@@ -22,6 +22,7 @@ STEP_ADVANCE_REF = 128
 STEP_MARGIN_ALL = 256
 REFILL_ALIAS_BUG, REFILL_INTERP_GUESS, REFILL_DRAW_NOISE = 1, 2, 4      # MPC_REFILL_* (mpc_episode_refill_dev)
 TRACE_START, TRACE_STEP = 0, 1      # MPC_TRACE_* (mpc_episode_trace_dev)
+SELECT_BROADCAST = 1                # MPC_SELECT_BROADCAST (mpc_select_best_dev)
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
 MAX_SQP_ITER = 100       # MPC_MAX_SQP_ITER
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
@@ -99,6 +100,8 @@ SYMBOLS = {
     "mpc_shift_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "mpc_reset_guess_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_reset_guess_interp_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mpc_seed_guesses_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "mpc_select_best_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _d, C.c_int] + [_vp] * 7),
     "mpc_plant_step_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_obstacle_step_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _d, _d, _vp]),
     "mpc_linearize_dev": (C.c_int, [_vp, C.c_int] + [_vp] * 12),

@@ -284,6 +284,39 @@ int mpc_closed_loop_step_dev(mpc_handle *h, int batch, double *d_x0, double *d_o
 int mpc_shift_dev(mpc_handle *h, int batch, double *d_X, double *d_U, void *stream);
 int mpc_reset_guess_dev(mpc_handle *h, int batch, const double *d_x0, double *d_X, double *d_U, void *stream);
 int mpc_reset_guess_interp_dev(mpc_handle *h, int batch, const double *d_x0, const double *d_goal, double *d_X, double *d_U, void *stream);
+/* MULTI-START: K initial guesses per scenario, the best kept on the device.  The problem is non-convex -- an obstacle on the line from robot to goal
+ * splits the solutions into "pass left" and "pass right", and an RTI / SQP iteration stays in the family its guess sits in (the reference starts every
+ * solve from ONE guess, robot_ocp_problem.py:286-306, and shifts it, :253-258) -- so a caller spends some of the batch on several guesses per scenario.
+ * Layout: `groups` scenarios of K members; member k of group g is instance g K + k of the ordinary arrays, and every member of a group is given the
+ * same x0, obstacles and goal.  The solve between the two calls is the ordinary launch (mpc_solve_dev, mpc_closed_loop_step_dev) on groups * K
+ * instances: neither call changes what a solve launches.  Both: MPC_ERR_ARG (with a message, nothing launched) for a null handle or a null mandatory
+ * pointer, K outside 1 .. 64, groups < 0 or groups * K > max_batch; groups = 0 does nothing.
+ *
+ * mpc_seed_guesses_dev writes the iterate of member k of every group from the group's x0 (d_x0[groups][5]) and goal (d_goal[groups][2]) and the
+ * lateral offset a = d_offsets[k] in metres (d_offsets[K]).  With d = goal - x0[0:2], L = |d|, t = d / L, n = (-t_y, t_x), s_i = i / N, for i = 0 .. N:
+ *   X[i][0:2] = x0[0:2] + s_i d + a sin(pi s_i) n                                  (the straight line bent sideways by a half sine)
+ *   X[i][2]   = x0_psi + wrap(atan2(tau_y, tau_x) - x0_psi),  tau = d + a pi cos(pi s_i) n the path tangent, wrap(e) = e - 2 pi rint(e / 2 pi)
+ *   X[i][3:5] = 0 for i >= 1;  X[0] = x0 (all five entries);  U = 0.
+ * L < 1e-9: the member gets the plain guess of mpc_reset_guess_dev.  keep_first != 0: member 0 of every group is not touched (the closed loop's
+ * shifted warm start).  Non-finite inputs propagate into the iterate; the solve then reports status 4, as for any non-finite warm start.
+ *
+ * mpc_select_best_dev reads d_cost[groups * K] and d_status[groups * K] of a solve and decides per group:
+ *   - member k is ELIGIBLE when its status is 0 or 2 and its cost is finite;
+ *   - the winner is the eligible member of least cost, ties to the lowest k (a cross-lane butterfly with a lexicographic compare: no atomics, no
+ *     dependence on the order workgroups run in, the same answer every time);
+ *   - with incumbent_margin = m > 0 (0 <= m < 1; outside: MPC_ERR_ARG) an eligible member 0 stays the winner unless the challenger's cost is
+ *     < (1 - m) cost[0] -- hysteresis against changing sides every control step;
+ *   - no eligible member: winner = -1, best_cost = +inf, best_u0 = (0, 0), nothing is copied.
+ * Outputs: d_winner[groups] (int32, mandatory), d_best_cost[groups], d_best_u0[groups][2] (each may be NULL).  best_u0 is row winner of d_u0
+ * [groups * K][2], the u* array of the solve, bit for bit; with d_u0 NULL it is U[0] of the winner's row of d_U.
+ * flags: MPC_SELECT_BROADCAST copies the winner's rows of d_X and d_U into every other member of its group (read once, written K - 1 times, never
+ * onto itself), so that a following mpc_shift_dev leaves every member on the winner's shifted iterate; without it d_X / d_U may be NULL (unless
+ * best_u0 is to come from d_U) and are not written.  Unknown flags: MPC_ERR_ARG. */
+#define MPC_SELECT_BROADCAST 1
+int mpc_seed_guesses_dev(mpc_handle *h, int groups, int K, const double *d_x0, const double *d_goal, const double *d_offsets, int keep_first,
+                         double *d_X, double *d_U, void *stream);
+int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, const int32_t *d_status, double incumbent_margin, int flags,
+                        double *d_X, double *d_U, int32_t *d_winner, double *d_best_cost, double *d_best_u0, const double *d_u0, void *stream);
 int mpc_plant_step_dev(mpc_handle *h, int batch, const double *d_x, const double *d_u, double *d_xnext, void *stream);
 /* Obstacle.step() ground-truth motion (visualization.py:20-33); d_noise[B*n_obst][2] standard normals or NULL */
 int mpc_obstacle_step_dev(mpc_handle *h, int count, double *d_obst, const double *d_noise,
