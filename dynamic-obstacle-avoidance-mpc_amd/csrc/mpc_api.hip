@@ -1596,6 +1596,7 @@ int mpc_set_accumulators(mpc_handle *h, int32_t *d_iters_acc, int32_t *d_status_
 int mpc_debug_trace(mpc_handle *h, int enable, int batch, double *host_out)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (host_out && (batch < 1 || batch > h->max_batch)) return fail(MPC_ERR_ARG, "mpc_debug_trace: batch outside [1, max_batch]");
     HIPCHK(hipSetDevice(h->device));
     const size_t count = (size_t)h->max_batch * h->cfg.qp_iter_max * 4;
     if (enable && !h->d_trace) { int rc = own(h, &h->d_trace, count); if (rc) return rc; HIPCHK(hipMemset(h->d_trace, 0, count * sizeof(double))); }

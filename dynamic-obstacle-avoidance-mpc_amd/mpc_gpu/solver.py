@@ -535,6 +535,15 @@ class BatchedMpc:
     def set_accumulators(self, iters_acc=None, status_acc=None):
         _lib.check(_lib.lib().mpc_set_accumulators(self._h, _ptr(iters_acc), _ptr(status_acc)))
 
+    def debug_trace(self, enable=True, batch=None):
+        """(mu, sigma, alpha, cmax) of every interior-point iteration of the following solves (include/mpc_gpu.h mpc_debug_trace): switches the record
+        on or off and returns what it held, (batch, qp_iter_max, 4) with instance b's iterations in block b -- zeros right after enabling and while
+        it is off.  The call waits for the handle's stream only: a caller who solved on another stream synchronises that stream first."""
+        batch = self.max_batch if batch is None else int(batch)
+        out = np.zeros((batch if 1 <= batch <= self.max_batch else 1, int(self.cfg.qp_iter_max), 4))      # (`batch` itself is the library's to judge)
+        _lib.check(_lib.lib().mpc_debug_trace(self._h, 1 if enable else 0, batch, _ptr(out)))
+        return out
+
     def profile_enable(self, on=True, every=1):
         """HIP events around every `every`-th solve launch (on=False: off)."""
         _lib.check(_lib.lib().mpc_profile_enable(self._h, int(every) if on else 0))

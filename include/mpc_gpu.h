@@ -503,7 +503,10 @@ int mpc_profile_read(mpc_handle *h, double *sum_ms, int *launches);
 int mpc_set_accumulators(mpc_handle *h, int32_t *d_iters_acc, int32_t *d_status_acc);
 
 /* Debug aid for parity work: when enabled, every solve records (mu, sigma, alpha, cmax) of each interior-point
- * iteration into a device buffer [max_batch][qp_iter_max][4]; host_out (may be NULL) receives the first `batch` rows. */
+ * iteration into a device buffer [max_batch][qp_iter_max][4]; host_out (may be NULL) receives the first `batch` rows
+ * (instance b's iterations at [b], whatever the launch order; batch outside [1, max_batch] with a host_out: MPC_ERR_ARG).
+ * Rows at and behind an instance's iteration count keep what they held (zero from enabling on).
+ * The call waits for the handle's stream only: a caller who solved on another stream synchronises that stream first. */
 int mpc_debug_trace(mpc_handle *h, int enable, int batch, double *host_out);
 
 /* lanes per instance (64, 32, 16 or 8) the dispatcher picked for `batch`; 0 = automatic (default) */

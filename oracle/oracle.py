@@ -71,10 +71,24 @@ def use_bench_build():
     return so
 
 
+_OTHER = None
+
+
+def use_library(path):
+    """a child process of tests/test_ip_trace_host.py only: switch THIS process to another build of the same source (there: -ffp-contract=fast, a
+    second rounding of the same arithmetic).  The checker of the process that runs the tests is never switched."""
+    global _LIB, _OTHER
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    _OTHER = os.path.abspath(path)
+    _LIB = None
+    return _OTHER
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        _LIB = C.CDLL(os.path.join(_HERE, "liborc_bench.so") if _BENCH else build())
+        _LIB = C.CDLL(_OTHER if _OTHER else os.path.join(_HERE, "liborc_bench.so") if _BENCH else build())
         L = _LIB
         cp = C.POINTER(OrcConfig)
         L.orc_default_config.argtypes = [cp, C.c_int, C.c_int, _d]
