@@ -475,6 +475,137 @@ __global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, 
     }
 }
 
+// ROLLOUT MERIT (mpc_rollout_merit_dev): what a plan's inputs do on the plant.  Instance b rolls its U out from x0 -- X^r_0 = x0, X^r_{i+1} = F(X^r_i, U_i) with
+// dyn_step's F -- and reports the NLP objective at (X^r, U) as the solve's tail forms it, the defect of a GIVEN iterate X, the least margin of X^r to the
+// obstacles and the largest violation of the state boxes by X^r.  (No reference counterpart; the defect is acados' get_residuals()[1] of the iterate.)
+// x0, P and goal come from row b / members (members = K: the K members of a multi-start group share one row), U, X and every per-instance table from row b.
+// One wavefront per instance, stage i on lane i (N + 1 <= 63), four instances per workgroup; no LDS, no atomics.
+// The plant is a chain of integrators (adjoint_inputs uses the same fact for the transposed problem), so the rollout is not a serial chain of N steps but
+// three levels of exclusive prefix sums over the stage lanes:
+//   (v, om)_i = (v, om)_0 + sum_{k < i} dt u_k;   psi_i = psi_0 + sum_{k < i} (dt om_k + dt^2 / 2 u_al,k);   (x, y)_i = (x, y)_0 + sum_{k < i} (sx, sy)_k,
+// (sx, sy)_k being dyn_step's own quadrature at lane k's (psi_k, v_k, om_k, u_k): four sincos per lane, all lanes at once.  A scan is six __shfl_up rounds in a
+// fixed order (distances 1 .. 32), so a launch gives the same bits every run; against the serial chain a sum of <= 62 terms differs by its rounding alone.
+// Cost, defect, margin and box violation are then per lane and end in one wavefront reduction each (sum, max, min, max); lane 0 stores.  The obstacle loop is a
+// run-time loop (1 .. 32 obstacles, mpc_create2's handles included).  A non-finite input reaches every later stage of its own instance and so its merit; the
+// lanes of a wavefront hold one instance, nothing of a neighbour's is read or written.
+struct MeritArgs {
+    const double *U, *X;                                        // [B][N][2]; [B][N + 1][5] or null (needed for the defect alone)
+    double *merit, *defect, *margin, *boxviol, *Xr;             // [B] each and [B][N + 1][5]; any of them null
+    int members;
+};
+
+// exclusive prefix sums of a and b over the 64 lanes, lane 0 first: inclusive Hillis-Steele rounds, then one lane up
+__device__ __forceinline__ void scan2_exclusive(double &a, double &b, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double ta = __shfl_up(a, d), tb = __shfl_up(b, d);
+        if (lane >= d) { a += ta; b += tb; }
+    }
+    const double ea = __shfl_up(a, 1), eb = __shfl_up(b, 1);
+    a = lane ? ea : 0.0; b = lane ? eb : 0.0;
+}
+
+__global__ __launch_bounds__(kGroupThreads) void rollout_merit_kernel(const KParams p, const MeritArgs a)
+{
+    const int i = threadIdx.x & 63;
+    const int inst = __builtin_amdgcn_readfirstlane(blockIdx.x * kGroupWaves + (threadIdx.x >> 6));
+    if (inst >= p.batch) return;                                // (wave-uniform: every cross-lane step below runs with all 64 lanes)
+    const int N = p.N, no = p.n_obst, row = inst / a.members;
+    const bool act = i <= N, has_u = i < N;
+    const double dt = p.dt;
+    double x0v[5], gl[2], ui[2] = {0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < 5; c++) x0v[c] = p.x0[(size_t)row * 5 + c];
+    gl[0] = p.goal[(size_t)row * 2]; gl[1] = p.goal[(size_t)row * 2 + 1];
+    if (has_u) { ui[0] = a.U[((size_t)inst * N + i) * 2]; ui[1] = a.U[((size_t)inst * N + i) * 2 + 1]; }
+    // ---- the rollout: three levels of scans (lanes >= N add zero) ----
+    double xr[5];
+    xr[3] = dt * ui[0]; xr[4] = dt * ui[1];
+    scan2_exclusive(xr[3], xr[4], i);
+    xr[3] += x0v[3]; xr[4] += x0v[4];
+    double dpsi = has_u ? dt * xr[4] + p.h2 * ui[1] : 0.0, unused = 0.0;
+    scan2_exclusive(dpsi, unused, i);
+    xr[2] = x0v[2] + dpsi;
+    double sx = 0.0, sy = 0.0;
+    if (has_u) {
+        const double xs[5] = {0.0, 0.0, xr[2], xr[3], xr[4]};
+        double xn[5];
+        dyn_step<false>(xs, ui, dt, xn, nullptr, nullptr);
+        sx = xn[0]; sy = xn[1];
+    }
+    scan2_exclusive(sx, sy, i);
+    xr[0] = x0v[0] + sx; xr[1] = x0v[1] + sy;
+    if (a.Xr && act) {
+#pragma unroll
+        for (int c = 0; c < 5; c++) a.Xr[((size_t)inst * (N + 1) + i) * 5 + c] = xr[c];
+    }
+    // ---- the NLP objective at (X^r, U) with everything the solve's tail uses for this instance, and the margin ----
+    if (a.merit || a.margin) {
+        const double ex = x0v[0] - gl[0], ey = x0v[1] - gl[1];                                  // slack schedule, robot_ocp_problem.py:145-152
+        const double scale = p.slack_a * (ex * ex + ey * ey + x0v[3] * x0v[3] + x0v[4] * x0v[4] + p.slack_b);
+        const double alpha_i = p.alpha ? p.alpha[(size_t)inst * (N + 1) + (act ? i : N)] : scale * (double)(N - i) / (double)N;
+        const double zpen = alpha_i * (has_u ? p.ss : 1.0);
+        double J = 0.0, margin = INFINITY;
+        if (act) {
+            double r[6];
+            load_ref_or_goal<true>(p.yref, p.ref_off, p.ref_T, inst, i, has_u, gl, r);
+            if (p.ip_w) {
+                IpConst *pw = ip_const(p.ip_w, (size_t)inst * kIpW);
+                const double wg[6] = {pw[kIpWg], pw[kIpWg + 1], pw[kIpWg + 2], pw[kIpWg + 3], pw[kIpWg + 4], pw[kIpWg + 5]};
+                const double we[4] = {pw[kIpWe], pw[kIpWe + 1], pw[kIpWe + 2], pw[kIpWe + 3]};
+                J = ls_cost_ref(wg, we, xr, ui, r, has_u);
+            } else {
+                J = ls_cost_ref(p.Wg, p.Weg, xr, ui, r, has_u);
+            }
+            const uint32_t present = p.omask ? omask_word(p.omask, inst, no) : 0xffffffffu;
+            const double *Pg = p.P + ((size_t)row * (N + 1) + i) * no * 2;
+            for (int j = 0; j < no; j++) {
+                if (!((present >> j) & 1u)) continue;           // an absent obstacle: no penalty, no margin; its words of P are not read
+                const double dx = xr[0] - Pg[2 * j], dy = xr[1] - Pg[2 * j + 1], d2 = dx * dx + dy * dy;
+                const double hv = d2 - (p.ip_r2 ? p.ip_r2[(size_t)inst * no + j] : p.r2);
+                const double v = hv < 0 ? -hv : 0.0;
+                J += zpen * (v + 0.5 * v * v);
+                if (i >= 1) margin = fmin(margin, sqrt(d2) - (p.ip_rhit ? p.ip_rhit[(size_t)inst * no + j] : p.r_hit));
+            }
+        }
+        if (a.merit) { J = seg_sum<64>(J, i); if (i == 0) a.merit[inst] = J; }
+        if (a.margin) { margin = -seg_max<64>(-margin, i); if (i == 0) a.margin[inst] = margin; }
+    }
+    // ---- the defect of the given iterate: max(|X_0 - x0|, max_i |X_{i+1} - F(X_i, U_i)|) ----
+    if (a.defect) {
+        double def = 0.0;
+        if (has_u) {
+            const double *Xg = a.X + ((size_t)inst * (N + 1) + i) * 5;
+            const double xi[5] = {Xg[0], Xg[1], Xg[2], Xg[3], Xg[4]};
+            double xn[5];
+            dyn_step<false>(xi, ui, dt, xn, nullptr, nullptr);
+#pragma unroll
+            for (int c = 0; c < 5; c++) {
+                def = fmax(def, fabs(Xg[5 + c] - xn[c]));
+                if (i == 0) def = fmax(def, fabs(xi[c] - x0v[c]));
+            }
+        }
+        def = seg_max<64>(def, i);
+        if (i == 0) a.defect[inst] = def;
+    }
+    // ---- the largest violation of the instance's state boxes by X^r: x, y, v, om at the stages that have the rows ----
+    if (a.boxviol) {
+        double viol = 0.0;
+        if (i >= 1 && (i < N || (i == N && p.bx_terminal))) {
+            const double xs[4] = {xr[0], xr[1], xr[3], xr[4]};
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const double lo = p.ip_b ? p.ip_b[(size_t)inst * kIpB + kIpBxLo + c] : p.bx_lo[c];
+                const double hi = p.ip_b ? p.ip_b[(size_t)inst * kIpB + kIpBxHi + c] : p.bx_hi[c];
+                viol = fmax(viol, fmax(lo - xs[c], xs[c] - hi));
+            }
+        }
+        viol = seg_max<64>(viol, i);
+        if (i == 0) a.boxviol[inst] = viol;
+    }
+}
+
 // EPISODE REFILL (mpc_episode_refill_dev): a sweep over more seeds than there are slots streams the seeds through the slots -- in front of every
 // fused control step, a slot whose episode has ended (ep_flags bit 0: goal reached, robot_ocp_problem.py:247-250; or ep_steps >= max_steps: the budget of
 // experiments.py:20-36) parks its result row under its seed index and starts the next seed that has not been started yet.  Two launches:

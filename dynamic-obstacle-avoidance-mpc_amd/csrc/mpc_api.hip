@@ -812,6 +812,30 @@ int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, 
     return MPC_OK;
 }
 
+int mpc_rollout_merit_dev(mpc_handle *h, int batch, int members, const double *d_x0, const double *d_P, const double *d_goal, const double *d_X,
+                          const double *d_U, double *d_merit, double *d_defect, double *d_margin, double *d_boxviol, double *d_Xr, void *stream)
+{
+    // (what needs no handle is judged first: the same answers with and without a device)
+    if (batch < 1) return fail(MPC_ERR_ARG, "batch outside [1, max_batch]");
+    if (members < 1) return fail(MPC_ERR_ARG, "members must be >= 1");
+    if (!d_merit && !d_defect && !d_margin && !d_boxviol && !d_Xr) return fail(MPC_ERR_ARG, "no output asked for");
+    if (d_defect && !d_X) return fail(MPC_ERR_ARG, "d_defect needs d_X (the defect is that of a given iterate)");
+    if (!d_x0 || !d_P || !d_goal || !d_U) return fail(MPC_ERR_ARG, "null device pointer (d_x0, d_P, d_goal and d_U are mandatory)");
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (batch > h->max_batch) return fail(MPC_ERR_ARG, "batch outside [1, max_batch]");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = pick(h, stream);
+    // the constants and per-instance inputs of the solve that would be launched now: its kernel arguments, none of its outputs
+    mpc::KParams p = solve_params(h, batch, d_x0, d_P, nullptr, d_goal, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    p.trace = nullptr;
+    p.r_hit = 1.0 + 0.2;               // o.r + R_ROBOT, as mpc_closed_loop_step_dev sets it
+    int rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc;
+    mpc::MeritArgs a = {d_U, d_X, d_merit, d_defect, d_margin, d_boxviol, d_Xr, members};
+    hipLaunchKernelGGL(mpc::rollout_merit_kernel, dim3((batch + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, p, a);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 int mpc_plant_step_dev(mpc_handle *h, int batch, const double *d_x, const double *d_u, double *d_xnext, void *stream)
 {
     int rc = check_batch(h, batch); if (rc) return rc;

@@ -102,6 +102,7 @@ SYMBOLS = {
     "mpc_reset_guess_interp_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mpc_seed_guesses_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "mpc_select_best_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _d, C.c_int] + [_vp] * 7),
+    "mpc_rollout_merit_dev": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 11),
     "mpc_plant_step_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_obstacle_step_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _d, _d, _vp]),
     "mpc_linearize_dev": (C.c_int, [_vp, C.c_int] + [_vp] * 12),

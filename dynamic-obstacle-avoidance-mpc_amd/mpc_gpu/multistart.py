@@ -6,8 +6,12 @@ instance g K + k, and every member of a group is given the group's x0, obstacles
 
     mpc_seed_guesses_dev  ->  the ordinary solve launch (closed_loop_step_dev with flags = 0: the look-ahead fused)  ->  mpc_select_best_dev (broadcast)
 
+select_by="rollout" puts two launches between the solve and the selection -- mpc_predict_dev on the G scenario rows and mpc_rollout_merit_dev on the members'
+solved (X, U) with members = K -- and the selection then compares the candidates' ROLLOUT MERITS, the NLP objective of what the plant does under each U,
+instead of the costs the solve reports for iterates that need not be dynamically consistent.
+
 Nothing leaves the device between them: torch replicates the group inputs and carries the tensors, the `_dev` entry points do the work.  The pure helpers
-(`check_offsets`, `check_margin`, `check_group_shapes`, `replicate`) import without a GPU.  run_episodes, run_seed_sweep and PipelinedMpc do not know
+(`check_offsets`, `check_margin`, `check_select_by`, `check_group_shapes`, `replicate`) import without a GPU.  run_episodes, run_seed_sweep and PipelinedMpc do not know
 about groups."""
 import numpy as np
 
@@ -34,6 +38,16 @@ def check_margin(incumbent_margin):
     if not (0.0 <= m < 1.0):
         raise ValueError(f"incumbent_margin must be in [0, 1), got {incumbent_margin}")
     return m
+
+
+SELECT_BY = ("cost", "rollout")
+
+
+def check_select_by(select_by):
+    """what the selection compares: "cost" (the cost the solve reports) or "rollout" (mpc_rollout_merit_dev's merit) -- or ValueError"""
+    if not isinstance(select_by, str) or select_by not in SELECT_BY:
+        raise ValueError(f"select_by must be one of {SELECT_BY}, got {select_by!r}")
+    return select_by
 
 
 def check_group_shapes(scenarios, n_obst, x0, obstacles, goal):
@@ -65,7 +79,8 @@ class MultiStartMpc:
     Inputs and outputs are float64 / int32 device tensors; a numpy array is uploaded.  Everything runs on the object's own stream, which waits for the
     caller's current torch stream on entry and which that stream waits for on exit."""
 
-    def __init__(self, N=20, n_obst=3, Tf=2.0, scenarios=1, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, device=0, **cfg):
+    def __init__(self, N=20, n_obst=3, Tf=2.0, scenarios=1, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, device=0, select_by="cost", **cfg):
+        self.select_by = check_select_by(select_by)
         import torch
         off = check_offsets(offsets)
         self.K, self.G = int(off.shape[0]), check_scenarios(scenarios, off.shape[0])
@@ -84,6 +99,9 @@ class MultiStartMpc:
         self.cand_u0, self.cand_cost, self.cand_status, self.cand_iters = f64(B, 2), f64(B), i32(B), i32(B)
         self.winner, self.cost, self.u0 = i32(G), f64(G), f64(G, 2)
         self._xn, self._X1, self._U1 = f64(G, 5), f64(G, N + 1, 5), f64(G, N, 2)      # plant output; the reseed of member 0 of a failed group
+        if self.select_by == "rollout":      # the scenarios' look-ahead (one row per group) and what the rollout reports per candidate
+            self._P = f64(G, N + 1, no, 2)
+            self.cand_merit, self.cand_defect, self.cand_margin = f64(B), f64(B), f64(B)
         self.solved_X = self.solved_U = None
         self._warm = False
         torch.cuda.synchronize(self.dev)
@@ -153,14 +171,23 @@ class MultiStartMpc:
                                         self.cand_iters, flags=0, stream=s)
         if keep_solution:
             self.solved_X, self.solved_U = self.X.clone(), self.U.clone()
-        _lib.check(_lib.lib().mpc_select_best_dev(self.inner._h, self.G, self.K, self.cand_cost.data_ptr(), self.cand_status.data_ptr(), self.margin,
+        by = self.cand_cost
+        if self.select_by == "rollout":
+            self.inner.predict_dev(self.G, self._obst[:, 0].contiguous(), self._P, stream=s)
+            self.inner.rollout_merit_dev(self.B, self._x0[:, 0].contiguous(), self._P, self._goal[:, 0].contiguous(), self.U, X=self.X, merit=self.cand_merit,
+                                         defect=self.cand_defect, margin=self.cand_margin, members=self.K, stream=s)
+            by = self.cand_merit
+        _lib.check(_lib.lib().mpc_select_best_dev(self.inner._h, self.G, self.K, by.data_ptr(), self.cand_status.data_ptr(), self.margin,
                                                   _lib.SELECT_BROADCAST, self.X.data_ptr(), self.U.data_ptr(), self.winner.data_ptr(),
                                                   self.cost.data_ptr(), self.u0.data_ptr(), self.cand_u0.data_ptr(), s))
 
     def _result(self):
         G, K = self.G, self.K
-        return dict(u0=self.u0, cost=self.cost, winner=self.winner, cand_cost=self.cand_cost.view(G, K), cand_status=self.cand_status.view(G, K),
-                    cand_iters=self.cand_iters.view(G, K), cand_u0=self.cand_u0.view(G, K, 2))
+        out = dict(u0=self.u0, cost=self.cost, winner=self.winner, cand_cost=self.cand_cost.view(G, K), cand_status=self.cand_status.view(G, K),
+                   cand_iters=self.cand_iters.view(G, K), cand_u0=self.cand_u0.view(G, K, 2))
+        if self.select_by == "rollout":
+            out.update(cand_merit=self.cand_merit.view(G, K), cand_defect=self.cand_defect.view(G, K), cand_margin=self.cand_margin.view(G, K))
+        return out
 
     def _on_stream(self):
         torch = self._torch
@@ -173,7 +200,8 @@ class MultiStartMpc:
         solve launch over all scenarios * K members, select with broadcast -- behind it every member of a group holds the winner's iterate.
         x0 (G, 5), obstacles (G, n_obst, 4) = (x, y, vx, vy), goal (G, 2).  Returns device tensors that the next call overwrites: per scenario u0 (G, 2),
         cost (G,), winner (G,) int32 (-1: no eligible member; then cost = +inf, u0 = 0 and nothing was copied); per candidate cand_cost, cand_status,
-        cand_iters (G, K) and cand_u0 (G, K, 2).  keep_solution: solved_X / solved_U keep a copy of every member's iterate in front of the broadcast."""
+        cand_iters (G, K) and cand_u0 (G, K, 2).  select_by="rollout": the selection goes by the candidates' rollout merits, `cost` is the winner's merit, and
+        the dict also holds cand_merit, cand_defect and cand_margin (G, K) (mpc_rollout_merit_dev).  keep_solution: solved_X / solved_U keep a copy of every member's iterate in front of the broadcast."""
         outer, ctx = self._on_stream()
         with ctx:
             self._solve(x0, obstacles, goal, True, keep_first, keep_solution, self.stream.cuda_stream)

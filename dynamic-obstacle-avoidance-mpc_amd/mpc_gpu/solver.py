@@ -508,6 +508,14 @@ class BatchedMpc:
     def predict_dev(self, batch, obst, P, stream=None):
         _lib.check(_lib.lib().mpc_predict_dev(self._h, batch, _ptr(obst), _ptr(P), _ptr(stream)))
 
+    def rollout_merit_dev(self, batch, x0, P, goal, U, X=None, merit=None, defect=None, margin=None, boxviol=None, Xr=None, members=1, stream=None):
+        """Score the plans U (batch, N, 2) by simulating them (include/mpc_gpu.h mpc_rollout_merit_dev): X^r rolled out from x0 with the plant's integrator,
+        merit (batch,) the NLP objective at (X^r, U) as the solve launched now would report it, defect (batch,) of the given iterate X (batch, N+1, 5),
+        margin (batch,) of X^r to the obstacles, boxviol (batch,) of the state boxes by X^r, Xr (batch, N+1, 5).  Instance b reads row b // members of
+        x0, P (rows, N+1, n_obst, 2) and goal.  Device tensors; every output is optional, at least one must be given, and defect needs X."""
+        _lib.check(_lib.lib().mpc_rollout_merit_dev(self._h, int(batch), int(members), _ptr(x0), _ptr(P), _ptr(goal), _ptr(X), _ptr(U), _ptr(merit),
+                                                    _ptr(defect), _ptr(margin), _ptr(boxviol), _ptr(Xr), _ptr(stream)))
+
     def shift_dev(self, batch, X, U, stream=None):
         _lib.check(_lib.lib().mpc_shift_dev(self._h, batch, _ptr(X), _ptr(U), _ptr(stream)))
 

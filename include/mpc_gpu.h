@@ -317,6 +317,29 @@ int mpc_seed_guesses_dev(mpc_handle *h, int groups, int K, const double *d_x0, c
                          double *d_X, double *d_U, void *stream);
 int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, const int32_t *d_status, double incumbent_margin, int flags,
                         double *d_X, double *d_U, int32_t *d_winner, double *d_best_cost, double *d_best_u0, const double *d_u0, void *stream);
+/* ROLLOUT MERIT: score a plan by simulating its inputs.  The cost a solve reports is the NLP objective at the iterate (X + dX, U + dU), whose states follow
+ * the linearisation about the guess, not the plant; one RTI iteration from a poor guess that pair is far from dynamically consistent, and its cost cannot be
+ * compared with that of a converged one.  This call rolls U out from x0 -- X^r_0 = x0, X^r_{i+1} = F(X^r_i, U_i), F the integrator of mpc_plant_step_dev
+ * (robot_model.py:39-43) -- and reports, per instance b (nothing in the reference stands behind merit, margin, boxviol or Xr; the defect is what acados'
+ * get_residuals()[1], res_eq, measures on the iterate):
+ *   d_merit[b]    the NLP objective (LS cost + exact penalty alpha_i ss (v + v^2 / 2), v = max(0, -h)) at (X^r, U), with everything the cost of the solve
+ *                 launched at this moment would use for instance b: the slack schedule (built-in from (x0, goal), or mpc_set_slack_schedule's), the per-stage
+ *                 reference at its current offset, per-instance W / We / r_safe, the obstacle mask;
+ *   d_defect[b]   max(|X_0 - x0|_inf, max_i |X_{i+1} - F(X_i, U_i)|_inf) of the GIVEN iterate d_X (needs d_X; d_X is read for nothing else);
+ *   d_margin[b]   min over i = 1 .. N and the present obstacles j of |X^r_i[0:2] - P_ij| - r_hit_j, r_hit the fused step's (1.2, or the per-instance table);
+ *                 +inf when no obstacle is present;
+ *   d_boxviol[b]  the largest violation (>= 0) of the instance's state boxes (mpc_config's, or mpc_set_instance_bounds') by X^r: x, y, v, omega at stages
+ *                 1 .. N - 1, and N under bx_terminal;
+ *   d_Xr[b]       X^r itself, [N + 1][5].
+ * Instance b takes x0[5], P[N + 1][n_obst][2] and goal[2] from row b / members of d_x0, d_P, d_goal (members = 1: one row per instance; members = K: a
+ * multi-start group shares one row, so P is predicted once per scenario), and U[N][2], X[N + 1][5] and every per-instance table from row b.  Every output
+ * pointer may be NULL, not all of them; an output that is not asked for is not written.  MPC_ERR_ARG (with a message, nothing launched): batch < 1 or
+ * > max_batch, members < 1, no output, d_defect without d_X, a null mandatory pointer or handle, and a per-instance feature that covers fewer instances than
+ * batch.  Non-finite inputs propagate into the instance's own merit (mpc_select_best_dev treats such a member as not eligible) and touch no other
+ * instance's words.  The rollout is three levels of prefix sums over the horizon (the plant is a chain of integrators), summed in a fixed order: the same
+ * bits every launch, and the serial chain of mpc_plant_step_dev to rounding (a sum of <= 62 terms in another order). */
+int mpc_rollout_merit_dev(mpc_handle *h, int batch, int members, const double *d_x0, const double *d_P, const double *d_goal, const double *d_X,
+                          const double *d_U, double *d_merit, double *d_defect, double *d_margin, double *d_boxviol, double *d_Xr, void *stream);
 int mpc_plant_step_dev(mpc_handle *h, int batch, const double *d_x, const double *d_u, double *d_xnext, void *stream);
 /* Obstacle.step() ground-truth motion (visualization.py:20-33); d_noise[B*n_obst][2] standard normals or NULL */
 int mpc_obstacle_step_dev(mpc_handle *h, int count, double *d_obst, const double *d_noise,
