@@ -378,6 +378,25 @@ __global__ void reset_guess_kernel(int batch, int N, const double *__restrict__ 
 constexpr int kGroupThreads = 256, kGroupWaves = kGroupThreads / 64;
 constexpr double kPi = 3.14159265358979323846;
 
+// stage i of the family's iterate with offset a around the state x and d = goal - x[0:2] of length L, written ONCE for seed_guesses_kernel and
+// group_step_kernel: s = i / N, sn = sin(pi s), cs = cos(pi s) are the caller's (a lane forms them once for all the members it writes)
+__device__ __forceinline__ void seed_stage(const double x[5], double dx, double dy, double L, double a, int i, double s, double sn, double cs, double xi[5])
+{
+    const double px = x[0], py = x[1], psi = x[2];
+    xi[0] = px; xi[1] = py; xi[2] = psi; xi[3] = 0.0; xi[4] = 0.0;
+    if (!(L < 1e-9)) {                                          // (a NaN length takes this branch and propagates)
+        if (i == 0) {
+            xi[3] = x[3]; xi[4] = x[4];
+        } else {
+            const double nx = -dy / L, ny = dx / L;
+            xi[0] = px + s * dx + a * sn * nx;
+            xi[1] = py + s * dy + a * sn * ny;
+            const double e = atan2(dy + a * kPi * cs * ny, dx + a * kPi * cs * nx) - psi;
+            xi[2] = psi + (e - 2.0 * kPi * rint(e / (2.0 * kPi)));
+        }
+    }
+}
+
 __global__ __launch_bounds__(kGroupThreads) void seed_guesses_kernel(int groups, int K, int N, int keep_first, const double *__restrict__ x0,
                                                                      const double *__restrict__ goal, const double *__restrict__ offsets,
                                                                      double *__restrict__ X, double *__restrict__ U)
@@ -387,23 +406,12 @@ __global__ __launch_bounds__(kGroupThreads) void seed_guesses_kernel(int groups,
     if (inst >= groups * K) return;
     const int g = inst / K, k = inst - g * K;
     if ((keep_first && k == 0) || i > N) return;
-    const double *x = x0 + (size_t)g * 5;
-    const double px = x[0], py = x[1], psi = x[2];
-    const double dx = goal[(size_t)g * 2] - px, dy = goal[(size_t)g * 2 + 1] - py;
+    const double x[5] = {x0[(size_t)g * 5], x0[(size_t)g * 5 + 1], x0[(size_t)g * 5 + 2], x0[(size_t)g * 5 + 3], x0[(size_t)g * 5 + 4]};
+    const double dx = goal[(size_t)g * 2] - x[0], dy = goal[(size_t)g * 2 + 1] - x[1];
     const double L = sqrt(dx * dx + dy * dy);
-    double xi[5] = {px, py, psi, 0.0, 0.0};
-    if (!(L < 1e-9)) {                                          // (a NaN length takes this branch and propagates)
-        if (i == 0) {
-            xi[3] = x[3]; xi[4] = x[4];
-        } else {
-            const double a = offsets[k], nx = -dy / L, ny = dx / L, s = (double)i / (double)N;
-            const double sn = sin(kPi * s), cs = cos(kPi * s);
-            xi[0] = px + s * dx + a * sn * nx;
-            xi[1] = py + s * dy + a * sn * ny;
-            const double e = atan2(dy + a * kPi * cs * ny, dx + a * kPi * cs * nx) - psi;
-            xi[2] = psi + (e - 2.0 * kPi * rint(e / (2.0 * kPi)));
-        }
-    }
+    const double s = (double)i / (double)N;
+    double xi[5];
+    seed_stage(x, dx, dy, L, offsets[k], i, s, sin(kPi * s), cos(kPi * s), xi);
     double *Xi = X + ((size_t)inst * (N + 1) + i) * 5;
 #pragma unroll
     for (int c = 0; c < 5; c++) Xi[c] = xi[c];
@@ -422,16 +430,12 @@ __global__ __launch_bounds__(kGroupThreads) void seed_guesses_kernel(int groups,
 constexpr int kSelectBroadcast = 1;                             // MPC_SELECT_BROADCAST
 constexpr int kSelectXRounds = 5, kSelectURounds = 2;           // 64 x 5 >= 5 (N + 1), 64 x 2 >= 2 N for N <= 62
 
-__global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, int K, int N, double margin, int flags, const double *__restrict__ cost,
-                                                                    const int32_t *__restrict__ status, double *X, double *U,
-                                                                    int32_t *__restrict__ winner, double *__restrict__ best_cost,
-                                                                    double *__restrict__ best_u0, const double *__restrict__ u0)
+// the rule itself, written ONCE for select_best_kernel and group_step_kernel: called by all 64 lanes of the group's wavefront, every lane returns the
+// winner (-1: no eligible member) and gets its cost in c (+inf without a winner)
+__device__ __forceinline__ int select_member(int K, double margin, const double *__restrict__ cost, const int32_t *__restrict__ status, size_t base,
+                                             int lane, double &c)
 {
-    const int lane = threadIdx.x & 63;
-    const int g = blockIdx.x * kGroupWaves + (threadIdx.x >> 6);
-    if (g >= groups) return;
-    const size_t base = (size_t)g * K;
-    double c = INFINITY;
+    c = INFINITY;
     int idx = 64 + lane;
     if (lane < K) {
         const double cc = cost[base + lane];
@@ -447,7 +451,21 @@ __global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, 
         if (oc < c || (oc == c && oi < idx)) { c = oc; idx = oi; }
     }
     if (margin > 0.0 && keep0 && idx != 0 && !(c < (1.0 - margin) * c0)) { c = c0; idx = 0; }
-    const int w = idx < 64 ? idx : -1;
+    if (idx >= 64) c = INFINITY;
+    return idx < 64 ? idx : -1;
+}
+
+__global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, int K, int N, double margin, int flags, const double *__restrict__ cost,
+                                                                    const int32_t *__restrict__ status, double *X, double *U,
+                                                                    int32_t *__restrict__ winner, double *__restrict__ best_cost,
+                                                                    double *__restrict__ best_u0, const double *__restrict__ u0)
+{
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kGroupWaves + (threadIdx.x >> 6);
+    if (g >= groups) return;
+    const size_t base = (size_t)g * K;
+    double c;
+    const int w = select_member(K, margin, cost, status, base, lane, c);
     if (lane == 0) {
         winner[g] = w;
         if (best_cost) best_cost[g] = w >= 0 ? c : INFINITY;
@@ -472,6 +490,132 @@ __global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, 
         for (int r = 0; r < kSelectXRounds; r++) { const int j = lane + 64 * r; if (j < LX) xd[j] = xr[r]; }
 #pragma unroll
         for (int r = 0; r < kSelectURounds; r++) { const int j = lane + 64 * r; if (j < LU) ud[j] = ur[r]; }
+    }
+}
+
+// GROUP CONTROL STEP (mpc_group_step_dev): everything a multi-start control step does behind its solve launch, in ONE launch, for every group g whose
+// episode runs (ep_flags[g] bit 0 clear) -- in this order:
+//   1. select      select_member on key / status; winner, best_key, best_u0 = the winner's row of the solve's u0, (0, 0) without a winner;
+//   2. plant       x[g] <- F(x[g], best_u0) with dyn_step, in place;
+//   3. obstacles   obst[g] advanced in place, obstacle j on lane j (a run-time count, 1 .. 32): obstacle_noise / obstacle_advance as obstacle_step_kernel;
+//   4. bookkeeping the fused step's rule (rti_kernel.hpp, "plant, obstacles, episode bookkeeping") on the NEW state and the MOVED obstacles, with r_hit and the
+//                  obstacle mask of row g K of the per-instance tables; lost / switched counters;
+//   5. iterates    member 0 <- the winner's iterate shifted (shift_kernel's rule), members 1 .. K - 1 <- seed_stage for offsets[k] around the new x[g];
+//                  without a winner member 0 is seeded too (offsets[0]).  No broadcast: no word is written that this launch overwrites;
+//   6. inputs      the new x[g], obst[g], goal[g] into the K member rows of the replicated arrays, member_flags[g K + k] = ep_flags[g] & 1.
+// One wavefront per group, a stage per lane where rows are formed (N + 1 <= 63), a member per lane in the selection (K <= 64), four groups per workgroup;
+// no LDS, no atomics, no workgroup barrier (a wavefront that has nothing to do leaves).  HAZARDS: a wavefront touches the words of its own group alone, and
+// it reads EVERYTHING it reads of them -- the winner's rows among them, which point 5 overwrites when the winner is member 1 .. K - 1 -- before its first
+// store: the reads are issued above the wait below, which lets none of them be outstanding when the stores begin.  An idle group reads its flag and
+// returns: none of its words is written.
+struct GroupStepArgs {
+    int groups, K, N, n_obst, flags;
+    double margin, dt, randomness, vmax, tol_goal, r_hit;
+    World world;
+    const double *key; const int32_t *status; const double *u0, *goal, *offsets, *noise;
+    double *x, *obst, *X, *U;
+    int32_t *winner; double *best_key, *best_u0, *min_margin; int32_t *ep_flags, *ep_steps, *lost, *switched;
+    double *member_x, *member_obst, *member_goal; int32_t *member_flags;
+    const double *ip_rhit; const uint32_t *omask;               // the tables of the solve the step stands behind, or null
+};
+constexpr int kGroupMarginAll = 1;                              // MPC_GROUP_MARGIN_ALL
+
+__global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupStepArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * kGroupWaves + (threadIdx.x >> 6));
+    if (g >= a.groups) return;                                  // (wave-uniform, like every branch around a cross-lane step below)
+    const int fl0 = a.ep_flags[g];
+    if (fl0 & 1) return;
+    const int K = a.K, N = a.N, no = a.n_obst;
+    const size_t base = (size_t)g * K;
+    // ---- 1. select; then every read of the group's words ----
+    double best;
+    const int w = select_member(K, a.margin, a.key, a.status, base, lane, best);
+    double ub[2] = {0.0, 0.0};
+    if (w >= 0) { ub[0] = a.u0[(base + w) * 2]; ub[1] = a.u0[(base + w) * 2 + 1]; }
+    double xg[5];
+#pragma unroll
+    for (int c = 0; c < 5; c++) xg[c] = a.x[(size_t)g * 5 + c];
+    const double gx = a.goal[(size_t)g * 2], gy = a.goal[(size_t)g * 2 + 1];
+    const double off = lane < K ? a.offsets[lane] : 0.0;
+    const double mm0 = a.min_margin[g];
+    const int steps0 = a.ep_steps[g];
+    const int lost0 = a.lost ? a.lost[g] : 0, sw0 = a.switched ? a.switched[g] : 0;
+    // the winner's iterate as member 0 will hold it: lane i <= N takes X[w][min(i + 1, N)] (X[N] kept), lane i < N - 1 takes U[w][i + 1] (U[N - 1] = 0)
+    double xs[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, us[2] = {0.0, 0.0};
+    if (w >= 0 && lane <= N) {
+        const double *Xw = a.X + ((base + w) * (size_t)(N + 1) + (lane < N ? lane + 1 : N)) * 5;
+#pragma unroll
+        for (int c = 0; c < 5; c++) xs[c] = Xw[c];
+        if (lane < N - 1) { const double *Uw = a.U + ((base + w) * (size_t)N + lane + 1) * 2; us[0] = Uw[0]; us[1] = Uw[1]; }
+    }
+    // ---- 2. plant (every lane, the same value) ----
+    double xn[5];
+    dyn_step<false>(xg, ub, a.dt, xn, nullptr, nullptr);
+    // ---- 3. obstacles, and the margin of the new state to where they are now ----
+    double ob[4] = {0.0, 0.0, 0.0, 0.0}, margin = INFINITY;
+    if (lane < no) {
+        const double *o = a.obst + ((size_t)g * no + lane) * 4;
+        ob[0] = o[0]; ob[1] = o[1]; ob[2] = o[2]; ob[3] = o[3];
+        if (a.noise) obstacle_noise(a.randomness, a.vmax, a.noise[((size_t)g * no + lane) * 2], a.noise[((size_t)g * no + lane) * 2 + 1], ob[2], ob[3]);
+        obstacle_advance(a.world, a.dt, ob[0], ob[2], ob[1], ob[3]);
+        const double ddx = xn[0] - ob[0], ddy = xn[1] - ob[1];
+        margin = sqrt(ddx * ddx + ddy * ddy) - (a.ip_rhit ? a.ip_rhit[base * no + lane] : a.r_hit);
+        // an absent obstacle moves, but is not counted (kGroupMarginAll: it is)
+        if (a.omask && !(a.flags & kGroupMarginAll) && !((omask_word(a.omask, (int)base, no) >> lane) & 1u)) margin = INFINITY;
+    }
+    margin = -seg_max<64>(-margin, lane);
+    // ---- 4. bookkeeping ----
+    int fl = fl0;
+    if (xn[0] < a.world.xmin || xn[0] > a.world.xmax || xn[1] < a.world.ymin || xn[1] > a.world.ymax) fl |= 2;
+    const double mm = fmin(mm0, margin);
+    if (mm <= 0.0) fl |= 4;
+    const double ex = xn[0] - gx, ey = xn[1] - gy;
+    const bool reached = sqrt(ex * ex + ey * ey) <= a.tol_goal;
+    if (reached) fl |= 1;
+    // ---- every load of the group's words has returned before the first store is issued ----
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        a.winner[g] = w;
+        if (a.best_key) a.best_key[g] = best;
+        a.min_margin[g] = mm;
+        a.ep_flags[g] = fl;
+        if (!reached) a.ep_steps[g] = steps0 + 1;
+        if (a.lost && w < 0) a.lost[g] = lost0 + 1;
+        if (a.switched && w > 0) a.switched[g] = sw0 + 1;
+    }
+    if (a.best_u0 && lane < 2) a.best_u0[(size_t)g * 2 + lane] = lane ? ub[1] : ub[0];
+    const double xc = lane == 0 ? xn[0] : (lane == 1 ? xn[1] : (lane == 2 ? xn[2] : (lane == 3 ? xn[3] : xn[4])));      // lane c < 5: entry c of the new state
+    if (lane < 5) a.x[(size_t)g * 5 + lane] = xc;
+    if (lane < no) { double *o = a.obst + ((size_t)g * no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+    if (a.member_flags && lane < K) a.member_flags[base + lane] = fl & 1;
+    // ---- 5. the next iterates and 6. the members' inputs ----
+    const double dx = gx - xn[0], dy = gy - xn[1];
+    const double L = sqrt(dx * dx + dy * dy);
+    const double s = (double)lane / (double)N;
+    const double sn = sin(kPi * s), cs = cos(kPi * s);          // once per lane, not once per member
+    for (int k = 0; k < K; k++) {
+        const double ak = __shfl(off, k);
+        double xi[5], ui[2] = {0.0, 0.0};
+        if (k == 0 && w >= 0) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) xi[c] = xs[c];
+            ui[0] = us[0]; ui[1] = us[1];
+        } else {
+            seed_stage(xn, dx, dy, L, ak, lane, s, sn, cs, xi);
+        }
+        if (lane <= N) {
+            double *Xi = a.X + ((base + k) * (size_t)(N + 1) + lane) * 5;
+#pragma unroll
+            for (int c = 0; c < 5; c++) Xi[c] = xi[c];
+            if (lane < N) { double *Ui = a.U + ((base + k) * (size_t)N + lane) * 2; Ui[0] = ui[0]; Ui[1] = ui[1]; }
+        }
+        if (a.member_x && lane < 5) a.member_x[(base + k) * 5 + lane] = xc;
+        if (a.member_goal && lane < 2) a.member_goal[(base + k) * 2 + lane] = lane ? gy : gx;
+        if (a.member_obst && lane < no) { double *o = a.member_obst + ((base + k) * (size_t)no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
     }
 }
 

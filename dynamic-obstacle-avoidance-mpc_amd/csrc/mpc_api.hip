@@ -812,6 +812,42 @@ int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, 
     return MPC_OK;
 }
 
+static_assert(mpc::kGroupMarginAll == MPC_GROUP_MARGIN_ALL, "the kernel's flag is the header's");
+int mpc_group_step_dev(mpc_handle *h, int groups, int K, const double *d_key, const int32_t *d_status, const double *d_u0, double incumbent_margin,
+                       int flags, double *d_x, double *d_obst, const double *d_goal, const double *d_offsets, const double *d_noise, double randomness,
+                       double vmax, double *d_X, double *d_U, const mpc_group_step_out *out, void *stream)
+{
+    int rc = check_groups(h, groups, K); if (rc) return rc;
+    if (!(incumbent_margin >= 0.0) || !(incumbent_margin < 1.0)) return fail(MPC_ERR_ARG, "incumbent_margin must be in [0, 1)");
+    if (flags & ~MPC_GROUP_MARGIN_ALL) return fail(MPC_ERR_ARG, "unknown flags (MPC_GROUP_MARGIN_ALL is the only one)");
+    if (groups == 0) return MPC_OK;
+    if (!d_key || !d_status || !d_u0 || !d_x || !d_obst || !d_goal || !d_offsets || !d_X || !d_U || !out)
+        return fail(MPC_ERR_ARG, "null device pointer (d_key, d_status, d_u0, d_x, d_obst, d_goal, d_offsets, d_X, d_U and out are mandatory)");
+    if (!out->winner || !out->min_margin || !out->ep_flags || !out->ep_steps)
+        return fail(MPC_ERR_ARG, "null device pointer in out (winner, min_margin, ep_flags and ep_steps are mandatory)");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = pick(h, stream);
+    // the per-instance tables of the solve this step stands behind (r_hit rows, obstacle mask), with that solve's coverage checks
+    mpc::KParams p = solve_params(h, groups * K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    p.trace = nullptr;
+    rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc;
+    mpc::GroupStepArgs a;
+    a.groups = groups; a.K = K; a.N = h->cfg.N; a.n_obst = h->cfg.n_obst; a.flags = flags;
+    a.margin = incumbent_margin; a.dt = h->cfg.Tf / h->cfg.N; a.randomness = randomness; a.vmax = vmax;
+    a.tol_goal = 0.15;               // TOL, src/models/world_specification.py:45
+    a.r_hit = 1.0 + 0.2;             // o.r + R_ROBOT, as mpc_closed_loop_step_dev sets it
+    a.world = make_world(h->cfg);
+    a.key = d_key; a.status = d_status; a.u0 = d_u0; a.goal = d_goal; a.offsets = d_offsets; a.noise = d_noise;
+    a.x = d_x; a.obst = d_obst; a.X = d_X; a.U = d_U;
+    a.winner = out->winner; a.best_key = out->best_key; a.best_u0 = out->best_u0; a.min_margin = out->min_margin;
+    a.ep_flags = out->ep_flags; a.ep_steps = out->ep_steps; a.lost = out->lost; a.switched = out->switched;
+    a.member_x = out->member_x; a.member_obst = out->member_obst; a.member_goal = out->member_goal; a.member_flags = out->member_flags;
+    a.ip_rhit = p.ip_rhit; a.omask = p.omask;
+    hipLaunchKernelGGL(mpc::group_step_kernel, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 int mpc_rollout_merit_dev(mpc_handle *h, int batch, int members, const double *d_x0, const double *d_P, const double *d_goal, const double *d_X,
                           const double *d_U, double *d_merit, double *d_defect, double *d_margin, double *d_boxviol, double *d_Xr, void *stream)
 {

@@ -23,6 +23,7 @@ STEP_MARGIN_ALL = 256
 REFILL_ALIAS_BUG, REFILL_INTERP_GUESS, REFILL_DRAW_NOISE = 1, 2, 4      # MPC_REFILL_* (mpc_episode_refill_dev)
 TRACE_START, TRACE_STEP = 0, 1      # MPC_TRACE_* (mpc_episode_trace_dev)
 SELECT_BROADCAST = 1                # MPC_SELECT_BROADCAST (mpc_select_best_dev)
+GROUP_MARGIN_ALL = 1                # MPC_GROUP_MARGIN_ALL (mpc_group_step_dev)
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
 MAX_SQP_ITER = 100       # MPC_MAX_SQP_ITER
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
@@ -61,6 +62,12 @@ class RefillTables(C.Structure):
 class EpisodeTrace(C.Structure):
     """Mirror of `struct mpc_episode_trace` (include/mpc_gpu.h): device pointers only -- the row map, the per-slot state and the per-seed rows of a sweep's trace."""
     _fields_ = [(n, _vp) for n in ("seed_row", "slot_state", "len", "x", "obst", "u", "status", "iters", "pred")]
+
+
+class GroupStepOut(C.Structure):
+    """Mirror of `struct mpc_group_step_out` (include/mpc_gpu.h): device pointers only -- what the group control step writes per group and per member."""
+    _fields_ = [(n, _vp) for n in ("winner", "best_key", "best_u0", "min_margin", "ep_flags", "ep_steps", "lost", "switched",
+                                   "member_x", "member_obst", "member_goal", "member_flags")]
 
 
 _cfgp = C.POINTER(MpcConfig)
@@ -102,6 +109,8 @@ SYMBOLS = {
     "mpc_reset_guess_interp_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mpc_seed_guesses_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "mpc_select_best_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _d, C.c_int] + [_vp] * 7),
+    "mpc_group_step_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _d, C.c_int, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp,
+                                     C.POINTER(GroupStepOut), _vp]),
     "mpc_rollout_merit_dev": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 11),
     "mpc_plant_step_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_obstacle_step_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _d, _d, _vp]),

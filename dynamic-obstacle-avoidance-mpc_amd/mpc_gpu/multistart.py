@@ -11,8 +11,12 @@ solved (X, U) with members = K -- and the selection then compares the candidates
 instead of the costs the solve reports for iterates that need not be dynamically consistent.
 
 Nothing leaves the device between them: torch replicates the group inputs and carries the tensors, the `_dev` entry points do the work.  The pure helpers
-(`check_offsets`, `check_margin`, `check_select_by`, `check_group_shapes`, `replicate`) import without a GPU.  run_episodes, run_seed_sweep and PipelinedMpc do not know
-about groups."""
+(`check_offsets`, `check_margin`, `check_select_by`, `check_group_shapes`, `replicate`, `episode_arguments`) import without a GPU.
+
+The CLOSED LOOP has two forms.  step() composes a control step from the entry points above and the plant / obstacle / shift / seed launches.  step_fused()
+runs the member solve and then ONE launch, mpc_group_step_dev (select, plant, obstacles, episode bookkeeping per group, next iterates, the members' inputs;
+DESIGN.md section 4m), and run_multistart_episodes drives it to the reference's result table.  run_seed_sweep and PipelinedMpc do not know about groups
+(DESIGN.md section 8)."""
 import numpy as np
 
 from . import _lib
@@ -93,7 +97,7 @@ class MultiStartMpc:
         G, K, B, N, no = self.G, self.K, self.B, self.N, self.n_obst
         f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=self.dev)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=self.dev)
-        self.offsets = torch.from_numpy(off).to(self.dev)
+        self.offsets, self.offsets_host = torch.from_numpy(off).to(self.dev), off
         self.X, self.U = f64(B, N + 1, 5), f64(B, N, 2)                      # the iterates of all members
         self._x0, self._obst, self._goal = f64(G, K, 5), f64(G, K, no, 4), f64(G, K, 2)      # the group inputs, replicated per member
         self.cand_u0, self.cand_cost, self.cand_status, self.cand_iters = f64(B, 2), f64(B), i32(B), i32(B)
@@ -103,7 +107,7 @@ class MultiStartMpc:
             self._P = f64(G, N + 1, no, 2)
             self.cand_merit, self.cand_defect, self.cand_margin = f64(B), f64(B), f64(B)
         self.solved_X = self.solved_U = None
-        self._warm = False
+        self._warm = self._fused_warm = False
         torch.cuda.synchronize(self.dev)
 
     # ------------------------------------------------------------------ lifetime
@@ -239,6 +243,191 @@ class MultiStartMpc:
         outer.wait_stream(self.stream)
         return self._result()
 
+    # ------------------------------------------------------------------ the fused control step (mpc_group_step_dev)
+    def _group_arrays(self):
+        """the group bookkeeping of the fused step, the members' flag words and the scratch words of the member solve, made on first use"""
+        if getattr(self, "ep_flags", None) is None:
+            torch, G, B = self._torch, self.G, self.B
+            f64 = dict(dtype=torch.float64, device=self.dev); i32 = dict(dtype=torch.int32, device=self.dev)
+            self.min_margin, self.ep_flags, self.ep_steps = torch.full((G,), float("inf"), **f64), torch.zeros(G, **i32), torch.zeros(G, **i32)
+            self.lost_steps, self.switched_steps = torch.zeros(G, **i32), torch.zeros(G, **i32)
+            self.member_flags, self._scratch_margin, self._scratch_steps = torch.zeros(B, **i32), torch.full((B,), float("inf"), **f64), torch.zeros(B, **i32)
+            p = lambda t: t.data_ptr()
+            self._out = _lib.GroupStepOut(winner=p(self.winner), best_key=p(self.cost), best_u0=p(self.u0), min_margin=p(self.min_margin), ep_flags=p(self.ep_flags),
+                                          ep_steps=p(self.ep_steps), lost=p(self.lost_steps), switched=p(self.switched_steps), member_x=p(self._x0),
+                                          member_obst=p(self._obst), member_goal=p(self._goal), member_flags=p(self.member_flags))
+
+    def restart(self):
+        """forget the closed loop: the next step / step_fused seeds every member again, and the fused step's bookkeeping starts over (margin +inf, flags, steps
+        and counters 0)"""
+        self._warm = self._fused_warm = False
+        if getattr(self, "ep_flags", None) is not None:
+            with self._torch.cuda.stream(self.stream):
+                self.min_margin.fill_(float("inf")); self._scratch_margin.fill_(float("inf"))
+                for t in (self.ep_flags, self.ep_steps, self.lost_steps, self.switched_steps, self.member_flags, self._scratch_steps):
+                    t.zero_()
+            self.stream.synchronize()
+
+    def step_fused(self, x, obst, goal, noise=None, randomness=0.1, vmax=2.0, margin_all=False):
+        """step() with everything behind the solve in ONE launch (mpc_group_step_dev) and the episode bookkeeping per group on the device: a control step is
+        the member solve (closed_loop_step_dev with flags = STEP_METRICS alone on the members' own flag words: members of a finished group idle) ->
+        [select_by="rollout": predict_dev on the G scenario rows, rollout_merit_dev on the members] -> the group tail: select, plant (x in place), obstacles
+        (obst in place, noise (G, n_obst, 2) standard normals as a contiguous float64 device tensor, or None), bookkeeping, next iterates, the members'
+        inputs.  The FIRST call (and the first after restart()) loads the members from x, obst, goal and seeds every member; every later call solves what
+        the last one left, so x, obst and goal must then be the tensors that call was given (step() and step_fused() are not to be mixed without a restart()
+        between them: step() does not maintain the members' inputs).  A group whose ep_flags bit 0 is set is neither solved nor
+        stepped.  Returns step()'s dict and the group bookkeeping: min_margin, ep_flags, ep_steps, lost_steps, switched_steps (G,)."""
+        torch = self._torch
+        for t in (x, obst, goal) + (() if noise is None else (noise,)):
+            if not (isinstance(t, torch.Tensor) and t.is_contiguous() and t.dtype == torch.float64 and t.is_cuda):
+                raise ValueError("step_fused works in place and without copies: x, obst, goal and noise are contiguous float64 device tensors")
+        check_group_shapes(self.G, self.n_obst, x, obst, goal)
+        if noise is not None and tuple(noise.shape) != (self.G, self.n_obst, 2):
+            raise ValueError(f"noise must be {(self.G, self.n_obst, 2)}, got {tuple(noise.shape)}")
+        self._group_arrays()
+        outer, ctx = self._on_stream()
+        m, G, K, B = self.inner, self.G, self.K, self.B
+        with ctx:
+            s = self.stream.cuda_stream
+            if not (self._warm and self._fused_warm):
+                self._load(x, obst, goal)
+                self.member_flags.copy_((self.ep_flags & 1).repeat_interleave(K))
+                self._seed(x, goal, False, s)
+                self._warm = self._fused_warm = True
+            m.closed_loop_step_dev(B, self._x0, self._obst, self._goal, self.X, self.U, self.cand_u0, self.cand_cost, self.cand_status, self.cand_iters,
+                                   flags=_lib.STEP_METRICS, min_margin=self._scratch_margin, ep_flags=self.member_flags, ep_steps=self._scratch_steps, stream=s)
+            by = self.cand_cost
+            if self.select_by == "rollout":
+                m.predict_dev(G, obst, self._P, stream=s)
+                m.rollout_merit_dev(B, x, self._P, goal, self.U, X=self.X, merit=self.cand_merit, defect=self.cand_defect, margin=self.cand_margin, members=K, stream=s)
+                by = self.cand_merit
+            _lib.check(_lib.lib().mpc_group_step_dev(m._h, G, K, by.data_ptr(), self.cand_status.data_ptr(), self.cand_u0.data_ptr(), self.margin,
+                                                     _lib.GROUP_MARGIN_ALL if margin_all else 0, x.data_ptr(), obst.data_ptr(), goal.data_ptr(),
+                                                     self.offsets.data_ptr(), None if noise is None else noise.data_ptr(), randomness, vmax,
+                                                     self.X.data_ptr(), self.U.data_ptr(), self._out, s))
+        outer.wait_stream(self.stream)
+        return dict(self._result(), min_margin=self.min_margin, ep_flags=self.ep_flags, ep_steps=self.ep_steps, lost_steps=self.lost_steps,
+                    switched_steps=self.switched_steps)
+
     def iterates(self):
         """the iterates of all members as they stand, (G, K, N + 1, 5) and (G, K, N, 2) device views"""
         return self.X.view(self.G, self.K, self.N + 1, 5), self.U.view(self.G, self.K, self.N, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- episodes of groups
+def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", n_obst=5, max_iter=400, random_move=True, first_seed=0,
+                      noise=None, sqp=None, r_safe=None, r_hit=None, active=None, solver=None):
+    """run_multistart_episodes' arguments, checked on the host before anything touches a device.  Returns dict(G, K, n_obst, x0 (G, 5), goal (G, 2), obst (the
+    array (G, n_obst, 4) or None), scenario (the name or None), offsets, margin, select_by, max_iter, noise (None, "reference", "torch" or the array), first_seed)."""
+    from .episodes import _episode_noise
+    off, margin, select_by = check_offsets(offsets), check_margin(incumbent_margin), check_select_by(select_by)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    if x0.ndim != 2 or x0.shape[1] != 5 or x0.shape[0] < 1:
+        raise ValueError(f"x0 must be (G, 5) with one row per group (G >= 1), got {x0.shape}")
+    G, K = x0.shape[0], int(off.shape[0])
+    try:
+        goal = np.ascontiguousarray(np.broadcast_to(np.asarray(goal, dtype=np.float64), (G, 2)))
+    except ValueError:
+        raise ValueError(f"goal must be (2,) or ({G}, 2), got {np.shape(goal)}") from None
+    scenario = obst if isinstance(obst, str) else None
+    if scenario is not None:
+        if scenario not in BatchedMpc.SCENARIOS:
+            raise ValueError(f"unknown scenario {scenario!r}: one of {sorted(BatchedMpc.SCENARIOS)}")
+        if isinstance(n_obst, bool) or int(n_obst) != n_obst or not 1 <= int(n_obst) <= 32:
+            raise ValueError(f"n_obst must be a whole number in 1 .. 32, got {n_obst!r}")
+        n_obst, obst = int(n_obst), None
+    else:
+        obst = np.ascontiguousarray(obst, dtype=np.float64)
+        if obst.ndim != 3 or obst.shape[0] != G or obst.shape[2] != 4 or not 1 <= obst.shape[1] <= 32:
+            raise ValueError(f"obst must be a scenario name or ({G}, n_obst, 4) with 1 .. 32 obstacles, got {obst.shape}")
+        n_obst = obst.shape[1]
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"max_iter must be a whole number >= 1, got {max_iter!r}")
+    if isinstance(first_seed, bool) or int(first_seed) != first_seed or not 0 <= int(first_seed) or int(first_seed) + G > 2 ** 32:
+        raise ValueError("first_seed .. first_seed + G - 1 must be numpy seeds in [0, 2^32)")
+    noise = _episode_noise(noise, scenario, 0, bool(random_move), int(max_iter), G, n_obst)
+    if sqp is not None and (not hasattr(sqp, "__len__") or len(sqp) != 2):
+        raise ValueError("sqp must be None or (max_iter, step_tol)")
+    for name, a in (("r_safe", r_safe), ("r_hit", r_hit)):
+        if a is not None:
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape not in ((G,), (G, n_obst)) or not np.isfinite(a).all() or not (a > 0.0).all():
+                raise ValueError(f"{name} must be ({G},) or ({G}, {n_obst}) finite radii > 0 (one row per group), got shape {a.shape}")
+    if active is not None and (np.asarray(active).shape != (G, n_obst) or np.asarray(active).dtype != np.bool_):
+        raise ValueError(f"active must be a bool array ({G}, {n_obst}) (one row per group), got {np.asarray(active).dtype} {np.asarray(active).shape}")
+    if solver is not None:
+        if not isinstance(solver, MultiStartMpc):
+            raise ValueError("solver must be a MultiStartMpc (the groups' own handle)")
+        if (solver.G, solver.n_obst) != (G, n_obst) or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin or solver.select_by != select_by:
+            raise ValueError(f"solver holds {solver.G} groups of {solver.n_obst} obstacles, offsets {solver.offsets_host.tolist()}, margin {solver.margin}, "
+                             f"select_by {solver.select_by!r}: not what this call asks for")
+    return dict(G=G, K=K, n_obst=n_obst, x0=x0, goal=goal, obst=obst, scenario=scenario, offsets=off, margin=margin, select_by=select_by, max_iter=int(max_iter),
+                noise=noise, first_seed=int(first_seed))
+
+
+def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True,
+                            first_seed=0, noise=None, sqp=None, r_safe=None, r_hit=None, active=None, margin_all=False, solver=None, device=0, **cfg):
+    """run_episodes for GROUPS: G closed-loop episodes of K = len(offsets) candidate iterates each, one MultiStartMpc.step_fused per control step (noise draw ->
+    member solve -> [predict, rollout merit] -> group tail), episode bookkeeping per group on the device.  x0 (G, 5), goal (2,) or (G, 2), obst (G, n_obst, 4)
+    -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): group s is then the reference's episode for np.random.seed(first_seed + s) (experiments.py:20-36), its
+    scenario draw and its noise stream produced on the device (mpc_generate_scenarios_dev, mpc_noise_init_dev, mpc_noise_draw_dev over the G scenario rows with
+    the GROUP flags: a finished group draws no more).  The plant starts from x0 as given.
+    noise: as run_episodes -- an array (>= max_iter, G, n_obst, 2), "reference" (the default with a scenario name), "torch" (the default with explicit
+    obstacle states); random_move=False: the obstacles draw nothing.  sqp (max_iter, step_tol), r_safe / r_hit ((G,) or (G, n_obst)), active (bool (G, n_obst))
+    with margin_all: per GROUP, as run_episodes takes them per instance (MultiStartMpc replicates them over the members).
+    A group that has reached its goal is neither solved nor stepped.  The loop ends as run_episodes' does: every 25 control steps the
+    done flag goes to pinned host memory behind an event and is looked at once that event has passed -- no stall, at most ~25 steps on idle groups.
+    solver: a caller's MultiStartMpc with the same groups, offsets, margin and select_by; it is restart()ed, and leaves with the features of this call switched
+    OFF again whether the call returns or raises (_HandleLease).  The arguments that need no device are checked before a handle is touched (episode_arguments).
+    Not offered: groups in run_seed_sweep (refill), PipelinedMpc, compaction, record / trace.
+    Returns dict(table (G, 6) = [hit, reached, min_margin, dist_to_goal, iters, out_of_bounds] (episodes.result_table), x_last (G, 5), steps_run, solves = the
+    member solves of running groups = K (sum of table[:, 4] + table[:, 1]), lost_steps (G,): control steps on which no member was eligible, switched_steps (G,):
+    control steps on which the winner was not member 0)."""
+    from .episodes import _HandleLease, _noise_source, result_table
+    from types import SimpleNamespace
+    a = episode_arguments(x0, goal, obst, offsets, incumbent_margin, select_by, n_obst, max_iter, random_move, first_seed, noise, sqp, r_safe, r_hit, active, solver)
+    import torch
+    G, K, no = a["G"], a["K"], a["n_obst"]
+    dev = torch.device("cuda", device if solver is None else solver.dev.index)
+    make = lambda: MultiStartMpc(N, no, Tf, scenarios=G, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"], **cfg)
+    with _HandleLease(solver, make) as lease:
+        ms = lease.m
+        lease.stream = ms.stream
+        if r_safe is not None or r_hit is not None:
+            lease.attach("set_instance_params", r_safe=r_safe, r_hit=r_hit)
+        if active is not None:
+            lease.attach("set_obstacle_mask", np.asarray(active))
+        if sqp is not None:
+            lease.attach("set_sqp", *sqp)
+        ms.restart()
+        with torch.cuda.stream(ms.stream):
+            s = ms.stream.cuda_stream
+            f64 = dict(dtype=torch.float64, device=dev)
+            x, dgoal = torch.from_numpy(a["x0"].copy()).to(dev), torch.from_numpy(a["goal"].copy()).to(dev)
+            if a["scenario"] is not None:
+                dobst = torch.zeros(G, no, 4, **f64)
+                ms.inner.generate_scenarios_dev(a["scenario"], G, dobst, seed0=a["first_seed"], stream=s)
+            else:
+                dobst = torch.from_numpy(a["obst"].copy()).to(dev)
+            ms._group_arrays()
+            rows = SimpleNamespace(rows=G, obst=dobst, flags=ms.ep_flags, f64=f64, gen_state=None, nbuf=None)
+            draw = _noise_source(torch, ms.inner, rows, a["noise"], a["scenario"], a["first_seed"], 0, s)
+            done_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            done_event = None
+            k = 0
+            while k < a["max_iter"]:
+                nz = draw(k)
+                ms.step_fused(x, dobst, dgoal, noise=None if nz is None else nz.contiguous(), margin_all=bool(margin_all) and active is not None)
+                k += 1
+                if done_event is not None and done_event.query():
+                    if int(done_host[0]) == 1:
+                        break
+                    done_event = None
+                if k % 25 == 0 and done_event is None:
+                    done_host.copy_((ms.ep_flags & 1).min().to(torch.int32).reshape(1), non_blocking=True)
+                    done_event = torch.cuda.Event(); done_event.record(ms.stream)
+            ms.stream.synchronize()
+            xl = x.cpu().numpy()
+            table = result_table(ms.ep_flags.cpu().numpy(), ms.min_margin.cpu().numpy(), xl, a["goal"], ms.ep_steps.cpu().numpy())
+            lost, switched = ms.lost_steps.cpu().numpy().copy(), ms.switched_steps.cpu().numpy().copy()
+    return dict(table=table, x_last=xl, steps_run=k, solves=K * int(table[:, 4].sum() + table[:, 1].sum()), lost_steps=lost, switched_steps=switched)

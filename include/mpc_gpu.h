@@ -317,6 +317,45 @@ int mpc_seed_guesses_dev(mpc_handle *h, int groups, int K, const double *d_x0, c
                          double *d_X, double *d_U, void *stream);
 int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, const int32_t *d_status, double incumbent_margin, int flags,
                         double *d_X, double *d_U, int32_t *d_winner, double *d_best_cost, double *d_best_u0, const double *d_u0, void *stream);
+/* MULTI-START, THE GROUP CONTROL STEP: everything a closed-loop control step of `groups` scenarios does BEHIND its solve launch, in one launch, episode
+ * bookkeeping included.  The solve in front of it is the ordinary launch over groups * K instances (member k of group g = instance g K + k); with
+ * select-by-rollout, mpc_predict_dev and mpc_rollout_merit_dev stand between the two.  Per group g whose ep_flags[g] bit 0 is clear, in this order:
+ *   1. SELECT by exactly the rule of mpc_select_best_dev on d_key[groups * K] (the reported cost, or the rollout merit), d_status and incumbent_margin:
+ *      out->winner[g], out->best_key[g], out->best_u0[g] = row winner of d_u0[groups * K][2] bit for bit, (0, 0) without a winner;
+ *   2. PLANT: d_x[g] <- F(d_x[g], best_u0[g]) in place (d_x[groups][5]; F the integrator of mpc_plant_step_dev);
+ *   3. OBSTACLES: d_obst[g] advanced in place (d_obst[groups][n_obst][4]) with mpc_obstacle_step_dev's arithmetic: d_noise[groups][n_obst][2] standard
+ *      normals or NULL, randomness, vmax; any obstacle count a handle can have (1 .. 32);
+ *   4. BOOKKEEPING, the rule of mpc_closed_loop_step_dev's MPC_STEP_METRICS on the NEW state and the MOVED obstacles: margin = min over the obstacles of
+ *      |x[0:2] - o[0:2]| - r_hit, r_hit = 1.2 or row g K of the per-instance table (mpc_set_instance_params); an obstacle absent under the mask of row g K
+ *      (mpc_set_obstacle_mask) does not count unless MPC_GROUP_MARGIN_ALL is given; min_margin[g] = min(min_margin[g], margin); ep_flags[g] bit 1 = outside
+ *      the arena, bit 2 = min_margin <= 0, bit 0 = within 0.15 of d_goal[g] -- otherwise ep_steps[g] += 1; out->lost[g] += 1 when no member was eligible,
+ *      out->switched[g] += 1 when winner > 0;
+ *   5. NEXT ITERATES: member 0 <- the winner's iterate shifted (mpc_shift_dev's rule: X[N] kept, U[N - 1] = 0); members 1 .. K - 1 <- the guess of
+ *      mpc_seed_guesses_dev for d_offsets[k] around the NEW d_x[g] and d_goal[g]; a group without a winner applied u = 0 and has member 0 seeded too, with
+ *      d_offsets[0].  There is no broadcast: the launch writes no word that it overwrites;
+ *   6. MEMBER INPUTS of the next solve: the new x[g], obst[g] and goal[g] into rows g K .. g K + K - 1 of out->member_x [groups * K][5], out->member_obst
+ *      [groups * K][n_obst][4], out->member_goal [groups * K][2], and out->member_flags[g K + k] = ep_flags[g] & 1.
+ * A group whose bit 0 is set on entry is IDLE: the launch reads its flag and writes none of its words.  It is not solved either when the solve launch is
+ * mpc_closed_loop_step_dev with flags = MPC_STEP_METRICS alone on out->member_flags and two scratch arrays of groups * K words (margin, steps): that launch
+ * idles the members whose flag is set and moves nothing; what it writes into the scratch words and member_flags of a running member is ignored, the group
+ * arrays are the record and this call rewrites member_flags.
+ * out: device pointers only, copied by the call; winner, min_margin (preset to +inf), ep_flags and ep_steps are mandatory, every other field may be NULL
+ * and is then not written.  The member arrays must not overlap the group arrays.  MPC_ERR_ARG (with a message, nothing launched): a null handle or null
+ * mandatory pointer (d_key, d_status, d_u0, d_x, d_obst, d_goal, d_offsets, d_X, d_U, out), K outside 1 .. 64, groups < 0 or groups * K > max_batch,
+ * incumbent_margin outside [0, 1), unknown flags, a per-instance feature that covers fewer than groups * K instances.  groups = 0 does nothing. */
+#define MPC_GROUP_MARGIN_ALL 1
+typedef struct mpc_group_step_out {
+    int32_t *winner;                                           /* [groups] */
+    double *best_key, *best_u0;                                /* [groups], [groups][2] */
+    double *min_margin;                                        /* [groups] */
+    int32_t *ep_flags, *ep_steps;                              /* [groups] */
+    int32_t *lost, *switched;                                  /* [groups] */
+    double *member_x, *member_obst, *member_goal;              /* [groups * K] rows */
+    int32_t *member_flags;                                     /* [groups * K] */
+} mpc_group_step_out;
+int mpc_group_step_dev(mpc_handle *h, int groups, int K, const double *d_key, const int32_t *d_status, const double *d_u0, double incumbent_margin,
+                       int flags, double *d_x, double *d_obst, const double *d_goal, const double *d_offsets, const double *d_noise, double randomness,
+                       double vmax, double *d_X, double *d_U, const mpc_group_step_out *out, void *stream);
 /* ROLLOUT MERIT: score a plan by simulating its inputs.  The cost a solve reports is the NLP objective at the iterate (X + dX, U + dU), whose states follow
  * the linearisation about the guess, not the plant; one RTI iteration from a poor guess that pair is far from dynamically consistent, and its cost cannot be
  * compared with that of a converged one.  This call rolls U out from x0 -- X^r_0 = x0, X^r_{i+1} = F(X^r_i, U_i), F the integrator of mpc_plant_step_dev
