@@ -961,6 +961,113 @@ __global__ __launch_bounds__(64) void refill_apply_ext_kernel(int slots, int n_o
                                     X, U, min_margin, ep_flags, ep_steps, state, noise, slot_seed, res_f, res_i, ex);
 }
 
+// GROUP REFILL (mpc_group_refill_dev): the refill for multi-start groups.  A slot is a group of K members; refill_decide_kernel runs
+// unchanged on the group words, and this kernel applies its decision with one wavefront per group, four groups per workgroup as in group_step_kernel:
+//   keep   (the episode runs on)         the wavefront leaves: none of the group's or its members' words is written;
+//   park   (finished, slot_seed >= 0)    res_f[seed] = min_margin, x[5]; res_i[seed] = ep_flags, ep_steps, lost, switched;
+//   drain  (finished, no seed left)      slot_seed = -1, ep_flags |= 1, member_flags = 1 (the member solve idles them) and nothing else;
+//   start k                              lane 0 seeds the generator and takes the scenario's draws (seed_scenario: mpc_noise_init_dev's state, the values of
+//                                        mpc_generate_scenarios_dev) -- the one serial part, ~2000 dependent integer steps --; the draws go to the lanes by
+//                                        broadcasts, obstacle j to lane j; x = the start row as given, the goal row, the bookkeeping of a new episode; members
+//                                        0 .. K - 1 seeded with seed_stage, a stage per lane, sin and cos formed once per lane; x, obst, goal into the K member
+//                                        rows, member_flags = 0.  winner, best_key and best_u0 are the group step's and are not written.
+// HAZARDS: the kernel overwrites the words it parks.  As in group_step_kernel a wavefront issues every load of its group's words above the wait below and
+// stores only behind it; it writes words of its own group, its own members and its own seed (seed indices are handed out once), and reads none that another
+// wavefront writes.  No LDS, no atomics, no workgroup barrier.  No noise is drawn: noise_draw_kernel follows on the group rows with the group flags.
+struct GroupRefillArgs {
+    int groups, K, N, n_obst, scenario, per_seed;
+    unsigned seed_first;
+    double x_lo, x_hi, y_lo, y_hi, v_max, edge;
+    const int32_t *assign; const double *start, *goal_src, *offsets;
+    double *x, *obst, *goal, *X, *U, *min_margin;
+    int32_t *ep_flags, *ep_steps, *lost, *switched;
+    unsigned *state; int32_t *slot_seed;
+    double *res_f; int32_t *res_i;
+    double *member_x, *member_obst, *member_goal; int32_t *member_flags;
+};
+constexpr int kGroupRefillMaxObst = 32;                        // MPC_MAX_OBST: the scenario's draws of one group, held by lane 0 until they are dealt out
+
+__global__ __launch_bounds__(kGroupThreads) void group_refill_apply_kernel(const GroupRefillArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * kGroupWaves + (threadIdx.x >> 6));
+    if (g >= a.groups) return;                                  // (wave-uniform, like every branch around a cross-lane step below)
+    const int as = __builtin_amdgcn_readfirstlane(a.assign[g]);
+    if (as == kRefillKeep) return;
+    const int K = a.K, N = a.N, no = a.n_obst;
+    const size_t base = (size_t)g * K;
+    // ---- every read of the group's words, and of the rows a start needs ----
+    const int old = __builtin_amdgcn_readfirstlane(a.slot_seed[g]);
+    const double mm0 = a.min_margin[g];
+    const int fl0 = a.ep_flags[g], steps0 = a.ep_steps[g], lost0 = a.lost[g], sw0 = a.switched[g];
+    double xg[5];
+#pragma unroll
+    for (int c = 0; c < 5; c++) xg[c] = a.x[(size_t)g * 5 + c];
+    double xs[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, gx = 0.0, gy = 0.0;
+    if (as >= 0) {
+        const size_t row = a.per_seed ? (size_t)as : 0;
+#pragma unroll
+        for (int c = 0; c < 5; c++) xs[c] = a.start[row * 5 + c];
+        gx = a.goal_src[row * 2]; gy = a.goal_src[row * 2 + 1];
+    }
+    const double off = lane < K ? a.offsets[lane] : 0.0;
+    // ---- every load of the group's words has returned before the first store is issued ----
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (old >= 0) {                                             // park: the raw words of the result row; the table's columns are formed on the host
+        const double xo = lane == 0 ? xg[0] : (lane == 1 ? xg[1] : (lane == 2 ? xg[2] : (lane == 3 ? xg[3] : xg[4])));
+        if (lane < 5) a.res_f[(size_t)old * 6 + 1 + lane] = xo;
+        if (lane == 0) {
+            a.res_f[(size_t)old * 6] = mm0;
+            int32_t *ri = a.res_i + (size_t)old * 4;
+            ri[0] = fl0; ri[1] = steps0; ri[2] = lost0; ri[3] = sw0;
+        }
+    }
+    if (as == kRefillDrain) {                                   // the sweep is exhausted: the group idles like one that has reached its goal
+        if (lane == 0) { a.slot_seed[g] = -1; a.ep_flags[g] = fl0 | 1; }
+        if (lane < K) a.member_flags[base + lane] = 1;
+        return;
+    }
+    // ---- start seed index `as`: the generator and the scenario's draws on lane 0, then obstacle j to lane j ----
+    double draws[kGroupRefillMaxObst * 4] = {};
+    if (lane == 0)
+        seed_scenario(a.state + (size_t)g * kNoiseStateWords, draws, a.seed_first + (unsigned)as, no, a.scenario, a.x_lo, a.x_hi, a.y_lo, a.y_hi, a.v_max, a.edge);
+    double ob[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < no; j++) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) { const double v = __shfl(draws[j * 4 + c], 0); if (lane == j) ob[c] = v; }
+    }
+    const double xc = lane == 0 ? xs[0] : (lane == 1 ? xs[1] : (lane == 2 ? xs[2] : (lane == 3 ? xs[3] : xs[4])));      // lane c < 5: entry c of the start row
+    if (lane < 5) a.x[(size_t)g * 5 + lane] = xc;
+    if (lane < 2) a.goal[(size_t)g * 2 + lane] = lane ? gy : gx;
+    if (lane < no) { double *o = a.obst + ((size_t)g * no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+    if (lane == 0) {
+        a.min_margin[g] = INFINITY; a.ep_flags[g] = 0; a.ep_steps[g] = 0; a.lost[g] = 0; a.switched[g] = 0;
+        a.slot_seed[g] = as;
+    }
+    if (lane < K) a.member_flags[base + lane] = 0;
+    // ---- the members' iterates (seed_guesses_kernel's family, keep_first = 0) and inputs ----
+    const double dx = gx - xs[0], dy = gy - xs[1];
+    const double L = sqrt(dx * dx + dy * dy);
+    const double s = (double)lane / (double)N;
+    const double sn = sin(kPi * s), cs = cos(kPi * s);          // once per lane, not once per member
+    for (int k = 0; k < K; k++) {
+        const double ak = __shfl(off, k);
+        double xi[5];
+        seed_stage(xs, dx, dy, L, ak, lane, s, sn, cs, xi);
+        if (lane <= N) {
+            double *Xi = a.X + ((base + k) * (size_t)(N + 1) + lane) * 5;
+#pragma unroll
+            for (int c = 0; c < 5; c++) Xi[c] = xi[c];
+            if (lane < N) { double *Ui = a.U + ((base + k) * (size_t)N + lane) * 2; Ui[0] = 0.0; Ui[1] = 0.0; }
+        }
+        if (lane < 5) a.member_x[(base + k) * 5 + lane] = xc;
+        if (lane < 2) a.member_goal[(base + k) * 2 + lane] = lane ? gy : gx;
+        if (lane < no) { double *o = a.member_obst + ((base + k) * (size_t)no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+    }
+}
+
 // RING FILL (mpc_episode_ring_fill_dev), one thread per ring entry e.  With handed = cursor[0] (the seed indices started so far) thread e owns the one index k in
 // [handed, handed + capacity) with k % capacity == e; if that index exists and the entry does not hold it yet, the thread seeds seed_first + k there -- refill_apply's
 // own sequence (seed_scenario), so the state is mpc_noise_init_dev's -- and writes the tag LAST.  An entry is overwritten only by k + capacity, which is owned only once

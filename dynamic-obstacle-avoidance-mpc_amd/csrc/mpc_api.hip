@@ -1203,6 +1203,44 @@ int mpc_episode_refill_dev(mpc_handle *h, int slots, int scenario, unsigned seed
     return MPC_OK;
 }
 
+static_assert(mpc::kGroupRefillMaxObst == MPC_MAX_OBST, "the kernel holds one group's scenario draws for the largest handle");
+int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigned seed_first, int seed_count, int max_steps, const double *box,
+                         const double *d_start, const double *d_goal_rows, int per_seed, const double *d_offsets, const mpc_group_refill_arrays *a,
+                         void *stream)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (K < 1 || K > 64) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: K must be in [1, 64] (one member per lane of the group's wavefront)");
+    if (groups < 1 || (long long)groups * K > h->max_batch) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: groups < 1 or groups * K > max_batch");
+    if (scenario < 0 || scenario > 2) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: scenario must be 0 (RANDOM), 1 (CENTER) or 2 (EDGE)");
+    if (seed_count < 0) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: seed_count must be >= 0");
+    if (max_steps < 1) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: max_steps must be >= 1");
+    if (per_seed != 0 && per_seed != 1) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: per_seed must be 0 or 1");
+    if (!box || !d_start || !d_goal_rows || !d_offsets || !a) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: null box, start rows, goal rows, offsets or arrays");
+    if (!a->x || !a->obst || !a->goal || !a->X || !a->U || !a->min_margin || !a->ep_flags || !a->ep_steps || !a->lost || !a->switched || !a->state)
+        return fail(MPC_ERR_ARG, "mpc_group_refill_dev: null group array (x, obst, goal, X, U, min_margin, ep_flags, ep_steps, lost, switched, state)");
+    if (!a->slot_seed || !a->cursor || !a->res_f || !a->res_i) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: null slot_seed, cursor or result array");
+    if (!a->member_x || !a->member_obst || !a->member_goal || !a->member_flags) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: null member array");
+    if (h->rt_on) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: per-seed tables and the status log (mpc_set_refill_tables_dev) are not offered for groups");
+    if (h->ring_cap) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: the ring of seeded episodes (mpc_episode_ring_dev) is not offered for groups");
+    if (h->trace_rows) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: per-seed trajectories (mpc_episode_trace_set_dev) are not offered for groups");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = own(h, &h->d_refill_assign, (size_t)h->max_batch); if (rc) return rc;
+    hipStream_t s = pick(h, stream);
+    hipLaunchKernelGGL(mpc::refill_decide_kernel, dim3(1), dim3(mpc::kRefillThreads), 0, s, groups, seed_count, max_steps, a->ep_flags, a->ep_steps,
+                       h->d_refill_assign, a->cursor);
+    mpc::GroupRefillArgs ga;
+    ga.groups = groups; ga.K = K; ga.N = h->cfg.N; ga.n_obst = h->cfg.n_obst; ga.scenario = scenario; ga.per_seed = per_seed; ga.seed_first = seed_first;
+    ga.x_lo = box[0]; ga.x_hi = box[1]; ga.y_lo = box[2]; ga.y_hi = box[3]; ga.v_max = box[4]; ga.edge = box[5];
+    ga.assign = h->d_refill_assign; ga.start = d_start; ga.goal_src = d_goal_rows; ga.offsets = d_offsets;
+    ga.x = a->x; ga.obst = a->obst; ga.goal = a->goal; ga.X = a->X; ga.U = a->U; ga.min_margin = a->min_margin;
+    ga.ep_flags = a->ep_flags; ga.ep_steps = a->ep_steps; ga.lost = a->lost; ga.switched = a->switched;
+    ga.state = a->state; ga.slot_seed = a->slot_seed; ga.res_f = a->res_f; ga.res_i = a->res_i;
+    ga.member_x = a->member_x; ga.member_obst = a->member_obst; ga.member_goal = a->member_goal; ga.member_flags = a->member_flags;
+    hipLaunchKernelGGL(mpc::group_refill_apply_kernel, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, ga);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 int mpc_set_refill_tables_dev(mpc_handle *h, const mpc_refill_tables *t)
 {
     if (!h) return fail(MPC_ERR_ARG, "null handle");

@@ -70,6 +70,13 @@ class GroupStepOut(C.Structure):
                                    "member_x", "member_obst", "member_goal", "member_flags")]
 
 
+class GroupRefillArrays(C.Structure):
+    """Mirror of `struct mpc_group_refill_arrays` (include/mpc_gpu.h): device pointers only -- what the refill for groups reads and writes per group, per
+    member and per seed."""
+    _fields_ = [(n, _vp) for n in ("x", "obst", "goal", "X", "U", "min_margin", "ep_flags", "ep_steps", "lost", "switched", "state", "slot_seed", "cursor",
+                                   "res_f", "res_i", "member_x", "member_obst", "member_goal", "member_flags")]
+
+
 _cfgp = C.POINTER(MpcConfig)
 SYMBOLS = {
     "mpc_abi_version": (C.c_int, []),
@@ -136,6 +143,8 @@ SYMBOLS = {
     "mpc_noise_init_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, _vp, _vp]),
     "mpc_noise_draw_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_episode_refill_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 15),
+    "mpc_group_refill_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp,
+                                       C.POINTER(GroupRefillArrays), _vp]),
     "mpc_set_refill_tables_dev": (C.c_int, [_vp, C.POINTER(RefillTables)]),
     "mpc_episode_status_log_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mpc_episode_ring_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),

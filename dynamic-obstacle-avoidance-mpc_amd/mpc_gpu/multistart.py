@@ -15,8 +15,9 @@ Nothing leaves the device between them: torch replicates the group inputs and ca
 
 The CLOSED LOOP has two forms.  step() composes a control step from the entry points above and the plant / obstacle / shift / seed launches.  step_fused()
 runs the member solve and then ONE launch, mpc_group_step_dev (select, plant, obstacles, episode bookkeeping per group, next iterates, the members' inputs;
-DESIGN.md section 4m), and run_multistart_episodes drives it to the reference's result table.  run_seed_sweep and PipelinedMpc do not know about groups
-(DESIGN.md section 8)."""
+DESIGN.md section 4m), and run_multistart_episodes drives it to the reference's result table.  run_multistart_sweep streams more seeds than there are
+groups through the groups: a finished group starts the next seed on the device (mpc_group_refill_dev).  PipelinedMpc does not know
+about groups."""
 import numpy as np
 
 from . import _lib
@@ -268,6 +269,13 @@ class MultiStartMpc:
                     t.zero_()
             self.stream.synchronize()
 
+    def members_loaded(self):
+        """say that the members ARE loaded: something else (mpc_group_refill_dev, run_multistart_sweep) has written every member's iterate, the replicated
+        member inputs and member_flags on the device, so the next step_fused solves what it finds instead of loading and seeding the members from its
+        arguments.  restart() takes it back."""
+        self._group_arrays()
+        self._warm = self._fused_warm = True
+
     def step_fused(self, x, obst, goal, noise=None, randomness=0.1, vmax=2.0, margin_all=False):
         """step() with everything behind the solve in ONE launch (mpc_group_step_dev) and the episode bookkeeping per group on the device: a control step is
         the member solve (closed_loop_step_dev with flags = STEP_METRICS alone on the members' own flag words: members of a finished group idle) ->
@@ -275,7 +283,7 @@ class MultiStartMpc:
         (obst in place, noise (G, n_obst, 2) standard normals as a contiguous float64 device tensor, or None), bookkeeping, next iterates, the members'
         inputs.  The FIRST call (and the first after restart()) loads the members from x, obst, goal and seeds every member; every later call solves what
         the last one left, so x, obst and goal must then be the tensors that call was given (step() and step_fused() are not to be mixed without a restart()
-        between them: step() does not maintain the members' inputs).  A group whose ep_flags bit 0 is set is neither solved nor
+        between them: step() does not maintain the members' inputs; members_loaded() in front of the first call skips its load).  A group whose ep_flags bit 0 is set is neither solved nor
         stepped.  Returns step()'s dict and the group bookkeeping: min_margin, ep_flags, ep_steps, lost_steps, switched_steps (G,)."""
         torch = self._torch
         for t in (x, obst, goal) + (() if noise is None else (noise,)):
@@ -379,7 +387,8 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
     done flag goes to pinned host memory behind an event and is looked at once that event has passed -- no stall, at most ~25 steps on idle groups.
     solver: a caller's MultiStartMpc with the same groups, offsets, margin and select_by; it is restart()ed, and leaves with the features of this call switched
     OFF again whether the call returns or raises (_HandleLease).  The arguments that need no device are checked before a handle is touched (episode_arguments).
-    Not offered: groups in run_seed_sweep (refill), PipelinedMpc, compaction, record / trace.
+    Not offered: PipelinedMpc, compaction, record / trace.  More seeds than groups, or groups that do not idle once their episode has
+    ended: run_multistart_sweep (the refill for groups).
     Returns dict(table (G, 6) = [hit, reached, min_margin, dist_to_goal, iters, out_of_bounds] (episodes.result_table), x_last (G, 5), steps_run, solves = the
     member solves of running groups = K (sum of table[:, 4] + table[:, 1]), lost_steps (G,): control steps on which no member was eligible, switched_steps (G,):
     control steps on which the winner was not member 0)."""
@@ -431,3 +440,133 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
             table = result_table(ms.ep_flags.cpu().numpy(), ms.min_margin.cpu().numpy(), xl, a["goal"], ms.ep_steps.cpu().numpy())
             lost, switched = ms.lost_steps.cpu().numpy().copy(), ms.switched_steps.cpu().numpy().copy()
     return dict(table=table, x_last=xl, steps_run=k, solves=K * int(table[:, 4].sum() + table[:, 1].sum()), lost_steps=lost, switched_steps=switched)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- seed sweeps of groups
+_SWEEP_NOT_OFFERED = ("r_safe", "r_hit", "W", "We", "active", "margin_all", "bounds", "status_log", "ring", "ring_every", "trace", "trace_pred", "trace_max_bytes",
+                      "record", "noise", "seed", "first_seed", "compact_from")
+
+
+def sweep_arguments(start, goal, scenario, seeds, slots, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", n_obst=5, max_iter=400, sqp=None,
+                    poll_every=25, solver=None):
+    """run_multistart_sweep's arguments, checked on the host before anything touches a device.  Returns dict(first, count, start (rows, 5), goal (rows, 2),
+    per_seed, S = the group slots used, K, n_obst, offsets, margin, select_by, max_iter, poll_every, bound = the control steps the loop launches at most)."""
+    from .episodes import _sweep_arguments
+    off, margin, select_by = check_offsets(offsets), check_margin(incumbent_margin), check_select_by(select_by)
+    first, count, start, goal, per_seed = _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every)
+    if isinstance(n_obst, bool) or int(n_obst) != n_obst or not 1 <= int(n_obst) <= 32:
+        raise ValueError(f"n_obst must be a whole number in 1 .. 32, got {n_obst!r}")
+    if sqp is not None and (not hasattr(sqp, "__len__") or len(sqp) != 2):
+        raise ValueError("sqp must be None or (max_iter, step_tol)")
+    S, K = min(int(slots), count), int(off.shape[0])
+    if solver is not None:
+        if not isinstance(solver, MultiStartMpc):
+            raise ValueError("solver must be a MultiStartMpc (the groups' own handle)")
+        if solver.G != S or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin or solver.select_by != select_by:
+            raise ValueError(f"solver holds {solver.G} groups, offsets {solver.offsets_host.tolist()}, margin {solver.margin}, select_by {solver.select_by!r}: "
+                             f"this call asks for {S} group slots, offsets {off.tolist()}, margin {margin}, select_by {select_by!r}")
+        n_obst = solver.n_obst
+    return dict(first=first, count=count, start=start, goal=goal, per_seed=per_seed, S=S, K=K, n_obst=int(n_obst), offsets=off, margin=margin, select_by=select_by,
+                max_iter=int(max_iter), poll_every=int(poll_every), bound=-(-count // S) * int(max_iter) + int(poll_every))
+
+
+def _sweep_state(torch, ms, a, scenario, random_move=True):
+    """the device state of a sweep of groups on the MultiStartMpc `ms` (restart()ed), on the current stream: the start and goal rows, the group rows x, obst,
+    goal, the generator states and the noise they draw into (nbuf; None: the obstacles draw nothing), slot_seed, cursor and the result rows of a["count"]
+    seeds, all preset as the first call of a sweep wants them (every group "finished" and without a seed: the first refill fills them all; the members
+    count as loaded); `refill(stream)` is one mpc_group_refill_dev call on them and the handle's own group and member arrays.  a: sweep_arguments' dict."""
+    from types import SimpleNamespace
+    S, no, count, dev = a["S"], ms.n_obst, a["count"], ms.dev
+    f64 = dict(dtype=torch.float64, device=dev); i32 = dict(dtype=torch.int32, device=dev)
+    st = SimpleNamespace(start_rows=torch.from_numpy(a["start"]).to(dev), goal_rows=torch.from_numpy(a["goal"]).to(dev), x=torch.zeros(S, 5, **f64),
+                         obst=torch.zeros(S, no, 4, **f64), goal=torch.zeros(S, 2, **f64), state=torch.zeros(S, _lib.lib().mpc_noise_state_words(), **i32),
+                         nbuf=torch.zeros(S, no, 2, **f64) if random_move else None, slot_seed=torch.full((S,), -1, **i32), cursor=torch.zeros(2, **i32),
+                         res_f=torch.full((count, 6), float("nan"), **f64), res_i=torch.full((count, 4), -1, **i32), box=BatchedMpc._scenario_box())
+    ms.members_loaded()
+    ms.ep_flags.fill_(1); ms.member_flags.fill_(1)
+    p = lambda t: t.data_ptr()
+    st.arrays = _lib.GroupRefillArrays(x=p(st.x), obst=p(st.obst), goal=p(st.goal), X=p(ms.X), U=p(ms.U), min_margin=p(ms.min_margin), ep_flags=p(ms.ep_flags),
+                                       ep_steps=p(ms.ep_steps), lost=p(ms.lost_steps), switched=p(ms.switched_steps), state=p(st.state), slot_seed=p(st.slot_seed),
+                                       cursor=p(st.cursor), res_f=p(st.res_f), res_i=p(st.res_i), member_x=p(ms._x0), member_obst=p(ms._obst),
+                                       member_goal=p(ms._goal), member_flags=p(ms.member_flags))
+    st.refill = lambda stream: _lib.check(_lib.lib().mpc_group_refill_dev(ms.inner._h, S, ms.K, BatchedMpc.SCENARIOS[scenario], a["first"], count, a["max_iter"],
+                                                                          st.box.ctypes.data, p(st.start_rows), p(st.goal_rows), 1 if a["per_seed"] else 0,
+                                                                          p(ms.offsets), st.arrays, stream))
+    return st
+
+
+def run_multistart_sweep(start, goal, scenario, seeds, slots, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", N=20, Tf=2.0, n_obst=5, max_iter=400,
+                         random_move=True, sqp=None, poll_every=25, solver=None, device=0, **cfg):
+    """run_seed_sweep for GROUPS: the seeds stream through min(slots, count) GROUP slots of K = len(offsets) members each, and a group whose episode has ended
+    (goal reached, or max_iter control steps spent) starts the next seed on the device, in front of the next member solve (mpc_group_refill_dev: no host
+    read, no gather; a finished group does not idle in its K wavefront slots while seeds are left).  Seed index k is group k of
+    run_multistart_episodes(start rows, goal, scenario, first_seed=first, ...) on ONE batch of `count` groups: the same scenario draw, noise stream, guesses
+    and control steps -- the rows are those of that batch to the rounding of the wavefront sums (three member solves share a wavefront).
+    scenario, seeds, start (5,) or (count, 5), goal (2,) or (count, 2), poll_every: as run_seed_sweep.  offsets, incumbent_margin, select_by, sqp, random_move:
+    as run_multistart_episodes.  One control step is refill -> poll copy -> noise draw on the group rows -> member solve -> [predict, rollout merit] -> group
+    tail (MultiStartMpc.step_fused on members that are already loaded).  The loop ends as run_seed_sweep's does and launches at most
+    ceil(count / S) * max_iter + poll_every control steps whatever the device returns.
+    solver: a caller's MultiStartMpc with min(slots, count) groups and the same offsets, margin and select_by; it is restart()ed on entry and on exit, and
+    leaves with the SQP setting of this call switched OFF again whether the call returns or raises (_HandleLease).
+    Not offered (TypeError, as run_seed_sweep answers `record`): per-seed feature tables (r_safe, r_hit, W, We, active, bounds), status_log, ring, trace.
+    Returns dict(table (count, 6), x_last (count, 5), steps_run, solves = K (sum of table[:, 4] + table[:, 1]), lost_steps (count,), switched_steps (count,),
+    schedule): table as episodes.result_table builds it; schedule (count, 2) = group slot and control step at which each seed started (poll_every = 1; None
+    otherwise) = refill_schedule's slot / start on the groups' episode lengths."""
+    not_offered = sorted(set(cfg) & set(_SWEEP_NOT_OFFERED))
+    if not_offered:
+        raise TypeError(f"run_multistart_sweep has no argument {not_offered[0]!r}: per-seed feature tables, the status log, the ring and the trace are "
+                        "run_seed_sweep's, and a batch's arguments are run_multistart_episodes'")
+    a = sweep_arguments(start, goal, scenario, seeds, slots, offsets, incumbent_margin, select_by, n_obst, max_iter, sqp, poll_every, solver)
+    from .episodes import _HandleLease, result_table
+    import torch
+    S, K, count, no, poll = a["S"], a["K"], a["count"], a["n_obst"], a["poll_every"]
+    make = lambda: MultiStartMpc(N, no, Tf, scenarios=S, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"], **cfg)
+    with _HandleLease(solver, make) as lease:
+        ms = lease.m
+        lease.stream = ms.stream
+        if sqp is not None:
+            lease.attach("set_sqp", *sqp)
+        ms.restart()
+        try:
+            with torch.cuda.stream(ms.stream):
+                s = ms.stream.cuda_stream
+                st = _sweep_state(torch, ms, a, scenario, random_move)
+                x, dobst, dgoal, nbuf, slot_seed, cursor = st.x, st.obst, st.goal, st.nbuf, st.slot_seed, st.cursor
+                schedule = np.full((count, 2), -1, dtype=np.int64) if poll == 1 else None
+                seen = np.full(S, -1, dtype=np.int64)
+                live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
+                live_event = None
+                k = 0
+                while True:
+                    st.refill(s)
+                    if poll == 1:
+                        now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
+                        new = (now != seen) & (now >= 0)
+                        schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
+                        seen = now
+                        if int(cursor[1].item()) == 0:
+                            break
+                    elif k % poll == 0:      # the count of the poll before this one (episodes._sweep_loop: the host stays at most two polls ahead of the device)
+                        if live_event is not None:
+                            live_event.synchronize()
+                            if int(live_host[0]) == 0:
+                                break
+                        live_host.copy_(cursor[1:2], non_blocking=True)
+                        live_event = torch.cuda.Event(); live_event.record(ms.stream)
+                    if k >= a["bound"]:
+                        break
+                    if nbuf is not None:
+                        ms.inner.noise_draw_dev(S, st.state, nbuf, ep_flags=ms.ep_flags, stream=s)
+                    ms.step_fused(x, dobst, dgoal, noise=nbuf)
+                    k += 1
+                ms.stream.synchronize()
+                left = int(cursor[1].item())
+                ri, rf = st.res_i.cpu().numpy(), st.res_f.cpu().numpy()
+                if left != 0 or (ri[:, 0] < 0).any():
+                    raise _lib.MpcError(f"the sweep did not drain within {a['bound']} control steps ({left} groups live, {int((ri[:, 0] < 0).sum())} rows not parked)")
+        finally:
+            ms.restart()
+    xl = np.ascontiguousarray(rf[:, 1:6])
+    table = result_table(ri[:, 0], rf[:, 0], xl, np.ascontiguousarray(np.broadcast_to(a["goal"], (count, 2)), dtype=np.float64), ri[:, 1])
+    return dict(table=table, x_last=xl, steps_run=k, solves=K * int(table[:, 4].sum() + table[:, 1].sum()), lost_steps=ri[:, 2].copy(), switched_steps=ri[:, 3].copy(),
+                schedule=schedule)

@@ -516,6 +516,49 @@ int mpc_episode_trace_set_dev(mpc_handle *h, int rows, int max_steps, const mpc_
 int mpc_episode_trace_dev(mpc_handle *h, int slots, int phase, const int32_t *d_slot_seed, const double *d_x0, const double *d_obst, const double *d_X,
                           const double *d_u0, const int32_t *d_status, const int32_t *d_iters, const int32_t *d_ep_flags, const int32_t *d_ep_steps,
                           void *stream);
+/* SEED SWEEPS OF MULTI-START GROUPS: the refill for groups.  A sweep of groups streams seed indices 0 .. seed_count-1 through a fixed number of GROUP slots
+ * -- a slot is a group of K members, member k of group g = instance g K + k, the layout of mpc_group_step_dev -- and a group whose episode has ended
+ * starts the next seed on the device.  Call this once per control step IN FRONT OF the member solve, on the solve's stream, with the arrays the solve and
+ * mpc_group_step_dev take.  The rule is mpc_episode_refill_dev's (experiments.py:20-36: seed after seed, each until its goal is reached or max_steps
+ * control steps are spent), per group:
+ *   DECIDE: mpc_episode_refill_dev's deciding launch, unchanged, on the group words a->ep_flags[groups] and a->ep_steps[groups].  A group is FINISHED when
+ *     its bit 0 is set or ep_steps >= max_steps; the seed indices not started yet go to the finished groups in ASCENDING GROUP ORDER; no atomics.
+ *     a->cursor[0] = seed indices handed out so far, a->cursor[1] = groups that run after this call (poll it; 0 = the sweep is over, every row parked).
+ *   APPLY, one wavefront per group, by what the decision handed the group:
+ *     - KEEP (not finished): none of the group's or its members' words is written;
+ *     - PARK (every finished group with slot_seed[g] >= 0): a->res_f[seed][6] = min_margin, x[5] and a->res_i[seed][4] = ep_flags, ep_steps, lost, switched;
+ *     - DRAIN (finished, no seed left): slot_seed[g] = -1, ep_flags[g] |= 1, member_flags[g K .. g K + K - 1] = 1 -- the member solve idles them -- and
+ *       nothing else;
+ *     - START seed index k: the generator seeded with seed_first + k into a->state[g] (the layout and the state of mpc_noise_init_dev) and the scenario's
+ *       uniform draws taken from it into a->obst[g] (the values of mpc_generate_scenarios_dev); x[g] = the start row AS GIVEN (there is no alias switch);
+ *       goal[g] = the goal row; min_margin = +inf, ep_flags = ep_steps = lost = switched = 0, slot_seed = k; members 0 .. K - 1 of a->X and a->U = the guess
+ *       family of mpc_seed_guesses_dev (keep_first = 0) for d_offsets around x[g] and goal[g]; x[g], obst[g], goal[g] into the K member rows of
+ *       a->member_x, a->member_obst, a->member_goal; member_flags = 0.  The selection's outputs (winner, best_key, best_u0) are not this call's.
+ * A wavefront reads every word it parks before it stores anything, and writes only words of its own group, its own members or its own seed.  No noise is
+ * drawn: mpc_noise_draw_dev on a->state with the group flags follows, as in a batch of groups.
+ * d_start [rows][5], d_goal_rows [rows][2]: rows = 1 (per_seed 0) or seed_count (per_seed 1, row k for index k).  box: as mpc_generate_scenarios_dev.
+ * First call of a sweep: slot_seed = -1, ep_flags = 1, member_flags = 1, cursor = {0, 0} -- every group is then filled by the same code.  Two launches; the
+ * decision is handed over in words of the handle, so consecutive calls on one handle belong on one stream.
+ * NOT OFFERED for groups, and refused rather than ignored: a handle with per-seed tables or a status log (mpc_set_refill_tables_dev), a ring
+ * (mpc_episode_ring_dev) or a trace (mpc_episode_trace_set_dev) attached.
+ * MPC_ERR_ARG (with a message, nothing launched): a null handle or a null pointer (every argument and every field of `a` is mandatory), K outside 1 .. 64,
+ * groups < 1 or groups * K > max_batch, seed_count < 0, max_steps < 1, scenario outside 0 .. 2, per_seed outside {0, 1}.
+ * a: device pointers only, copied by the call. */
+typedef struct mpc_group_refill_arrays {
+    double *x, *obst, *goal;                                   /* [groups][5], [groups][n_obst][4], [groups][2] */
+    double *X, *U;                                             /* [groups * K][N + 1][5], [groups * K][N][2] */
+    double *min_margin;                                        /* [groups] */
+    int32_t *ep_flags, *ep_steps, *lost, *switched;            /* [groups] */
+    uint32_t *state;                                           /* [groups][mpc_noise_state_words()] */
+    int32_t *slot_seed, *cursor;                               /* [groups], [2] */
+    double *res_f;                                             /* [seed_count][6] */
+    int32_t *res_i;                                            /* [seed_count][4] */
+    double *member_x, *member_obst, *member_goal;              /* [groups * K] rows */
+    int32_t *member_flags;                                     /* [groups * K] */
+} mpc_group_refill_arrays;
+int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigned seed_first, int seed_count, int max_steps, const double *box,
+                         const double *d_start, const double *d_goal_rows, int per_seed, const double *d_offsets, const mpc_group_refill_arrays *a,
+                         void *stream);
 /* MULTI-GPU: one process per GPU, every rank solves its own contiguous slice of the scenarios (the reference's 13 000 closed
  * loops, experiments.py:20-36, are independent), and the only exchange is an all-gather of the per-instance costs -- RCCL over xGMI, called directly
  * from this library (librccl.so.1 is loaded on first use; there is no link-time dependency and no other transport).  A C host does:
