@@ -455,6 +455,91 @@ __device__ __forceinline__ int select_member(int K, double margin, const double 
     return idx < 64 ? idx : -1;
 }
 
+// GUESS FAMILY FROM GEOMETRY (mpc_set_guess_geometry; include/mpc_gpu.h states the rule): the amplitudes of one group's members from the obstacles in the
+// way, written ONCE for seed_guesses_geom_kernel, group_step_kernel<true> and group_refill_apply_kernel<true>.  Called by all 64 lanes of a wavefront that
+// holds one group: (px, py) and (gx, gy) are the group's (the same on every lane), lane j < no holds obstacle j in ob, its radius r and its mask bit in
+// `present`, lane k < K holds offsets[k] in base; lane k returns the amplitude of member k (lanes >= K: base).  The rank of a blocking obstacle is a
+// count over the no obstacle lanes with the lexicographic compare (al, j); the member lanes then look for rank (k - 1) >> 1 and fetch its left / right.
+// The loops run to the run-time count `no` (wave-uniform) and no cross-lane step stands under a lane-dependent branch; no LDS, no atomics.  Contraction
+// is off so that the three callers and a host restatement round the same operations.
+struct GuessGeom { int mode; double clearance, a_max, lead, r_safe; const double *ip_r2; const uint32_t *omask; };
+
+// the radius and the mask bit the rule reads for obstacle `lane` of the group whose first member is instance `base`: row `base` of the per-instance
+// tables where the handle has them.  The table holds r_safe^2 (KParams::ip_r2), and sqrt(fl(r r)) = r in binary64 for any r whose square neither
+// overflows nor underflows (radii are finite and > 0), so the root is the caller's r_safe bit for bit
+__device__ __forceinline__ void guess_geometry_row(const GuessGeom &q, size_t base, int no, int lane, double &r, bool &present)
+{
+    r = q.r_safe; present = lane < no;
+    if (lane < no) {
+        if (q.ip_r2) r = sqrt(q.ip_r2[base * no + lane]);
+        if (q.omask) present = (omask_word(q.omask, (int)base, no) >> lane) & 1u;
+    }
+}
+
+__device__ __forceinline__ double guess_amplitudes(const GuessGeom &q, int K, int no, int lane, double px, double py, double gx, double gy,
+                                                   const double ob[4], double r, bool present, double base)
+{
+#pragma clang fp contract(off)
+    const double dx = gx - px, dy = gy - py;
+    const double L = sqrt(dx * dx + dy * dy);
+    const double tx = dx / L, ty = dy / L;
+    const double qx = ob[0] + q.lead * ob[2], qy = ob[1] + q.lead * ob[3];
+    const double ex = qx - px, ey = qy - py;
+    const double al = ex * tx + ey * ty, c = ex * (-ty) + ey * tx;
+    const double s = al / L, R = r + q.clearance;
+    const bool blocks = lane < no && present && s > 0.0 && s < 1.0 && fabs(c) < R;       // (a NaN fails every compare)
+    const double w = sin(kPi * s);
+    const double left = fmin(fmax((c + R) / w, -q.a_max), q.a_max), right = fmin(fmax((c - R) / w, -q.a_max), q.a_max);
+    int rank = blocks ? 0 : -1;
+    for (int j = 0; j < no; j++) {
+        const double aj = __shfl(al, j);
+        const int bj = __shfl((int)blocks, j);
+        if (blocks && bj && (aj < al || (aj == al && j < lane))) rank++;
+    }
+    const int want = lane >= 1 && lane < K ? (lane - 1) >> 1 : -2;
+    int src = -1;
+    for (int j = 0; j < no; j++)
+        if (__shfl(rank, j) == want) src = j;
+    const double lj = __shfl(left, src < 0 ? 0 : src), rj = __shfl(right, src < 0 ? 0 : src);
+    double amp = base;
+    if (src >= 0 && !(L < 1e-9)) amp = (lane & 1) ? lj : rj;
+    return amp;
+}
+
+// seed_guesses_kernel with the amplitudes from the geometry (mpc_seed_guesses_geom_dev): the same layout -- one wavefront per instance, a stage per lane,
+// four instances per workgroup -- and each wavefront evaluates its GROUP's rule for itself (obstacle j of the group on lane j, the base family on the
+// member lanes) and reads out its own member's amplitude; the wavefront of member 0 also stores the group's K amplitudes into offsets_out.  No lane
+// leaves in front of the cross-lane steps.  Every word written belongs to the wavefront's own instance (offsets_out: to its own group, by member 0).
+__global__ __launch_bounds__(kGroupThreads) void seed_guesses_geom_kernel(GuessGeom q, int groups, int K, int N, int n_obst, int keep_first,
+                                                                          const double *__restrict__ x0, const double *__restrict__ obst,
+                                                                          const double *__restrict__ goal, const double *__restrict__ offsets,
+                                                                          double *__restrict__ X, double *__restrict__ U, double *__restrict__ offsets_out)
+{
+    const int i = threadIdx.x & 63;
+    const int inst = __builtin_amdgcn_readfirstlane(blockIdx.x * kGroupWaves + (threadIdx.x >> 6));
+    if (inst >= groups * K) return;                             // (wave-uniform)
+    const int g = inst / K, k = inst - g * K;
+    const double x[5] = {x0[(size_t)g * 5], x0[(size_t)g * 5 + 1], x0[(size_t)g * 5 + 2], x0[(size_t)g * 5 + 3], x0[(size_t)g * 5 + 4]};
+    const double gx = goal[(size_t)g * 2], gy = goal[(size_t)g * 2 + 1];
+    double ob[4] = {0.0, 0.0, 0.0, 0.0}, r;
+    bool present;
+    if (i < n_obst) { const double *o = obst + ((size_t)g * n_obst + i) * 4; ob[0] = o[0]; ob[1] = o[1]; ob[2] = o[2]; ob[3] = o[3]; }
+    guess_geometry_row(q, (size_t)g * K, n_obst, i, r, present);
+    const double amp = guess_amplitudes(q, K, n_obst, i, x[0], x[1], gx, gy, ob, r, present, i < K ? offsets[i] : 0.0);
+    const double a = __shfl(amp, k);
+    if (k == 0 && offsets_out && i < K) offsets_out[(size_t)g * K + i] = amp;
+    if ((keep_first && k == 0) || i > N) return;
+    const double dx = gx - x[0], dy = gy - x[1];
+    const double L = sqrt(dx * dx + dy * dy);
+    const double s = (double)i / (double)N;
+    double xi[5];
+    seed_stage(x, dx, dy, L, a, i, s, sin(kPi * s), cos(kPi * s), xi);
+    double *Xi = X + ((size_t)inst * (N + 1) + i) * 5;
+#pragma unroll
+    for (int c = 0; c < 5; c++) Xi[c] = xi[c];
+    if (i < N) { double *Ui = U + ((size_t)inst * N + i) * 2; Ui[0] = 0.0; Ui[1] = 0.0; }
+}
+
 __global__ __launch_bounds__(kGroupThreads) void select_best_kernel(int groups, int K, int N, double margin, int flags, const double *__restrict__ cost,
                                                                     const int32_t *__restrict__ status, double *X, double *U,
                                                                     int32_t *__restrict__ winner, double *__restrict__ best_cost,
@@ -517,9 +602,14 @@ struct GroupStepArgs {
     int32_t *winner; double *best_key, *best_u0, *min_margin; int32_t *ep_flags, *ep_steps, *lost, *switched;
     double *member_x, *member_obst, *member_goal; int32_t *member_flags;
     const double *ip_rhit; const uint32_t *omask;               // the tables of the solve the step stands behind, or null
+    GuessGeom geom;                                             // the guess family from geometry (read by group_step_kernel<true> alone)
 };
 constexpr int kGroupMarginAll = 1;                              // MPC_GROUP_MARGIN_ALL
 
+// GEOM (mpc_set_guess_geometry): point 5 seeds members 1 .. K - 1 with guess_amplitudes on the new state and the moved obstacles instead of offsets[k].
+// A template parameter, not a branch: group_step_kernel<false> is the kernel as it was, instruction for instruction, and the launch picks the instantiation.
+// GEOM loads the r_safe row and the mask word of row g K ABOVE the wait like every other word of the group; the rule then works on registers (xn, ob).
+template <bool GEOM>
 __global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupStepArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -565,6 +655,9 @@ __global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupSt
         // an absent obstacle moves, but is not counted (kGroupMarginAll: it is)
         if (a.omask && !(a.flags & kGroupMarginAll) && !((omask_word(a.omask, (int)base, no) >> lane) & 1u)) margin = INFINITY;
     }
+    double geom_r = 0.0;
+    bool geom_on = false;
+    if constexpr (GEOM) guess_geometry_row(a.geom, base, no, lane, geom_r, geom_on);
     margin = -seg_max<64>(-margin, lane);
     // ---- 4. bookkeeping ----
     int fl = fl0;
@@ -597,8 +690,10 @@ __global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupSt
     const double L = sqrt(dx * dx + dy * dy);
     const double s = (double)lane / (double)N;
     const double sn = sin(kPi * s), cs = cos(kPi * s);          // once per lane, not once per member
+    double amp = off;
+    if constexpr (GEOM) amp = guess_amplitudes(a.geom, K, no, lane, xn[0], xn[1], gx, gy, ob, geom_r, geom_on, off);
     for (int k = 0; k < K; k++) {
-        const double ak = __shfl(off, k);
+        const double ak = __shfl(amp, k);
         double xi[5], ui[2] = {0.0, 0.0};
         if (k == 0 && w >= 0) {
 #pragma unroll
@@ -984,9 +1079,13 @@ struct GroupRefillArgs {
     unsigned *state; int32_t *slot_seed;
     double *res_f; int32_t *res_i;
     double *member_x, *member_obst, *member_goal; int32_t *member_flags;
+    GuessGeom geom;                                             // the guess family from geometry (read by group_refill_apply_kernel<true> alone)
 };
 constexpr int kGroupRefillMaxObst = 32;                        // MPC_MAX_OBST: the scenario's draws of one group, held by lane 0 until they are dealt out
 
+// GEOM: as in group_step_kernel -- <false> is the kernel as it was; <true> loads the r_safe row and the mask word of row g K above the wait and seeds
+// members 1 .. K - 1 of a started group with guess_amplitudes on the start row and the obstacles just drawn (member 0: offsets[0], which the rule keeps).
+template <bool GEOM>
 __global__ __launch_bounds__(kGroupThreads) void group_refill_apply_kernel(const GroupRefillArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -1011,6 +1110,9 @@ __global__ __launch_bounds__(kGroupThreads) void group_refill_apply_kernel(const
         gx = a.goal_src[row * 2]; gy = a.goal_src[row * 2 + 1];
     }
     const double off = lane < K ? a.offsets[lane] : 0.0;
+    double geom_r = 0.0;
+    bool geom_on = false;
+    if constexpr (GEOM) guess_geometry_row(a.geom, base, no, lane, geom_r, geom_on);
     // ---- every load of the group's words has returned before the first store is issued ----
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0);
@@ -1052,8 +1154,10 @@ __global__ __launch_bounds__(kGroupThreads) void group_refill_apply_kernel(const
     const double L = sqrt(dx * dx + dy * dy);
     const double s = (double)lane / (double)N;
     const double sn = sin(kPi * s), cs = cos(kPi * s);          // once per lane, not once per member
+    double amp = off;
+    if constexpr (GEOM) amp = guess_amplitudes(a.geom, K, no, lane, xs[0], xs[1], gx, gy, ob, geom_r, geom_on, off);
     for (int k = 0; k < K; k++) {
-        const double ak = __shfl(off, k);
+        const double ak = __shfl(amp, k);
         double xi[5];
         seed_stage(xs, dx, dy, L, ak, lane, s, sn, cs, xi);
         if (lane <= N) {

@@ -7,6 +7,7 @@
 #include "rti_wide_kernel.hpp"
 #include "solve_dispatch.hpp"
 
+#include <cmath>
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <mutex>
@@ -122,6 +123,8 @@ struct mpc_handle {
     int ring_scenario, ring_seed_count; unsigned ring_seed_first; double ring_box[6];
     int trace_rows, trace_max_steps;  // per-seed trajectories of a sweep (mpc_episode_trace_set_dev): rows, 0 = none attached; the caller's device arrays, used in place
     mpc_episode_trace trace;
+    int gg_mode;                      // guess family from geometry (mpc_set_guess_geometry): 0 off, 1 the amplitudes of seeded members from the obstacles in the way
+    double gg_clearance, gg_a_max, gg_lead;
 };
 
 namespace {
@@ -795,6 +798,46 @@ int mpc_seed_guesses_dev(mpc_handle *h, int groups, int K, const double *d_x0, c
     return MPC_OK;
 }
 
+int mpc_set_guess_geometry(mpc_handle *h, int mode, double clearance, double a_max, double lead)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (mode != 0 && mode != 1) return fail(MPC_ERR_ARG, "mpc_set_guess_geometry: mode must be 0 (off) or 1 (amplitudes from the obstacle geometry)");
+    if (!(clearance >= 0.0) || !std::isfinite(clearance)) return fail(MPC_ERR_ARG, "mpc_set_guess_geometry: clearance must be finite and >= 0");
+    if (!(a_max > 0.0) || !std::isfinite(a_max)) return fail(MPC_ERR_ARG, "mpc_set_guess_geometry: a_max must be finite and > 0");
+    if (!(lead >= 0.0) || !std::isfinite(lead)) return fail(MPC_ERR_ARG, "mpc_set_guess_geometry: lead must be finite and >= 0");
+    h->gg_mode = mode; h->gg_clearance = clearance; h->gg_a_max = a_max; h->gg_lead = lead;
+    return MPC_OK;
+}
+
+// the rule's parameters and the tables it reads of a solve over `p.batch` instances (attach_inputs has filled p): the r_safe^2 rows and the mask, or null
+static mpc::GuessGeom guess_geom(const mpc_handle *h, const mpc::KParams &p)
+{
+    mpc::GuessGeom q;
+    q.mode = h->gg_mode; q.clearance = h->gg_clearance; q.a_max = h->gg_a_max; q.lead = h->gg_lead;
+    q.r_safe = h->cfg.r_safe; q.ip_r2 = p.ip_r2; q.omask = p.omask;
+    return q;
+}
+
+int mpc_seed_guesses_geom_dev(mpc_handle *h, int groups, int K, const double *d_x0, const double *d_obst, const double *d_goal, const double *d_offsets,
+                              int keep_first, double *d_X, double *d_U, double *d_offsets_out, void *stream)
+{
+    int rc = check_groups(h, groups, K); if (rc) return rc;
+    if (!h->gg_mode) return fail(MPC_ERR_ARG, "mpc_seed_guesses_geom_dev: the guess geometry is off (mpc_set_guess_geometry); mpc_seed_guesses_dev seeds the fixed family");
+    if (groups == 0) return MPC_OK;
+    if (!d_x0 || !d_obst || !d_goal || !d_offsets || !d_X || !d_U) return fail(MPC_ERR_ARG, "null device pointer (only d_offsets_out may be null)");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = pick(h, stream);
+    const int count = groups * K;
+    // the per-instance tables of the solve the guesses are for (r_safe rows, obstacle mask), with that solve's coverage checks
+    mpc::KParams p = solve_params(h, count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    p.trace = nullptr;
+    rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc;
+    hipLaunchKernelGGL(mpc::seed_guesses_geom_kernel, dim3((count + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s,
+                       guess_geom(h, p), groups, K, h->cfg.N, h->cfg.n_obst, keep_first ? 1 : 0, d_x0, d_obst, d_goal, d_offsets, d_X, d_U, d_offsets_out);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, const int32_t *d_status, double incumbent_margin, int flags,
                         double *d_X, double *d_U, int32_t *d_winner, double *d_best_cost, double *d_best_u0, const double *d_u0, void *stream)
 {
@@ -843,7 +886,9 @@ int mpc_group_step_dev(mpc_handle *h, int groups, int K, const double *d_key, co
     a.ep_flags = out->ep_flags; a.ep_steps = out->ep_steps; a.lost = out->lost; a.switched = out->switched;
     a.member_x = out->member_x; a.member_obst = out->member_obst; a.member_goal = out->member_goal; a.member_flags = out->member_flags;
     a.ip_rhit = p.ip_rhit; a.omask = p.omask;
-    hipLaunchKernelGGL(mpc::group_step_kernel, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, a);
+    a.geom = guess_geom(h, p);
+    hipLaunchKernelGGL(h->gg_mode ? mpc::group_step_kernel<true> : mpc::group_step_kernel<false>, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves),
+                       dim3(mpc::kGroupThreads), 0, s, a);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -1226,9 +1271,14 @@ int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigne
     HIPCHK(hipSetDevice(h->device));
     int rc = own(h, &h->d_refill_assign, (size_t)h->max_batch); if (rc) return rc;
     hipStream_t s = pick(h, stream);
+    // the guess geometry reads the per-instance tables of the member solve (r_safe rows, obstacle mask), with that solve's coverage checks; off: none
+    mpc::KParams p = solve_params(h, groups * K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    p.trace = nullptr;
+    if (h->gg_mode) { rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc; }
     hipLaunchKernelGGL(mpc::refill_decide_kernel, dim3(1), dim3(mpc::kRefillThreads), 0, s, groups, seed_count, max_steps, a->ep_flags, a->ep_steps,
                        h->d_refill_assign, a->cursor);
     mpc::GroupRefillArgs ga;
+    ga.geom = guess_geom(h, p);
     ga.groups = groups; ga.K = K; ga.N = h->cfg.N; ga.n_obst = h->cfg.n_obst; ga.scenario = scenario; ga.per_seed = per_seed; ga.seed_first = seed_first;
     ga.x_lo = box[0]; ga.x_hi = box[1]; ga.y_lo = box[2]; ga.y_hi = box[3]; ga.v_max = box[4]; ga.edge = box[5];
     ga.assign = h->d_refill_assign; ga.start = d_start; ga.goal_src = d_goal_rows; ga.offsets = d_offsets;
@@ -1236,7 +1286,8 @@ int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigne
     ga.ep_flags = a->ep_flags; ga.ep_steps = a->ep_steps; ga.lost = a->lost; ga.switched = a->switched;
     ga.state = a->state; ga.slot_seed = a->slot_seed; ga.res_f = a->res_f; ga.res_i = a->res_i;
     ga.member_x = a->member_x; ga.member_obst = a->member_obst; ga.member_goal = a->member_goal; ga.member_flags = a->member_flags;
-    hipLaunchKernelGGL(mpc::group_refill_apply_kernel, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, ga);
+    hipLaunchKernelGGL(h->gg_mode ? mpc::group_refill_apply_kernel<true> : mpc::group_refill_apply_kernel<false>,
+                       dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, ga);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }

@@ -115,6 +115,8 @@ SYMBOLS = {
     "mpc_reset_guess_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_reset_guess_interp_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mpc_seed_guesses_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "mpc_set_guess_geometry": (C.c_int, [_vp, C.c_int, _d, _d, _d]),
+    "mpc_seed_guesses_geom_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mpc_select_best_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _d, C.c_int] + [_vp] * 7),
     "mpc_group_step_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _d, C.c_int, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp,
                                      C.POINTER(GroupStepOut), _vp]),

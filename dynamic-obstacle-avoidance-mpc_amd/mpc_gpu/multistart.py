@@ -11,13 +11,17 @@ solved (X, U) with members = K -- and the selection then compares the candidates
 instead of the costs the solve reports for iterates that need not be dynamically consistent.
 
 Nothing leaves the device between them: torch replicates the group inputs and carries the tensors, the `_dev` entry points do the work.  The pure helpers
-(`check_offsets`, `check_margin`, `check_select_by`, `check_group_shapes`, `replicate`, `episode_arguments`) import without a GPU.
+(`check_offsets`, `check_guess_geometry`, `check_margin`, `check_select_by`, `check_group_shapes`, `replicate`, `episode_arguments`) import without a GPU.
 
 The CLOSED LOOP has two forms.  step() composes a control step from the entry points above and the plant / obstacle / shift / seed launches.  step_fused()
 runs the member solve and then ONE launch, mpc_group_step_dev (select, plant, obstacles, episode bookkeeping per group, next iterates, the members' inputs;
 DESIGN.md section 4m), and run_multistart_episodes drives it to the reference's result table.  run_multistart_sweep streams more seeds than there are
 groups through the groups: a finished group starts the next seed on the device (mpc_group_refill_dev).  PipelinedMpc does not know
-about groups."""
+about groups.
+
+guess_geometry (off by default) replaces the fixed lateral offsets of members 1 .. K - 1 by amplitudes computed on the device from the obstacles that are in the
+way -- the pass-left / pass-right candidates of the nearest blocking obstacles (mpc_set_guess_geometry); `offsets` is then the base family a
+member falls back to."""
 import numpy as np
 
 from . import _lib
@@ -43,6 +47,34 @@ def check_margin(incumbent_margin):
     if not (0.0 <= m < 1.0):
         raise ValueError(f"incumbent_margin must be in [0, 1), got {incumbent_margin}")
     return m
+
+
+GUESS_GEOMETRY_DEFAULTS = dict(clearance=0.25, a_max=6.0, lead=0.0)      # metres beside r_safe, the largest amplitude in metres, seconds the obstacle is moved ahead
+
+
+def check_guess_geometry(guess_geometry):
+    """the guess-geometry setting of a MultiStartMpc: None or False (off) -> None; True -> the defaults; a dict with some of clearance >= 0, a_max > 0, lead >= 0
+    (finite floats) -> the defaults with those entries -- or ValueError"""
+    if guess_geometry is None or guess_geometry is False:
+        return None
+    if guess_geometry is True:
+        return dict(GUESS_GEOMETRY_DEFAULTS)
+    if not isinstance(guess_geometry, dict):
+        raise ValueError(f"guess_geometry must be None, True or a dict with some of {sorted(GUESS_GEOMETRY_DEFAULTS)}, got {guess_geometry!r}")
+    unknown = sorted(set(guess_geometry) - set(GUESS_GEOMETRY_DEFAULTS))
+    if unknown:
+        raise ValueError(f"guess_geometry has no entry {unknown[0]!r}: the entries are {sorted(GUESS_GEOMETRY_DEFAULTS)}")
+    out = dict(GUESS_GEOMETRY_DEFAULTS)
+    for k, v in guess_geometry.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"guess_geometry[{k!r}] must be a number, got {v!r}")
+        out[k] = float(v)
+    for k in ("clearance", "lead"):
+        if not (0.0 <= out[k] < np.inf):
+            raise ValueError(f"guess_geometry[{k!r}] must be finite and >= 0, got {out[k]}")
+    if not (0.0 < out["a_max"] < np.inf):
+        raise ValueError(f"guess_geometry['a_max'] must be finite and > 0, got {out['a_max']}")
+    return out
 
 
 SELECT_BY = ("cost", "rollout")
@@ -84,8 +116,9 @@ class MultiStartMpc:
     Inputs and outputs are float64 / int32 device tensors; a numpy array is uploaded.  Everything runs on the object's own stream, which waits for the
     caller's current torch stream on entry and which that stream waits for on exit."""
 
-    def __init__(self, N=20, n_obst=3, Tf=2.0, scenarios=1, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, device=0, select_by="cost", **cfg):
+    def __init__(self, N=20, n_obst=3, Tf=2.0, scenarios=1, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, device=0, select_by="cost", guess_geometry=None, **cfg):
         self.select_by = check_select_by(select_by)
+        self.guess_geometry = check_guess_geometry(guess_geometry)
         import torch
         off = check_offsets(offsets)
         self.K, self.G = int(off.shape[0]), check_scenarios(scenarios, off.shape[0])
@@ -109,6 +142,11 @@ class MultiStartMpc:
             self.cand_merit, self.cand_defect, self.cand_margin = f64(B), f64(B), f64(B)
         self.solved_X = self.solved_U = None
         self._warm = self._fused_warm = False
+        self.member_offsets = None                 # guess_geometry: the (G, K) amplitudes the last stand-alone seed launch wrote
+        if self.guess_geometry is not None:
+            q = self.guess_geometry
+            _lib.check(_lib.lib().mpc_set_guess_geometry(self.inner._h, 1, q["clearance"], q["a_max"], q["lead"]))
+            self.member_offsets = f64(G, K)
         torch.cuda.synchronize(self.dev)
 
     # ------------------------------------------------------------------ lifetime
@@ -163,15 +201,21 @@ class MultiStartMpc:
         self._obst.copy_(self._dev(obstacles)[:, None, :, :])
         self._goal.copy_(self._dev(goal)[:, None, :])
 
-    def _seed(self, x_rows, goal_rows, keep_first, s):
-        """mpc_seed_guesses_dev from per-GROUP rows: x_rows (G, 5) and goal_rows (G, 2), contiguous"""
+    def _seed(self, x_rows, goal_rows, keep_first, s, obst_rows=None):
+        """mpc_seed_guesses_dev from per-GROUP rows: x_rows (G, 5) and goal_rows (G, 2), contiguous; with guess_geometry mpc_seed_guesses_geom_dev on them and
+        obst_rows (G, n_obst, 4), the amplitudes into member_offsets"""
+        if self.guess_geometry is not None:
+            _lib.check(_lib.lib().mpc_seed_guesses_geom_dev(self.inner._h, self.G, self.K, x_rows.data_ptr(), obst_rows.data_ptr(), goal_rows.data_ptr(),
+                                                            self.offsets.data_ptr(), 1 if keep_first else 0, self.X.data_ptr(), self.U.data_ptr(),
+                                                            self.member_offsets.data_ptr(), s))
+            return
         _lib.check(_lib.lib().mpc_seed_guesses_dev(self.inner._h, self.G, self.K, x_rows.data_ptr(), goal_rows.data_ptr(), self.offsets.data_ptr(),
                                                    1 if keep_first else 0, self.X.data_ptr(), self.U.data_ptr(), s))
 
     def _solve(self, x0, obstacles, goal, seed, keep_first, keep_solution, s):
         self._load(x0, obstacles, goal)
         if seed:
-            self._seed(self._x0[:, 0].contiguous(), self._goal[:, 0].contiguous(), keep_first, s)
+            self._seed(self._x0[:, 0].contiguous(), self._goal[:, 0].contiguous(), keep_first, s, self._obst[:, 0].contiguous())
         self.inner.closed_loop_step_dev(self.B, self._x0, self._obst, self._goal, self.X, self.U, self.cand_u0, self.cand_cost, self.cand_status,
                                         self.cand_iters, flags=0, stream=s)
         if keep_solution:
@@ -233,7 +277,7 @@ class MultiStartMpc:
             m.obstacle_step_dev(G * self.n_obst, obst, None if noise is None else self._dev(noise).contiguous(), randomness, vmax, stream=s)
             m.shift_dev(self.B, self.X, self.U, stream=s)
             goal_rows = self._goal[:, 0].contiguous()
-            self._seed(x, goal_rows, True, s)
+            self._seed(x, goal_rows, True, s, obst)
             # a group without a winner: member 0 too starts again, from its own guess of the family (offsets[0]), selected on the device
             _lib.check(_lib.lib().mpc_seed_guesses_dev(m._h, G, 1, x.data_ptr(), goal_rows.data_ptr(), self.offsets.data_ptr(), 0,
                                                        self._X1.data_ptr(), self._U1.data_ptr(), s))
@@ -300,7 +344,7 @@ class MultiStartMpc:
             if not (self._warm and self._fused_warm):
                 self._load(x, obst, goal)
                 self.member_flags.copy_((self.ep_flags & 1).repeat_interleave(K))
-                self._seed(x, goal, False, s)
+                self._seed(x, goal, False, s, obst)
                 self._warm = self._fused_warm = True
             m.closed_loop_step_dev(B, self._x0, self._obst, self._goal, self.X, self.U, self.cand_u0, self.cand_cost, self.cand_status, self.cand_iters,
                                    flags=_lib.STEP_METRICS, min_margin=self._scratch_margin, ep_flags=self.member_flags, ep_steps=self._scratch_steps, stream=s)
@@ -324,11 +368,13 @@ class MultiStartMpc:
 
 # ---------------------------------------------------------------------------------------------------------------------- episodes of groups
 def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", n_obst=5, max_iter=400, random_move=True, first_seed=0,
-                      noise=None, sqp=None, r_safe=None, r_hit=None, active=None, solver=None):
+                      noise=None, sqp=None, r_safe=None, r_hit=None, active=None, solver=None, guess_geometry=None):
     """run_multistart_episodes' arguments, checked on the host before anything touches a device.  Returns dict(G, K, n_obst, x0 (G, 5), goal (G, 2), obst (the
-    array (G, n_obst, 4) or None), scenario (the name or None), offsets, margin, select_by, max_iter, noise (None, "reference", "torch" or the array), first_seed)."""
+    array (G, n_obst, 4) or None), scenario (the name or None), offsets, margin, select_by, max_iter, noise (None, "reference", "torch" or the array), first_seed,
+    guess_geometry (None or check_guess_geometry's dict))."""
     from .episodes import _episode_noise
     off, margin, select_by = check_offsets(offsets), check_margin(incumbent_margin), check_select_by(select_by)
+    geometry = check_guess_geometry(guess_geometry)
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     if x0.ndim != 2 or x0.shape[1] != 5 or x0.shape[0] < 1:
         raise ValueError(f"x0 must be (G, 5) with one row per group (G >= 1), got {x0.shape}")
@@ -369,12 +415,15 @@ def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=
         if (solver.G, solver.n_obst) != (G, n_obst) or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin or solver.select_by != select_by:
             raise ValueError(f"solver holds {solver.G} groups of {solver.n_obst} obstacles, offsets {solver.offsets_host.tolist()}, margin {solver.margin}, "
                              f"select_by {solver.select_by!r}: not what this call asks for")
+        if solver.guess_geometry != geometry:
+            raise ValueError(f"solver has guess_geometry {solver.guess_geometry}: this call asks for {geometry}")
     return dict(G=G, K=K, n_obst=n_obst, x0=x0, goal=goal, obst=obst, scenario=scenario, offsets=off, margin=margin, select_by=select_by, max_iter=int(max_iter),
-                noise=noise, first_seed=int(first_seed))
+                noise=noise, first_seed=int(first_seed), guess_geometry=geometry)
 
 
 def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True,
-                            first_seed=0, noise=None, sqp=None, r_safe=None, r_hit=None, active=None, margin_all=False, solver=None, device=0, **cfg):
+                            first_seed=0, noise=None, sqp=None, r_safe=None, r_hit=None, active=None, margin_all=False, solver=None, device=0,
+                            guess_geometry=None, **cfg):
     """run_episodes for GROUPS: G closed-loop episodes of K = len(offsets) candidate iterates each, one MultiStartMpc.step_fused per control step (noise draw ->
     member solve -> [predict, rollout merit] -> group tail), episode bookkeeping per group on the device.  x0 (G, 5), goal (2,) or (G, 2), obst (G, n_obst, 4)
     -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): group s is then the reference's episode for np.random.seed(first_seed + s) (experiments.py:20-36), its
@@ -382,7 +431,8 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
     the GROUP flags: a finished group draws no more).  The plant starts from x0 as given.
     noise: as run_episodes -- an array (>= max_iter, G, n_obst, 2), "reference" (the default with a scenario name), "torch" (the default with explicit
     obstacle states); random_move=False: the obstacles draw nothing.  sqp (max_iter, step_tol), r_safe / r_hit ((G,) or (G, n_obst)), active (bool (G, n_obst))
-    with margin_all: per GROUP, as run_episodes takes them per instance (MultiStartMpc replicates them over the members).
+    with margin_all: per GROUP, as run_episodes takes them per instance (MultiStartMpc replicates them over the members).  guess_geometry: as MultiStartMpc
+    takes it (the amplitudes of the seeded members from the obstacles in the way, formed by the group tail on the new state and the moved obstacles).
     A group that has reached its goal is neither solved nor stepped.  The loop ends as run_episodes' does: every 25 control steps the
     done flag goes to pinned host memory behind an event and is looked at once that event has passed -- no stall, at most ~25 steps on idle groups.
     solver: a caller's MultiStartMpc with the same groups, offsets, margin and select_by; it is restart()ed, and leaves with the features of this call switched
@@ -394,11 +444,13 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
     control steps on which the winner was not member 0)."""
     from .episodes import _HandleLease, _noise_source, result_table
     from types import SimpleNamespace
-    a = episode_arguments(x0, goal, obst, offsets, incumbent_margin, select_by, n_obst, max_iter, random_move, first_seed, noise, sqp, r_safe, r_hit, active, solver)
+    a = episode_arguments(x0, goal, obst, offsets, incumbent_margin, select_by, n_obst, max_iter, random_move, first_seed, noise, sqp, r_safe, r_hit, active, solver,
+                          guess_geometry)
     import torch
     G, K, no = a["G"], a["K"], a["n_obst"]
     dev = torch.device("cuda", device if solver is None else solver.dev.index)
-    make = lambda: MultiStartMpc(N, no, Tf, scenarios=G, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"], **cfg)
+    make = lambda: MultiStartMpc(N, no, Tf, scenarios=G, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"],
+                                 guess_geometry=a["guess_geometry"], **cfg)
     with _HandleLease(solver, make) as lease:
         ms = lease.m
         lease.stream = ms.stream
@@ -448,11 +500,13 @@ _SWEEP_NOT_OFFERED = ("r_safe", "r_hit", "W", "We", "active", "margin_all", "bou
 
 
 def sweep_arguments(start, goal, scenario, seeds, slots, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", n_obst=5, max_iter=400, sqp=None,
-                    poll_every=25, solver=None):
+                    poll_every=25, solver=None, guess_geometry=None):
     """run_multistart_sweep's arguments, checked on the host before anything touches a device.  Returns dict(first, count, start (rows, 5), goal (rows, 2),
-    per_seed, S = the group slots used, K, n_obst, offsets, margin, select_by, max_iter, poll_every, bound = the control steps the loop launches at most)."""
+    per_seed, S = the group slots used, K, n_obst, offsets, margin, select_by, max_iter, poll_every, bound = the control steps the loop launches at most,
+    guess_geometry = None or check_guess_geometry's dict)."""
     from .episodes import _sweep_arguments
     off, margin, select_by = check_offsets(offsets), check_margin(incumbent_margin), check_select_by(select_by)
+    geometry = check_guess_geometry(guess_geometry)
     first, count, start, goal, per_seed = _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every)
     if isinstance(n_obst, bool) or int(n_obst) != n_obst or not 1 <= int(n_obst) <= 32:
         raise ValueError(f"n_obst must be a whole number in 1 .. 32, got {n_obst!r}")
@@ -465,9 +519,11 @@ def sweep_arguments(start, goal, scenario, seeds, slots, offsets=DEFAULT_OFFSETS
         if solver.G != S or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin or solver.select_by != select_by:
             raise ValueError(f"solver holds {solver.G} groups, offsets {solver.offsets_host.tolist()}, margin {solver.margin}, select_by {solver.select_by!r}: "
                              f"this call asks for {S} group slots, offsets {off.tolist()}, margin {margin}, select_by {select_by!r}")
+        if solver.guess_geometry != geometry:
+            raise ValueError(f"solver has guess_geometry {solver.guess_geometry}: this call asks for {geometry}")
         n_obst = solver.n_obst
     return dict(first=first, count=count, start=start, goal=goal, per_seed=per_seed, S=S, K=K, n_obst=int(n_obst), offsets=off, margin=margin, select_by=select_by,
-                max_iter=int(max_iter), poll_every=int(poll_every), bound=-(-count // S) * int(max_iter) + int(poll_every))
+                max_iter=int(max_iter), poll_every=int(poll_every), bound=-(-count // S) * int(max_iter) + int(poll_every), guess_geometry=geometry)
 
 
 def _sweep_state(torch, ms, a, scenario, random_move=True):
@@ -496,14 +552,14 @@ def _sweep_state(torch, ms, a, scenario, random_move=True):
 
 
 def run_multistart_sweep(start, goal, scenario, seeds, slots, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", N=20, Tf=2.0, n_obst=5, max_iter=400,
-                         random_move=True, sqp=None, poll_every=25, solver=None, device=0, **cfg):
+                         random_move=True, sqp=None, poll_every=25, solver=None, device=0, guess_geometry=None, **cfg):
     """run_seed_sweep for GROUPS: the seeds stream through min(slots, count) GROUP slots of K = len(offsets) members each, and a group whose episode has ended
     (goal reached, or max_iter control steps spent) starts the next seed on the device, in front of the next member solve (mpc_group_refill_dev: no host
     read, no gather; a finished group does not idle in its K wavefront slots while seeds are left).  Seed index k is group k of
     run_multistart_episodes(start rows, goal, scenario, first_seed=first, ...) on ONE batch of `count` groups: the same scenario draw, noise stream, guesses
     and control steps -- the rows are those of that batch to the rounding of the wavefront sums (three member solves share a wavefront).
     scenario, seeds, start (5,) or (count, 5), goal (2,) or (count, 2), poll_every: as run_seed_sweep.  offsets, incumbent_margin, select_by, sqp, random_move:
-    as run_multistart_episodes.  One control step is refill -> poll copy -> noise draw on the group rows -> member solve -> [predict, rollout merit] -> group
+    as run_multistart_episodes; guess_geometry too (the refill forms a started group's amplitudes from its start row and the obstacles it has just drawn).  One control step is refill -> poll copy -> noise draw on the group rows -> member solve -> [predict, rollout merit] -> group
     tail (MultiStartMpc.step_fused on members that are already loaded).  The loop ends as run_seed_sweep's does and launches at most
     ceil(count / S) * max_iter + poll_every control steps whatever the device returns.
     solver: a caller's MultiStartMpc with min(slots, count) groups and the same offsets, margin and select_by; it is restart()ed on entry and on exit, and
@@ -516,11 +572,12 @@ def run_multistart_sweep(start, goal, scenario, seeds, slots, offsets=DEFAULT_OF
     if not_offered:
         raise TypeError(f"run_multistart_sweep has no argument {not_offered[0]!r}: per-seed feature tables, the status log, the ring and the trace are "
                         "run_seed_sweep's, and a batch's arguments are run_multistart_episodes'")
-    a = sweep_arguments(start, goal, scenario, seeds, slots, offsets, incumbent_margin, select_by, n_obst, max_iter, sqp, poll_every, solver)
+    a = sweep_arguments(start, goal, scenario, seeds, slots, offsets, incumbent_margin, select_by, n_obst, max_iter, sqp, poll_every, solver, guess_geometry)
     from .episodes import _HandleLease, result_table
     import torch
     S, K, count, no, poll = a["S"], a["K"], a["count"], a["n_obst"], a["poll_every"]
-    make = lambda: MultiStartMpc(N, no, Tf, scenarios=S, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"], **cfg)
+    make = lambda: MultiStartMpc(N, no, Tf, scenarios=S, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"],
+                                 guess_geometry=a["guess_geometry"], **cfg)
     with _HandleLease(solver, make) as lease:
         ms = lease.m
         lease.stream = ms.stream

@@ -332,7 +332,8 @@ int mpc_select_best_dev(mpc_handle *h, int groups, int K, const double *d_cost, 
  *      out->switched[g] += 1 when winner > 0;
  *   5. NEXT ITERATES: member 0 <- the winner's iterate shifted (mpc_shift_dev's rule: X[N] kept, U[N - 1] = 0); members 1 .. K - 1 <- the guess of
  *      mpc_seed_guesses_dev for d_offsets[k] around the NEW d_x[g] and d_goal[g]; a group without a winner applied u = 0 and has member 0 seeded too, with
- *      d_offsets[0].  There is no broadcast: the launch writes no word that it overwrites;
+ *      d_offsets[0].  There is no broadcast: the launch writes no word that it overwrites.  (With mpc_set_guess_geometry on, members 1 .. K - 1 take
+ *      the amplitudes of its rule on the new state and the moved obstacles, d_offsets being the base family: GUESS FAMILY FROM GEOMETRY below);
  *   6. MEMBER INPUTS of the next solve: the new x[g], obst[g] and goal[g] into rows g K .. g K + K - 1 of out->member_x [groups * K][5], out->member_obst
  *      [groups * K][n_obst][4], out->member_goal [groups * K][2], and out->member_flags[g K + k] = ep_flags[g] & 1.
  * A group whose bit 0 is set on entry is IDLE: the launch reads its flag and writes none of its words.  It is not solved either when the solve launch is
@@ -356,6 +357,28 @@ typedef struct mpc_group_step_out {
 int mpc_group_step_dev(mpc_handle *h, int groups, int K, const double *d_key, const int32_t *d_status, const double *d_u0, double incumbent_margin,
                        int flags, double *d_x, double *d_obst, const double *d_goal, const double *d_offsets, const double *d_noise, double randomness,
                        double vmax, double *d_X, double *d_U, const mpc_group_step_out *out, void *stream);
+/* MULTI-START, GUESS FAMILY FROM GEOMETRY: the lateral amplitudes of members 1 .. K - 1 chosen per group from the obstacles that are in the way, so that
+ * the members are the group's pass-left / pass-right candidates instead of one fixed family (no reference counterpart; docs/PROBLEM.md section 4).
+ * mpc_set_guess_geometry(h, mode, clearance, a_max, lead): mode 0 = off (the default of every handle; the other arguments are then checked and ignored),
+ * 1 = the rule below.  MPC_ERR_ARG: a null handle, any other mode, a NaN, negative or infinite clearance or lead, a_max that is not finite and > 0.
+ * THE RULE for one group with state x, goal, obstacle rows o_j = (x, y, vx, vy), j < n_obst, and base family offsets[K]: d = goal - x[0:2], L = |d|,
+ * t = d / L, n = (-t_y, t_x) as in mpc_seed_guesses_dev.  Per obstacle: q_j = o_j[0:2] + lead o_j[2:4] (no wall reflection), e_j = q_j - x[0:2],
+ * al_j = e_j . t, c_j = e_j . n, s_j = al_j / L, R_j = r_j + clearance with r_j = row g K of the per-instance r_safe table (mpc_set_instance_params) or the
+ * handle's r_safe.  Obstacle j BLOCKS when it is present under the obstacle mask of row g K (mpc_set_obstacle_mask), 0 < s_j < 1 and |c_j| < R_j, both
+ * strict -- a non-finite value makes the tests false.  A blocking obstacle offers, with w_j = sin(pi s_j), left_j = (c_j + R_j) / w_j and right_j =
+ * (c_j - R_j) / w_j, each clamped to [-a_max, a_max]: the family's path is displaced by a sin(pi s) at fraction s, so these put it R_j beside q_j.
+ * The blocking obstacles are ordered by al_j ascending, ties to the lower j.  Member 0 keeps offsets[0]; member k >= 1 takes, of the blocking obstacle
+ * of rank (k - 1) / 2, `left` when k is odd and `right` when k is even; where the order has no such obstacle the member keeps offsets[k].  L < 1e-9:
+ * every member keeps its base offset.  The iterate is mpc_seed_guesses_dev's for that amplitude.
+ * While the mode is on, mpc_group_step_dev (point 5, on the NEW state and the MOVED obstacles) and mpc_group_refill_dev (start, on the start row and the
+ * obstacles just drawn) form the amplitudes of the members they seed by this rule, d_offsets[K] being the base family; with the mode off both launch
+ * the kernels they launched before the mode existed.  Member 0 of a group with a winner is the shifted winner, of a group without one offsets[0], as before.
+ * mpc_seed_guesses_geom_dev is mpc_seed_guesses_dev with the rule applied per group: d_obst[groups][n_obst][4] are the groups' obstacle rows, and
+ * d_offsets_out[groups][K] (may be NULL) receives the amplitude of every member (member 0: offsets[0], under keep_first too).  MPC_ERR_ARG as
+ * mpc_seed_guesses_dev, and when the mode is off or a per-instance feature covers fewer than groups * K instances. */
+int mpc_set_guess_geometry(mpc_handle *h, int mode, double clearance, double a_max, double lead);
+int mpc_seed_guesses_geom_dev(mpc_handle *h, int groups, int K, const double *d_x0, const double *d_obst, const double *d_goal, const double *d_offsets,
+                              int keep_first, double *d_X, double *d_U, double *d_offsets_out, void *stream);
 /* ROLLOUT MERIT: score a plan by simulating its inputs.  The cost a solve reports is the NLP objective at the iterate (X + dX, U + dU), whose states follow
  * the linearisation about the guess, not the plant; one RTI iteration from a poor guess that pair is far from dynamically consistent, and its cost cannot be
  * compared with that of a converged one.  This call rolls U out from x0 -- X^r_0 = x0, X^r_{i+1} = F(X^r_i, U_i), F the integrator of mpc_plant_step_dev
@@ -534,6 +557,8 @@ int mpc_episode_trace_dev(mpc_handle *h, int slots, int phase, const int32_t *d_
  *       goal[g] = the goal row; min_margin = +inf, ep_flags = ep_steps = lost = switched = 0, slot_seed = k; members 0 .. K - 1 of a->X and a->U = the guess
  *       family of mpc_seed_guesses_dev (keep_first = 0) for d_offsets around x[g] and goal[g]; x[g], obst[g], goal[g] into the K member rows of
  *       a->member_x, a->member_obst, a->member_goal; member_flags = 0.  The selection's outputs (winner, best_key, best_u0) are not this call's.
+ *       (With mpc_set_guess_geometry on, members 1 .. K - 1 take the amplitudes of its rule on the start row and the obstacles just drawn, with row g K
+ *       of the handle's r_safe table and obstacle mask and that solve's coverage refusals; d_offsets is the base family.)
  * A wavefront reads every word it parks before it stores anything, and writes only words of its own group, its own members or its own seed.  No noise is
  * drawn: mpc_noise_draw_dev on a->state with the group flags follows, as in a batch of groups.
  * d_start [rows][5], d_goal_rows [rows][2]: rows = 1 (per_seed 0) or seed_count (per_seed 1, row k for index k).  box: as mpc_generate_scenarios_dev.
