@@ -397,6 +397,20 @@ __device__ __forceinline__ void seed_stage(const double x[5], double dx, double 
     }
 }
 
+// a lane's obstacle row, row `row` of an [..][4] array, written ONCE for the group kernels (geometry seed, group step, group refill).  The kernels that
+// fence their loads (group_step_kernel, group_refill_apply_kernel) load above the fence and store behind it; the pair holds no rule.  (The stage store, the
+// lane pick and the member-input store of these kernels stay written out: as helpers of any shape tried they changed the kernels' instructions.)
+__device__ __forceinline__ void load_obst_row(const double *obst, size_t row, double ob[4])
+{
+    const double *o = obst + row * 4;
+    ob[0] = o[0]; ob[1] = o[1]; ob[2] = o[2]; ob[3] = o[3];
+}
+__device__ __forceinline__ void store_obst_row(double *obst, size_t row, const double ob[4])
+{
+    double *o = obst + row * 4;
+    o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3];
+}
+
 __global__ __launch_bounds__(kGroupThreads) void seed_guesses_kernel(int groups, int K, int N, int keep_first, const double *__restrict__ x0,
                                                                      const double *__restrict__ goal, const double *__restrict__ offsets,
                                                                      double *__restrict__ X, double *__restrict__ U)
@@ -523,7 +537,7 @@ __global__ __launch_bounds__(kGroupThreads) void seed_guesses_geom_kernel(GuessG
     const double gx = goal[(size_t)g * 2], gy = goal[(size_t)g * 2 + 1];
     double ob[4] = {0.0, 0.0, 0.0, 0.0}, r;
     bool present;
-    if (i < n_obst) { const double *o = obst + ((size_t)g * n_obst + i) * 4; ob[0] = o[0]; ob[1] = o[1]; ob[2] = o[2]; ob[3] = o[3]; }
+    if (i < n_obst) load_obst_row(obst, (size_t)g * n_obst + i, ob);
     guess_geometry_row(q, (size_t)g * K, n_obst, i, r, present);
     const double amp = guess_amplitudes(q, K, n_obst, i, x[0], x[1], gx, gy, ob, r, present, i < K ? offsets[i] : 0.0);
     const double a = __shfl(amp, k);
@@ -646,8 +660,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupSt
     // ---- 3. obstacles, and the margin of the new state to where they are now ----
     double ob[4] = {0.0, 0.0, 0.0, 0.0}, margin = INFINITY;
     if (lane < no) {
-        const double *o = a.obst + ((size_t)g * no + lane) * 4;
-        ob[0] = o[0]; ob[1] = o[1]; ob[2] = o[2]; ob[3] = o[3];
+        load_obst_row(a.obst, (size_t)g * no + lane, ob);
         if (a.noise) obstacle_noise(a.randomness, a.vmax, a.noise[((size_t)g * no + lane) * 2], a.noise[((size_t)g * no + lane) * 2 + 1], ob[2], ob[3]);
         obstacle_advance(a.world, a.dt, ob[0], ob[2], ob[1], ob[3]);
         const double ddx = xn[0] - ob[0], ddy = xn[1] - ob[1];
@@ -683,7 +696,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupSt
     if (a.best_u0 && lane < 2) a.best_u0[(size_t)g * 2 + lane] = lane ? ub[1] : ub[0];
     const double xc = lane == 0 ? xn[0] : (lane == 1 ? xn[1] : (lane == 2 ? xn[2] : (lane == 3 ? xn[3] : xn[4])));      // lane c < 5: entry c of the new state
     if (lane < 5) a.x[(size_t)g * 5 + lane] = xc;
-    if (lane < no) { double *o = a.obst + ((size_t)g * no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+    if (lane < no) store_obst_row(a.obst, (size_t)g * no + lane, ob);
     if (a.member_flags && lane < K) a.member_flags[base + lane] = fl & 1;
     // ---- 5. the next iterates and 6. the members' inputs ----
     const double dx = gx - xn[0], dy = gy - xn[1];
@@ -710,7 +723,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_step_kernel(const GroupSt
         }
         if (a.member_x && lane < 5) a.member_x[(base + k) * 5 + lane] = xc;
         if (a.member_goal && lane < 2) a.member_goal[(base + k) * 2 + lane] = lane ? gy : gx;
-        if (a.member_obst && lane < no) { double *o = a.member_obst + ((base + k) * (size_t)no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+        if (a.member_obst && lane < no) store_obst_row(a.member_obst, (base + k) * (size_t)no + lane, ob);
     }
 }
 
@@ -1143,7 +1156,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_refill_apply_kernel(const
     const double xc = lane == 0 ? xs[0] : (lane == 1 ? xs[1] : (lane == 2 ? xs[2] : (lane == 3 ? xs[3] : xs[4])));      // lane c < 5: entry c of the start row
     if (lane < 5) a.x[(size_t)g * 5 + lane] = xc;
     if (lane < 2) a.goal[(size_t)g * 2 + lane] = lane ? gy : gx;
-    if (lane < no) { double *o = a.obst + ((size_t)g * no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+    if (lane < no) store_obst_row(a.obst, (size_t)g * no + lane, ob);
     if (lane == 0) {
         a.min_margin[g] = INFINITY; a.ep_flags[g] = 0; a.ep_steps[g] = 0; a.lost[g] = 0; a.switched[g] = 0;
         a.slot_seed[g] = as;
@@ -1168,7 +1181,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_refill_apply_kernel(const
         }
         if (lane < 5) a.member_x[(base + k) * 5 + lane] = xc;
         if (lane < 2) a.member_goal[(base + k) * 2 + lane] = lane ? gy : gx;
-        if (lane < no) { double *o = a.member_obst + ((base + k) * (size_t)no + lane) * 4; o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3]; }
+        if (lane < no) store_obst_row(a.member_obst, (base + k) * (size_t)no + lane, ob);
     }
 }
 

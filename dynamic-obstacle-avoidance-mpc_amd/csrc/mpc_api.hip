@@ -557,6 +557,16 @@ int attach_inputs(mpc_handle *h, mpc::KParams &p, hipStream_t s, AttachFor what)
     return check_covered(h->alpha, p.batch, "the slack schedule set by mpc_set_slack_schedule covers fewer instances than this solve");
 }
 
+// For a launch that stands beside the solve of `batch` instances (geometry guesses, group step, group refill, rollout merit): that solve's kernel arguments
+// as it would be launched now -- its constants, the inputs given, its per-instance tables with their coverage checks (attach; false: constants and inputs
+// alone, nothing is checked) --, none of its outputs, no trace
+int beside_solve(mpc_handle *h, int batch, const double *x0, const double *P, const double *goal, hipStream_t s, bool attach, mpc::KParams &p)
+{
+    p = solve_params(h, batch, x0, P, nullptr, goal, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    p.trace = nullptr;
+    return attach ? attach_inputs(h, p, s, kForSolve) : MPC_OK;
+}
+
 int launch_solve(mpc_handle *h, mpc::KParams &p, hipStream_t s)
 {
     p.iters_acc = h->d_iters_acc; p.status_acc = h->d_status_acc;
@@ -829,9 +839,8 @@ int mpc_seed_guesses_geom_dev(mpc_handle *h, int groups, int K, const double *d_
     hipStream_t s = pick(h, stream);
     const int count = groups * K;
     // the per-instance tables of the solve the guesses are for (r_safe rows, obstacle mask), with that solve's coverage checks
-    mpc::KParams p = solve_params(h, count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    p.trace = nullptr;
-    rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc;
+    mpc::KParams p;
+    rc = beside_solve(h, count, nullptr, nullptr, nullptr, s, true, p); if (rc) return rc;
     hipLaunchKernelGGL(mpc::seed_guesses_geom_kernel, dim3((count + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s,
                        guess_geom(h, p), groups, K, h->cfg.N, h->cfg.n_obst, keep_first ? 1 : 0, d_x0, d_obst, d_goal, d_offsets, d_X, d_U, d_offsets_out);
     HIPCHK(hipGetLastError());
@@ -871,9 +880,8 @@ int mpc_group_step_dev(mpc_handle *h, int groups, int K, const double *d_key, co
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = pick(h, stream);
     // the per-instance tables of the solve this step stands behind (r_hit rows, obstacle mask), with that solve's coverage checks
-    mpc::KParams p = solve_params(h, groups * K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    p.trace = nullptr;
-    rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc;
+    mpc::KParams p;
+    rc = beside_solve(h, groups * K, nullptr, nullptr, nullptr, s, true, p); if (rc) return rc;
     mpc::GroupStepArgs a;
     a.groups = groups; a.K = K; a.N = h->cfg.N; a.n_obst = h->cfg.n_obst; a.flags = flags;
     a.margin = incumbent_margin; a.dt = h->cfg.Tf / h->cfg.N; a.randomness = randomness; a.vmax = vmax;
@@ -907,10 +915,9 @@ int mpc_rollout_merit_dev(mpc_handle *h, int batch, int members, const double *d
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = pick(h, stream);
     // the constants and per-instance inputs of the solve that would be launched now: its kernel arguments, none of its outputs
-    mpc::KParams p = solve_params(h, batch, d_x0, d_P, nullptr, d_goal, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    p.trace = nullptr;
+    mpc::KParams p;
+    int rc = beside_solve(h, batch, d_x0, d_P, d_goal, s, true, p); if (rc) return rc;
     p.r_hit = 1.0 + 0.2;               // o.r + R_ROBOT, as mpc_closed_loop_step_dev sets it
-    int rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc;
     mpc::MeritArgs a = {d_U, d_X, d_merit, d_defect, d_margin, d_boxviol, d_Xr, members};
     hipLaunchKernelGGL(mpc::rollout_merit_kernel, dim3((batch + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, s, p, a);
     HIPCHK(hipGetLastError());
@@ -1272,9 +1279,8 @@ int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigne
     int rc = own(h, &h->d_refill_assign, (size_t)h->max_batch); if (rc) return rc;
     hipStream_t s = pick(h, stream);
     // the guess geometry reads the per-instance tables of the member solve (r_safe rows, obstacle mask), with that solve's coverage checks; off: none
-    mpc::KParams p = solve_params(h, groups * K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    p.trace = nullptr;
-    if (h->gg_mode) { rc = attach_inputs(h, p, s, kForSolve); if (rc) return rc; }
+    mpc::KParams p;
+    rc = beside_solve(h, groups * K, nullptr, nullptr, nullptr, s, h->gg_mode != 0, p); if (rc) return rc;
     hipLaunchKernelGGL(mpc::refill_decide_kernel, dim3(1), dim3(mpc::kRefillThreads), 0, s, groups, seed_count, max_steps, a->ep_flags, a->ep_steps,
                        h->d_refill_assign, a->cursor);
     mpc::GroupRefillArgs ga;

@@ -6,8 +6,11 @@ Output table columns are the reference's (src/simulation/robot_ocp_problem.py:27
 and `write_experiment` stores them as `;`-separated CSV + spec JSON like experiments.py:40-43, so tooling written for the
 reference's `test_data/` (evaluate_experiments.py:8-18) reads them.
 
-The two drivers, run_episodes (one batch) and run_seed_sweep (seeds streaming through slots), share the pieces below them: _HandleLease owns what a driver
-borrows on a handle, step_flags / refill_flags / result_table are the reference's protocol in one place each.
+Two loops carry four drivers: _episode_loop (one batch) runs run_episodes and multistart.run_multistart_episodes, _sweep_loop (seeds streaming through
+slots) runs run_seed_sweep and multistart.run_multistart_sweep.  A loop holds the protocol alone -- the step counter, when the host looks at the device and
+when it stops, the schedule a sweep records -- and a driver hands in its launches as callables; the loops touch no handle, so fakes on CPU tensors drive them.
+Below them the drivers share _HandleLease (what a driver borrows on a handle), _sweep_table (the parked rows of either sweep) and step_flags / refill_flags /
+result_table, the reference's protocol in one place each.
 """
 import json
 import os
@@ -158,33 +161,30 @@ def _compact(a, full):
     return True
 
 
-def _episode_loop(torch, m, a, draw, fl, max_iter, stream, log=None, rec=None, full=None):
-    """run_episodes' control steps: noise draw, fused step, the status log (torch ops on `log`), the clones of the record `rec`, the done-flag copy, the
-    compaction gathers (into `full`), until every episode has reached its goal or max_iter steps are spent.  Returns the steps launched."""
+def _episode_loop(torch, stream, max_iter, step, flags, every_25=None):
+    """The batch drivers' control steps: step(k) -- the driver's launches of control step k -- until every episode has reached its goal or max_iter steps are
+    spent.  flags(): the episodes' flag words as they stand (compaction rebinds them).  every_25(k), if given, stands in for the done-flag copy behind every
+    25th step (run_episodes' compaction, which reads the live count anyway); False: no episode is live.  Returns the steps launched."""
     # "every instance has reached its goal" without stalling the queue: every 25 control steps the flag goes to pinned host memory behind an event,
     # and is looked at only once that event has passed (so the loop runs at most ~25 steps longer than it has to -- on idle instances, which cost nothing)
-    done_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-    done_event = None
+    done_host = done_event = None
     k = 0
     while k < max_iter:
-        _fused_step(m, a, fl, draw(k), stream.cuda_stream)
-        if log is not None:      # (an episode that has reached its goal idles: its status word keeps the last solve's value and is not counted again)
-            live = (a.steps + (a.flags & 1)) > k
-            log.n2 += (live & (a.status == 2)).int(); log.n4 += (live & (a.status == 4)).int()
-            log.first_bad = torch.where(live & (a.status != 0) & (log.first_bad < 0), torch.full_like(log.first_bad, k), log.first_bad)
+        step(k)
         k += 1
-        if rec is not None:      # X holds the shifted prediction: stage j of the solve is X[j - 1], stage N is kept (:253-258)
-            rec.x.append(a.x0.clone()); rec.o.append(a.obst.clone()); rec.p.append(a.X.clone())
         if done_event is not None and done_event.query():
             if int(done_host[0]) == 1:
                 break
             done_event = None
-        if full is not None and k % 25 == 0:
-            if not _compact(a, full):
-                break
+        if k % 25 != 0:
             continue
-        if k % 25 == 0 and done_event is None:
-            done_host.copy_((a.flags & 1).min().to(torch.int32).reshape(1), non_blocking=True)
+        if every_25 is not None:
+            if not every_25(k):
+                break
+        elif done_event is None:
+            if done_host is None:      # (the first poll: a loop that ends before it needs no pinned memory)
+                done_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            done_host.copy_((flags() & 1).min().to(torch.int32).reshape(1), non_blocking=True)
             done_event = torch.cuda.Event(); done_event.record(stream)
     return k
 
@@ -268,7 +268,15 @@ def run_episodes(x0, goal, obst, N=20, Tf=2.0, max_iter=400, random_move=True, i
                 a.ids = torch.arange(B, device=dev)
                 full = {n: getattr(a, n).clone() for n in _PARKED}
             rec = SimpleNamespace(x=[a.x0.clone()], o=[a.obst.clone()], p=[]) if record else None
-            k = _episode_loop(torch, m, a, draw, fl, max_iter, stream, log=log, rec=rec, full=full)
+            def step(k):
+                _fused_step(m, a, fl, draw(k), s)
+                if log is not None:      # (an episode that has reached its goal idles: its status word keeps the last solve's value and is not counted again)
+                    live = (a.steps + (a.flags & 1)) > k
+                    log.n2 += (live & (a.status == 2)).int(); log.n4 += (live & (a.status == 4)).int()
+                    log.first_bad = torch.where(live & (a.status != 0) & (log.first_bad < 0), torch.full_like(log.first_bad, k), log.first_bad)
+                if rec is not None:      # X holds the shifted prediction: stage j of the solve is X[j - 1], stage N is kept (:253-258)
+                    rec.x.append(a.x0.clone()); rec.o.append(a.obst.clone()); rec.p.append(a.X.clone())
+            k = _episode_loop(torch, stream, max_iter, step, lambda: a.flags, every_25=None if full is None else lambda k: _compact(a, full))
             stream.synchronize()
             if full is not None:
                 for n in _PARKED:
@@ -535,27 +543,23 @@ def _attach_trace(lease, torch, a, tr, max_iter):
     return tarr, u0
 
 
-def _sweep_loop(torch, m, a, stream, scenario, first, per_seed, max_iter, poll_every, bound, fl, rf, ring_every=None, log=None, u0=None):
-    """the sweep's control steps, each one: ring fill (every ring_every steps; None: no ring), refill, poll copy, trace START (u0 given: a trace is attached),
-    fused step, status log (log given), trace STEP -- until the poll sees no live slot, or `bound` steps are spent whatever the device returns.
-    Returns (the fused steps launched, the schedule (count, 2) with poll_every = 1 or None)."""
-    s = stream.cuda_stream
-    schedule = np.full((a.count, 2), -1, dtype=np.int64) if poll_every == 1 else None
-    seen = np.full(a.rows, -1, dtype=np.int64)
-    live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
-    live_event = None
+def _sweep_loop(torch, stream, rows, count, slot_seed, cursor, poll_every, bound, refill, step):
+    """The sweep drivers' control steps, each one: refill(k) -- the driver's launches that park finished rows and start seeds, which leave the seed index of
+    every one of the `rows` slots (or groups) in slot_seed and the live count in cursor[1] --, the poll, the bound check, step(k) -- the driver's launches of
+    control step k -- until the poll sees no live row, or `bound` steps are spent whatever the device returns.
+    Returns (the steps launched, the schedule (count, 2) with poll_every = 1 or None)."""
+    schedule = np.full((count, 2), -1, dtype=np.int64) if poll_every == 1 else None
+    seen = np.full(rows, -1, dtype=np.int64)
+    live_host = live_event = None
     k = 0
     while True:
-        if ring_every is not None and k % ring_every == 0:
-            m.episode_ring_fill_dev(scenario, first, a.count, a.cursor, stream=s)
-        m.episode_refill_dev(a.rows, scenario, first, a.count, max_iter, a.start_rows, a.goal_rows, per_seed, a.x0, a.obst, a.goal, a.X, a.U, a.margin, a.flags,
-                             a.steps, a.gen_state, a.nbuf, a.slot_seed, a.cursor, a.res_f, a.res_i, flags=rf, stream=s)
+        refill(k)
         if poll_every == 1:
-            now = a.slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
+            now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
             new = (now != seen) & (now >= 0)
             schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
-            seen = now
-            if int(a.cursor[1].item()) == 0:
+            seen[:] = now                              # (by value: a host tensor's .cpu() is the tensor itself)
+            if int(cursor[1].item()) == 0:
                 break
         elif k % poll_every == 0:
             # the count of the poll before this one, which the device passed long ago: the host stays at most two polls ahead of the device (no idle
@@ -564,30 +568,33 @@ def _sweep_loop(torch, m, a, stream, scenario, first, per_seed, max_iter, poll_e
                 live_event.synchronize()
                 if int(live_host[0]) == 0:
                     break
-            live_host.copy_(a.cursor[1:2], non_blocking=True)
+            else:                                      # (the first poll of the event mode: the blocking mode needs no pinned memory)
+                live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
+            live_host.copy_(cursor[1:2], non_blocking=True)
             live_event = torch.cuda.Event(); live_event.record(stream)
         if k >= bound:
             break
-        if u0 is not None:           # the state every seed that has just started starts from: behind the refill, in front of the step
-            m.episode_trace_dev(a.rows, _lib.TRACE_START, a.slot_seed, a.x0, a.obst, ep_flags=a.flags, ep_steps=a.steps, stream=s)
-        _fused_step(m, a, fl, a.nbuf, s, u0=u0)
-        if log is not None:
-            m.episode_status_log_dev(a.rows, a.status, a.flags, a.steps, log, stream=s)
-        if u0 is not None:           # the step itself: the next refill overwrites a slot that has just finished
-            m.episode_trace_dev(a.rows, _lib.TRACE_STEP, a.slot_seed, a.x0, a.obst, a.X, u0, a.status, a.iters, a.flags, a.steps, stream=s)
+        step(k)
         k += 1
     return k, schedule
+
+
+def _sweep_table(cursor, res_i, res_f, goal, bound, noun):
+    """the parked rows of either sweep on the host, once its stream has drained: cursor[1] = the live count, res_f[k] = seed index k's min_margin and last state,
+    res_i[k] = its flag word, its step count and what the driver parks behind them (-1: not parked); noun: the driver's rows ("slots" | "groups").
+    Returns (table (count, 6), x_last (count, 5), the raw res_i) -- or MpcError: the sweep has not drained."""
+    left = int(cursor[1].item())
+    ri = res_i.cpu().numpy(); rfh = res_f.cpu().numpy()
+    if left != 0 or (ri[:, 0] < 0).any():
+        raise _lib.MpcError(f"the sweep did not drain within {bound} control steps ({left} {noun} live, {int((ri[:, 0] < 0).sum())} rows not parked)")
+    xl = np.ascontiguousarray(rfh[:, 1:6])
+    return result_table(ri[:, 0], rfh[:, 0], xl, np.ascontiguousarray(np.broadcast_to(goal, (ri.shape[0], 2)), dtype=np.float64), ri[:, 1]), xl, ri
 
 
 def _sweep_collect(a, goal, bound, tabs, seed_src, tarr, tr):
     """the sweep's results on the host, once its stream has drained: table and x_last from the parked rows, the status log, seed_src (None: not recorded),
     the traced rows cut to each seed's length -- held to the table's lengths.  Returns the result dict without steps_run and schedule."""
-    left = int(a.cursor[1].item())
-    ri = a.res_i.cpu().numpy(); rfh = a.res_f.cpu().numpy()
-    if left != 0 or (ri[:, 0] < 0).any():
-        raise _lib.MpcError(f"the sweep did not drain within {bound} control steps ({left} slots live, {int((ri[:, 0] < 0).sum())} rows not parked)")
-    xl = np.ascontiguousarray(rfh[:, 1:6])
-    table = result_table(ri[:, 0], rfh[:, 0], xl, np.ascontiguousarray(np.broadcast_to(goal, (a.count, 2)), dtype=np.float64), ri[:, 1])
+    table, xl, _ = _sweep_table(a.cursor, a.res_i, a.res_f, goal, bound, "slots")
     out = dict(table=table, x_last=xl, solves=int(table[:, 4].sum() + table[:, 1].sum()))
     if "res_log" in tabs:
         rl = tabs["res_log"].cpu().numpy()
@@ -675,8 +682,21 @@ def run_seed_sweep(start, goal, scenario, seeds, slots, N=20, Tf=2.0, n_obst=5, 
             tabs = _attach_tables(lease, torch, a, ft)
             ring = _attach_ring(lease, torch, a, ft["ring"]) if ft["ring"] is not None else None
             tarr, u0 = _attach_trace(lease, torch, a, tr, max_iter) if tr is not None else (None, None)
-            k, schedule = _sweep_loop(torch, m, a, stream, scenario, first, per_seed, max_iter, poll_every, bound, fl, rf,
-                                      ring_every=ft["ring_every"] if ring is not None else None, log=tabs.get("log"), u0=u0)
+            s, log, ring_every = stream.cuda_stream, tabs.get("log"), ft["ring_every"] if ring is not None else None
+            def refill(k):
+                if ring_every is not None and k % ring_every == 0:
+                    m.episode_ring_fill_dev(scenario, first, count, a.cursor, stream=s)
+                m.episode_refill_dev(S, scenario, first, count, max_iter, a.start_rows, a.goal_rows, per_seed, a.x0, a.obst, a.goal, a.X, a.U, a.margin, a.flags,
+                                     a.steps, a.gen_state, a.nbuf, a.slot_seed, a.cursor, a.res_f, a.res_i, flags=rf, stream=s)
+            def step(k):
+                if u0 is not None:           # the state every seed that has just started starts from: behind the refill, in front of the step
+                    m.episode_trace_dev(S, _lib.TRACE_START, a.slot_seed, a.x0, a.obst, ep_flags=a.flags, ep_steps=a.steps, stream=s)
+                _fused_step(m, a, fl, a.nbuf, s, u0=u0)
+                if log is not None:
+                    m.episode_status_log_dev(S, a.status, a.flags, a.steps, log, stream=s)
+                if u0 is not None:           # the step itself: the next refill overwrites a slot that has just finished
+                    m.episode_trace_dev(S, _lib.TRACE_STEP, a.slot_seed, a.x0, a.obst, a.X, u0, a.status, a.iters, a.flags, a.steps, stream=s)
+            k, schedule = _sweep_loop(torch, stream, S, count, a.slot_seed, a.cursor, poll_every, bound, refill, step)
             stream.synchronize()
             out = _sweep_collect(a, goal, bound, tabs, ring["seed_src"] if ring is not None and poll_every == 1 else None, tarr, tr)
     return dict(out, steps_run=k, schedule=schedule)

@@ -16,8 +16,9 @@ Nothing leaves the device between them: torch replicates the group inputs and ca
 The CLOSED LOOP has two forms.  step() composes a control step from the entry points above and the plant / obstacle / shift / seed launches.  step_fused()
 runs the member solve and then ONE launch, mpc_group_step_dev (select, plant, obstacles, episode bookkeeping per group, next iterates, the members' inputs;
 DESIGN.md section 4m), and run_multistart_episodes drives it to the reference's result table.  run_multistart_sweep streams more seeds than there are
-groups through the groups: a finished group starts the next seed on the device (mpc_group_refill_dev).  PipelinedMpc does not know
-about groups.
+groups through the groups: a finished group starts the next seed on the device (mpc_group_refill_dev).  Neither driver has a loop of
+its own: they hand their launches to episodes._episode_loop and episodes._sweep_loop, the two loops run_episodes and run_seed_sweep run on, and the sweep's
+rows come back through episodes._sweep_table.  PipelinedMpc does not know about groups.
 
 guess_geometry (off by default) replaces the fixed lateral offsets of members 1 .. K - 1 by amplitudes computed on the device from the obstacles that are in the
 way -- the pass-left / pass-right candidates of the nearest blocking obstacles (mpc_set_guess_geometry); `offsets` is then the base family a
@@ -212,6 +213,17 @@ class MultiStartMpc:
         _lib.check(_lib.lib().mpc_seed_guesses_dev(self.inner._h, self.G, self.K, x_rows.data_ptr(), goal_rows.data_ptr(), self.offsets.data_ptr(),
                                                    1 if keep_first else 0, self.X.data_ptr(), self.U.data_ptr(), s))
 
+    def _select_key(self, x, obst, goal, s):
+        """what the selection compares, behind the member solve: the costs it reports, or (select_by="rollout") the merits of predict_dev on the G group rows
+        `obst` and rollout_merit_dev on the members' (X, U) from the group rows x and goal.  The rows are made contiguous only where they are read (the
+        member-0 views of the replicated inputs are not; a caller's tensors are, and are passed as they are)."""
+        if self.select_by != "rollout":
+            return self.cand_cost
+        self.inner.predict_dev(self.G, obst.contiguous(), self._P, stream=s)
+        self.inner.rollout_merit_dev(self.B, x.contiguous(), self._P, goal.contiguous(), self.U, X=self.X, merit=self.cand_merit, defect=self.cand_defect,
+                                     margin=self.cand_margin, members=self.K, stream=s)
+        return self.cand_merit
+
     def _solve(self, x0, obstacles, goal, seed, keep_first, keep_solution, s):
         self._load(x0, obstacles, goal)
         if seed:
@@ -220,12 +232,7 @@ class MultiStartMpc:
                                         self.cand_iters, flags=0, stream=s)
         if keep_solution:
             self.solved_X, self.solved_U = self.X.clone(), self.U.clone()
-        by = self.cand_cost
-        if self.select_by == "rollout":
-            self.inner.predict_dev(self.G, self._obst[:, 0].contiguous(), self._P, stream=s)
-            self.inner.rollout_merit_dev(self.B, self._x0[:, 0].contiguous(), self._P, self._goal[:, 0].contiguous(), self.U, X=self.X, merit=self.cand_merit,
-                                         defect=self.cand_defect, margin=self.cand_margin, members=self.K, stream=s)
-            by = self.cand_merit
+        by = self._select_key(self._x0[:, 0], self._obst[:, 0], self._goal[:, 0], s)
         _lib.check(_lib.lib().mpc_select_best_dev(self.inner._h, self.G, self.K, by.data_ptr(), self.cand_status.data_ptr(), self.margin,
                                                   _lib.SELECT_BROADCAST, self.X.data_ptr(), self.U.data_ptr(), self.winner.data_ptr(),
                                                   self.cost.data_ptr(), self.u0.data_ptr(), self.cand_u0.data_ptr(), s))
@@ -348,11 +355,7 @@ class MultiStartMpc:
                 self._warm = self._fused_warm = True
             m.closed_loop_step_dev(B, self._x0, self._obst, self._goal, self.X, self.U, self.cand_u0, self.cand_cost, self.cand_status, self.cand_iters,
                                    flags=_lib.STEP_METRICS, min_margin=self._scratch_margin, ep_flags=self.member_flags, ep_steps=self._scratch_steps, stream=s)
-            by = self.cand_cost
-            if self.select_by == "rollout":
-                m.predict_dev(G, obst, self._P, stream=s)
-                m.rollout_merit_dev(B, x, self._P, goal, self.U, X=self.X, merit=self.cand_merit, defect=self.cand_defect, margin=self.cand_margin, members=K, stream=s)
-                by = self.cand_merit
+            by = self._select_key(x, obst, goal, s)
             _lib.check(_lib.lib().mpc_group_step_dev(m._h, G, K, by.data_ptr(), self.cand_status.data_ptr(), self.cand_u0.data_ptr(), self.margin,
                                                      _lib.GROUP_MARGIN_ALL if margin_all else 0, x.data_ptr(), obst.data_ptr(), goal.data_ptr(),
                                                      self.offsets.data_ptr(), None if noise is None else noise.data_ptr(), randomness, vmax,
@@ -364,6 +367,35 @@ class MultiStartMpc:
     def iterates(self):
         """the iterates of all members as they stand, (G, K, N + 1, 5) and (G, K, N, 2) device views"""
         return self.X.view(self.G, self.K, self.N + 1, 5), self.U.view(self.G, self.K, self.N, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the group drivers' argument checks
+def _check_n_obst(n_obst):
+    if isinstance(n_obst, bool) or int(n_obst) != n_obst or not 1 <= int(n_obst) <= 32:
+        raise ValueError(f"n_obst must be a whole number in 1 .. 32, got {n_obst!r}")
+    return int(n_obst)
+
+
+def _check_sqp(sqp):
+    if sqp is not None and (not hasattr(sqp, "__len__") or len(sqp) != 2):
+        raise ValueError("sqp must be None or (max_iter, step_tol)")
+
+
+def _check_solver(solver, G, off, margin, select_by, geometry, n_obst=None):
+    """a caller's handle (None: the driver makes its own) is the one the call asks for: G groups, the offsets, margin, select_by and guess geometry; n_obst
+    given: that obstacle count too (a batch of groups has its own; a sweep takes the handle's) -- or ValueError, in the words of the driver that asks"""
+    if solver is None:
+        return
+    if not isinstance(solver, MultiStartMpc):
+        raise ValueError("solver must be a MultiStartMpc (the groups' own handle)")
+    holds = f"offsets {solver.offsets_host.tolist()}, margin {solver.margin}, select_by {solver.select_by!r}"
+    if (solver.G != G or (n_obst is not None and solver.n_obst != n_obst) or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin
+            or solver.select_by != select_by):
+        if n_obst is not None:
+            raise ValueError(f"solver holds {solver.G} groups of {solver.n_obst} obstacles, {holds}: not what this call asks for")
+        raise ValueError(f"solver holds {solver.G} groups, {holds}: this call asks for {G} group slots, offsets {off.tolist()}, margin {margin}, select_by {select_by!r}")
+    if solver.guess_geometry != geometry:
+        raise ValueError(f"solver has guess_geometry {solver.guess_geometry}: this call asks for {geometry}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------- episodes of groups
@@ -387,9 +419,7 @@ def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=
     if scenario is not None:
         if scenario not in BatchedMpc.SCENARIOS:
             raise ValueError(f"unknown scenario {scenario!r}: one of {sorted(BatchedMpc.SCENARIOS)}")
-        if isinstance(n_obst, bool) or int(n_obst) != n_obst or not 1 <= int(n_obst) <= 32:
-            raise ValueError(f"n_obst must be a whole number in 1 .. 32, got {n_obst!r}")
-        n_obst, obst = int(n_obst), None
+        n_obst, obst = _check_n_obst(n_obst), None
     else:
         obst = np.ascontiguousarray(obst, dtype=np.float64)
         if obst.ndim != 3 or obst.shape[0] != G or obst.shape[2] != 4 or not 1 <= obst.shape[1] <= 32:
@@ -400,8 +430,7 @@ def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=
     if isinstance(first_seed, bool) or int(first_seed) != first_seed or not 0 <= int(first_seed) or int(first_seed) + G > 2 ** 32:
         raise ValueError("first_seed .. first_seed + G - 1 must be numpy seeds in [0, 2^32)")
     noise = _episode_noise(noise, scenario, 0, bool(random_move), int(max_iter), G, n_obst)
-    if sqp is not None and (not hasattr(sqp, "__len__") or len(sqp) != 2):
-        raise ValueError("sqp must be None or (max_iter, step_tol)")
+    _check_sqp(sqp)
     for name, a in (("r_safe", r_safe), ("r_hit", r_hit)):
         if a is not None:
             a = np.asarray(a, dtype=np.float64)
@@ -409,14 +438,7 @@ def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=
                 raise ValueError(f"{name} must be ({G},) or ({G}, {n_obst}) finite radii > 0 (one row per group), got shape {a.shape}")
     if active is not None and (np.asarray(active).shape != (G, n_obst) or np.asarray(active).dtype != np.bool_):
         raise ValueError(f"active must be a bool array ({G}, {n_obst}) (one row per group), got {np.asarray(active).dtype} {np.asarray(active).shape}")
-    if solver is not None:
-        if not isinstance(solver, MultiStartMpc):
-            raise ValueError("solver must be a MultiStartMpc (the groups' own handle)")
-        if (solver.G, solver.n_obst) != (G, n_obst) or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin or solver.select_by != select_by:
-            raise ValueError(f"solver holds {solver.G} groups of {solver.n_obst} obstacles, offsets {solver.offsets_host.tolist()}, margin {solver.margin}, "
-                             f"select_by {solver.select_by!r}: not what this call asks for")
-        if solver.guess_geometry != geometry:
-            raise ValueError(f"solver has guess_geometry {solver.guess_geometry}: this call asks for {geometry}")
+    _check_solver(solver, G, off, margin, select_by, geometry, n_obst=n_obst)
     return dict(G=G, K=K, n_obst=n_obst, x0=x0, goal=goal, obst=obst, scenario=scenario, offsets=off, margin=margin, select_by=select_by, max_iter=int(max_iter),
                 noise=noise, first_seed=int(first_seed), guess_geometry=geometry)
 
@@ -442,7 +464,7 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
     Returns dict(table (G, 6) = [hit, reached, min_margin, dist_to_goal, iters, out_of_bounds] (episodes.result_table), x_last (G, 5), steps_run, solves = the
     member solves of running groups = K (sum of table[:, 4] + table[:, 1]), lost_steps (G,): control steps on which no member was eligible, switched_steps (G,):
     control steps on which the winner was not member 0)."""
-    from .episodes import _HandleLease, _noise_source, result_table
+    from .episodes import _HandleLease, _episode_loop, _noise_source, result_table
     from types import SimpleNamespace
     a = episode_arguments(x0, goal, obst, offsets, incumbent_margin, select_by, n_obst, max_iter, random_move, first_seed, noise, sqp, r_safe, r_hit, active, solver,
                           guess_geometry)
@@ -473,20 +495,10 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
             ms._group_arrays()
             rows = SimpleNamespace(rows=G, obst=dobst, flags=ms.ep_flags, f64=f64, gen_state=None, nbuf=None)
             draw = _noise_source(torch, ms.inner, rows, a["noise"], a["scenario"], a["first_seed"], 0, s)
-            done_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-            done_event = None
-            k = 0
-            while k < a["max_iter"]:
+            def step(k):
                 nz = draw(k)
                 ms.step_fused(x, dobst, dgoal, noise=None if nz is None else nz.contiguous(), margin_all=bool(margin_all) and active is not None)
-                k += 1
-                if done_event is not None and done_event.query():
-                    if int(done_host[0]) == 1:
-                        break
-                    done_event = None
-                if k % 25 == 0 and done_event is None:
-                    done_host.copy_((ms.ep_flags & 1).min().to(torch.int32).reshape(1), non_blocking=True)
-                    done_event = torch.cuda.Event(); done_event.record(ms.stream)
+            k = _episode_loop(torch, ms.stream, a["max_iter"], step, lambda: ms.ep_flags)
             ms.stream.synchronize()
             xl = x.cpu().numpy()
             table = result_table(ms.ep_flags.cpu().numpy(), ms.min_margin.cpu().numpy(), xl, a["goal"], ms.ep_steps.cpu().numpy())
@@ -508,19 +520,11 @@ def sweep_arguments(start, goal, scenario, seeds, slots, offsets=DEFAULT_OFFSETS
     off, margin, select_by = check_offsets(offsets), check_margin(incumbent_margin), check_select_by(select_by)
     geometry = check_guess_geometry(guess_geometry)
     first, count, start, goal, per_seed = _sweep_arguments(start, goal, scenario, seeds, slots, max_iter, poll_every)
-    if isinstance(n_obst, bool) or int(n_obst) != n_obst or not 1 <= int(n_obst) <= 32:
-        raise ValueError(f"n_obst must be a whole number in 1 .. 32, got {n_obst!r}")
-    if sqp is not None and (not hasattr(sqp, "__len__") or len(sqp) != 2):
-        raise ValueError("sqp must be None or (max_iter, step_tol)")
+    n_obst = _check_n_obst(n_obst)
+    _check_sqp(sqp)
     S, K = min(int(slots), count), int(off.shape[0])
+    _check_solver(solver, S, off, margin, select_by, geometry)
     if solver is not None:
-        if not isinstance(solver, MultiStartMpc):
-            raise ValueError("solver must be a MultiStartMpc (the groups' own handle)")
-        if solver.G != S or solver.offsets_host.tolist() != off.tolist() or solver.margin != margin or solver.select_by != select_by:
-            raise ValueError(f"solver holds {solver.G} groups, offsets {solver.offsets_host.tolist()}, margin {solver.margin}, select_by {solver.select_by!r}: "
-                             f"this call asks for {S} group slots, offsets {off.tolist()}, margin {margin}, select_by {select_by!r}")
-        if solver.guess_geometry != geometry:
-            raise ValueError(f"solver has guess_geometry {solver.guess_geometry}: this call asks for {geometry}")
         n_obst = solver.n_obst
     return dict(first=first, count=count, start=start, goal=goal, per_seed=per_seed, S=S, K=K, n_obst=int(n_obst), offsets=off, margin=margin, select_by=select_by,
                 max_iter=int(max_iter), poll_every=int(poll_every), bound=-(-count // S) * int(max_iter) + int(poll_every), guess_geometry=geometry)
@@ -573,7 +577,7 @@ def run_multistart_sweep(start, goal, scenario, seeds, slots, offsets=DEFAULT_OF
         raise TypeError(f"run_multistart_sweep has no argument {not_offered[0]!r}: per-seed feature tables, the status log, the ring and the trace are "
                         "run_seed_sweep's, and a batch's arguments are run_multistart_episodes'")
     a = sweep_arguments(start, goal, scenario, seeds, slots, offsets, incumbent_margin, select_by, n_obst, max_iter, sqp, poll_every, solver, guess_geometry)
-    from .episodes import _HandleLease, result_table
+    from .episodes import _HandleLease, _sweep_loop, _sweep_table
     import torch
     S, K, count, no, poll = a["S"], a["K"], a["count"], a["n_obst"], a["poll_every"]
     make = lambda: MultiStartMpc(N, no, Tf, scenarios=S, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"],
@@ -588,42 +592,14 @@ def run_multistart_sweep(start, goal, scenario, seeds, slots, offsets=DEFAULT_OF
             with torch.cuda.stream(ms.stream):
                 s = ms.stream.cuda_stream
                 st = _sweep_state(torch, ms, a, scenario, random_move)
-                x, dobst, dgoal, nbuf, slot_seed, cursor = st.x, st.obst, st.goal, st.nbuf, st.slot_seed, st.cursor
-                schedule = np.full((count, 2), -1, dtype=np.int64) if poll == 1 else None
-                seen = np.full(S, -1, dtype=np.int64)
-                live_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
-                live_event = None
-                k = 0
-                while True:
-                    st.refill(s)
-                    if poll == 1:
-                        now = slot_seed.cpu().numpy()              # (blocking: this is the mode that records the schedule, not the one that is timed)
-                        new = (now != seen) & (now >= 0)
-                        schedule[now[new], 0] = np.nonzero(new)[0]; schedule[now[new], 1] = k
-                        seen = now
-                        if int(cursor[1].item()) == 0:
-                            break
-                    elif k % poll == 0:      # the count of the poll before this one (episodes._sweep_loop: the host stays at most two polls ahead of the device)
-                        if live_event is not None:
-                            live_event.synchronize()
-                            if int(live_host[0]) == 0:
-                                break
-                        live_host.copy_(cursor[1:2], non_blocking=True)
-                        live_event = torch.cuda.Event(); live_event.record(ms.stream)
-                    if k >= a["bound"]:
-                        break
-                    if nbuf is not None:
-                        ms.inner.noise_draw_dev(S, st.state, nbuf, ep_flags=ms.ep_flags, stream=s)
-                    ms.step_fused(x, dobst, dgoal, noise=nbuf)
-                    k += 1
+                def step(k):
+                    if st.nbuf is not None:
+                        ms.inner.noise_draw_dev(S, st.state, st.nbuf, ep_flags=ms.ep_flags, stream=s)
+                    ms.step_fused(st.x, st.obst, st.goal, noise=st.nbuf)
+                k, schedule = _sweep_loop(torch, ms.stream, S, count, st.slot_seed, st.cursor, poll, a["bound"], lambda k: st.refill(s), step)
                 ms.stream.synchronize()
-                left = int(cursor[1].item())
-                ri, rf = st.res_i.cpu().numpy(), st.res_f.cpu().numpy()
-                if left != 0 or (ri[:, 0] < 0).any():
-                    raise _lib.MpcError(f"the sweep did not drain within {a['bound']} control steps ({left} groups live, {int((ri[:, 0] < 0).sum())} rows not parked)")
+                table, xl, ri = _sweep_table(st.cursor, st.res_i, st.res_f, a["goal"], a["bound"], "groups")
         finally:
             ms.restart()
-    xl = np.ascontiguousarray(rf[:, 1:6])
-    table = result_table(ri[:, 0], rf[:, 0], xl, np.ascontiguousarray(np.broadcast_to(a["goal"], (count, 2)), dtype=np.float64), ri[:, 1])
     return dict(table=table, x_last=xl, steps_run=k, solves=K * int(table[:, 4].sum() + table[:, 1].sum()), lost_steps=ri[:, 2].copy(), switched_steps=ri[:, 3].copy(),
                 schedule=schedule)

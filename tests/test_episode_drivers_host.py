@@ -1,5 +1,6 @@
 """The episode drivers' shared core without a device: the lease that owns what a driver borrows on a handle (with a fake solver that records calls),
-run_episodes' refusals that need no device, and the one set of shape rules behind BatchedMpc's setters and run_seed_sweep's per-seed tables."""
+run_episodes' refusals that need no device, the one set of shape rules behind BatchedMpc's setters and run_seed_sweep's per-seed tables, and the two
+loops the four drivers run on (_sweep_loop, _episode_loop) with the sweeps' shared collect (_sweep_table), driven by fakes on CPU tensors."""
 import ctypes as C
 
 import numpy as np
@@ -231,3 +232,106 @@ def test_bounds_groups_are_normalised_alike_on_both_sides(ep, monkeypatch, name,
             ep._sweep_features(COUNT, NO, ep.DEFAULT_BOUNDS, bounds={name: bad})
     with pytest.raises(ValueError, match=f"per-seed {name} has {COUNT + 1} rows for {COUNT} seeds"):
         ep._sweep_features(COUNT, NO, ep.DEFAULT_BOUNDS, bounds={name: np.full((COUNT + 1, cols), value)})
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. the two loops, on fakes
+LENGTHS = [2, 5, 1, 3, 3, 1, 4, 2]          # the control steps seed index k runs; every episode ends on its goal
+ROWS = {"slots": 2, "groups": 4}            # the res_i columns of run_seed_sweep's rows and of run_multistart_sweep's (lost and switched behind them)
+
+
+class FakeSweep:
+    """a sweep's device side on CPU tensors: `refill` is the refill's rule (multistart_sweep_cases.decide, then park / drain / start on the bookkeeping
+    words alone), `step` one control step of every running row; both record their call"""
+
+    def __init__(self, torch, lengths, S, cols):
+        i32 = dict(dtype=torch.int32)
+        self.torch, self.lengths, self.S, self.cols, self.calls = torch, lengths, S, cols, []
+        self.flags, self.steps, self.slot_seed, self.cursor = torch.ones(S, **i32), torch.zeros(S, **i32), torch.full((S,), -1, **i32), torch.zeros(2, **i32)
+        self.res_f, self.res_i = torch.full((len(lengths), 6), float("nan"), dtype=torch.float64), torch.full((len(lengths), cols), -1, **i32)
+
+    def refill(self, k):
+        import multistart_sweep_cases as sc
+        self.calls.append("refill")
+        assign, cursor = sc.decide(self.flags.numpy(), self.steps.numpy(), int(self.cursor[0]), len(self.lengths), 10 ** 6)
+        for g, s in enumerate(assign.tolist()):
+            if s == sc.KEEP:
+                continue
+            old = int(self.slot_seed[g])
+            if old >= 0:          # park: margin 1 + seed, last state (seed, ...), flags, steps and, for groups, lost = seed and switched = 2 seed
+                self.res_f[old] = self.torch.tensor([1.0 + old] + [float(old)] * 5, dtype=self.torch.float64)
+                self.res_i[old] = self.torch.tensor([int(self.flags[g]), int(self.steps[g]), old, 2 * old][:self.cols], dtype=self.torch.int32)
+            if s == sc.DRAIN:
+                self.slot_seed[g] = -1; self.flags[g] |= 1
+            else:
+                self.slot_seed[g] = s; self.flags[g] = 0; self.steps[g] = 0
+        self.cursor[:] = self.torch.from_numpy(cursor)
+
+    def step(self, k):
+        self.calls.append("step")
+        for g in range(self.S):
+            if int(self.flags[g]) & 1:
+                continue
+            ran = int(self.steps[g]) + 1
+            if ran == self.lengths[int(self.slot_seed[g])]:
+                self.flags[g] |= 1          # (the step that reaches the goal is not counted)
+            else:
+                self.steps[g] = ran
+
+
+@pytest.mark.parametrize("noun", list(ROWS))
+def test_the_sweep_loop_records_the_models_schedule_and_calls_refill_step_in_turn(ep, no_device, noun):
+    import torch
+    S = 3
+    f = FakeSweep(torch, LENGTHS, S, ROWS[noun])
+    k, schedule = ep._sweep_loop(torch, None, S, len(LENGTHS), f.slot_seed, f.cursor, 1, 100, f.refill, f.step)
+    want = ep.refill_schedule(LENGTHS, S)
+    assert len(set(LENGTHS)) >= 3 and k == want["steps"]
+    assert np.array_equal(schedule[:, 0], want["slot"]) and np.array_equal(schedule[:, 1], want["start"])
+    assert f.calls == ["refill", "step"] * k + ["refill"]          # one refill per step, and the one that sees no live row
+    # the rows the fake has parked, through the drivers' shared collect
+    goal = np.array([[3.0, 4.0]])
+    table, xl, ri = ep._sweep_table(f.cursor, f.res_i, f.res_f, goal, 100, noun)
+    seeds = np.arange(len(LENGTHS))
+    assert np.array_equal(table[:, 4] + table[:, 1], LENGTHS) and np.array_equal(table[:, 2], 1.0 + seeds) and np.array_equal(xl, np.repeat(seeds[:, None], 5, axis=1))
+    assert ri.shape == (len(LENGTHS), ROWS[noun]) and (noun == "slots" or (np.array_equal(ri[:, 2], seeds) and np.array_equal(ri[:, 3], 2 * seeds)))
+
+
+def test_the_sweep_loop_stops_at_its_bound_whatever_the_cursor_says(ep, no_device):
+    import torch
+    calls, bound = [], 5
+    slot_seed, cursor = torch.full((2,), -1, dtype=torch.int32), torch.tensor([0, 1], dtype=torch.int32)          # cursor[1]: a row that never finishes
+    k, schedule = ep._sweep_loop(torch, None, 2, 4, slot_seed, cursor, 1, bound, lambda k: calls.append(("refill", k)), lambda k: calls.append(("step", k)))
+    assert k == bound and [c for c in calls if c[0] == "step"] == [("step", j) for j in range(bound)]
+    assert [c for c in calls if c[0] == "refill"] == [("refill", j) for j in range(bound + 1)] and (schedule == -1).all()
+
+
+def test_the_episode_loop_runs_max_iter_steps_and_needs_no_pinned_memory_before_its_first_poll(ep, no_device):
+    import torch
+
+    def flags():
+        raise AssertionError("no poll is due before control step 25")
+    ks = []
+    assert ep._episode_loop(torch, None, 7, ks.append, flags) == 7 and ks == list(range(7))
+    # the hook that stands in for the poll (run_episodes' compaction): called behind every 25th step, and its False ends the loop
+    ks, hooked = [], []
+    assert ep._episode_loop(torch, None, 60, ks.append, flags, every_25=lambda k: hooked.append(k) or k < 50) == 50
+    assert ks == list(range(50)) and hooked == [25, 50]
+
+
+@pytest.mark.parametrize("noun", list(ROWS))
+def test_the_shared_collect_refuses_a_sweep_that_has_not_drained_and_builds_result_table(ep, no_device, noun):
+    import torch
+    from mpc_gpu._lib import MpcError
+    rng = np.random.default_rng(7)
+    count, cols = 5, ROWS[noun]
+    ri = np.column_stack([rng.integers(0, 8, count), rng.integers(0, 30, count)] + [rng.integers(0, 9, count)] * (cols - 2)).astype(np.int32)
+    rf = rng.uniform(-3.0, 3.0, (count, 6))
+    for goal in (rng.uniform(-7.0, 7.0, (1, 2)), rng.uniform(-7.0, 7.0, (count, 2))):          # one goal row for all seeds, and one per seed
+        table, xl, raw = ep._sweep_table(torch.tensor([count, 0], dtype=torch.int32), torch.from_numpy(ri), torch.from_numpy(rf), goal, 40, noun)
+        assert np.array_equal(table, ep.result_table(ri[:, 0], rf[:, 0], rf[:, 1:6], np.broadcast_to(goal, (count, 2)), ri[:, 1]))
+        assert np.array_equal(xl, rf[:, 1:6]) and xl.flags["C_CONTIGUOUS"] and np.array_equal(raw, ri) and table.shape == (count, 6)
+    unparked = ri.copy(); unparked[3] = -1
+    with pytest.raises(MpcError, match=rf"did not drain within 40 control steps \(0 {noun} live, 1 rows not parked\)"):
+        ep._sweep_table(torch.tensor([count, 0], dtype=torch.int32), torch.from_numpy(unparked), torch.from_numpy(rf), goal, 40, noun)
+    with pytest.raises(MpcError, match=rf"did not drain within 40 control steps \(2 {noun} live, 0 rows not parked\)"):
+        ep._sweep_table(torch.tensor([count, 2], dtype=torch.int32), torch.from_numpy(ri), torch.from_numpy(rf), goal, 40, noun)
