@@ -2,46 +2,39 @@
 
 For each cell the same seeded batch is solved on the handle path and on the per-instance path with arrays that repeat the handle's own weights and
 radius (the same problems, the same iterations: the ratio is the cost of the path, not of other parameters); each rep is reset_guess + `--solves`
-warm-started RTI solves through the device API, timed with HIP events on the solve stream.  The two modes alternate rep by rep.  The handle path's
-device code is that of the build without the feature.  Writes one JSON (default profiles/instance_params_rates.json).
+warm-started RTI solves through the device API, timed on the solve stream by scripts/measure.py's protocol (HIP event window, the two modes alternating
+rep by rep).  The handle path's device code is that of the build without the feature.  Writes one JSON (default profiles/instance_params_rates.json).
 
     python scripts/instance_params_rate.py [--reps 5] [--solves 20] [--out profiles/instance_params_rates.json]
 """
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+import measure
 
 CELLS = [("C2", 1024, 20, 3), ("C3", 65536, 20, 3), ("C5", 32768, 50, 10), ("wide", 4096, 30, 20)]
+MODES = ("handle", "inst")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--solves", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "instance_params_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "instance_params_rates.json"))
     a = ap.parse_args()
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
     from helpers import random_batch
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     dev = torch.device("cuda", 0)
     rows = []
     for name, B, N, no in CELLS:
         Tf = 0.1 * N
         x0, goal, obst = random_batch(B, no, seed=2024 + B + N)
         res = {}
-        # a stream of its own: the legacy default stream's handle is 0, which the library reads as the handle's own stream (the events would then time
-        # the enqueue only)
-        with mpc_gpu.BatchedMpc(N, no, Tf, max_batch=B) as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-            st = torch.cuda.current_stream()
-            assert st.cuda_stream != 0
+        with mpc_gpu.BatchedMpc(N, no, Tf, max_batch=B) as s, measure.own_stream(torch) as st:
             cs = st.cuda_stream
             tx, to, tg = (torch.tensor(v, device=dev) for v in (x0, obst, goal))
             X = torch.zeros((B, N + 1, 5), dtype=torch.float64, device=dev); U = torch.zeros((B, N, 2), dtype=torch.float64, device=dev)
@@ -51,35 +44,24 @@ def main():
             s.predict_dev(B, to, P, stream=cs)
             W = np.tile([s.cfg.W[k] for k in range(6)], (B, 1)); We = np.tile([s.cfg.We[k] for k in range(4)], (B, 1))
             rs = np.full((B, no), float(s.cfg.r_safe))
-            names, times, its = {}, {"handle": [], "inst": []}, {"handle": [], "inst": []}
-            for rep in range(a.reps + 1):            # rep 0: warm-up of both modes
-                for mode in ("handle", "inst"):
-                    if mode == "inst":
-                        s.set_instance_params(W=W, We=We, r_safe=rs)
-                    else:
-                        s.set_instance_params()
+            names = {}
+
+            def rep(mode):      # (seconds per solve, mean iterations of the last solve)
+                def prepare():
+                    s.set_instance_params(**(dict(W=W, We=We, r_safe=rs) if mode == "inst" else {}))
                     names[mode] = s.kernel_name(B, lookahead=False)
                     s.reset_guess_dev(B, tx, X, U, stream=cs)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(st)
-                    tot = 0
-                    for _ in range(a.solves):
-                        s.solve_dev(B, tx, P, tg, X, U, u0, cost, status, iters, stream=cs)
-                    e1.record(st)
-                    torch.cuda.synchronize()
-                    if rep:
-                        times[mode].append(e0.elapsed_time(e1) / 1e3)
-                        its[mode].append(float(iters.double().mean()))
-            for mode in ("handle", "inst"):
-                ts = np.array(times[mode])
-                res[mode] = dict(kernel=names[mode], solves_per_s=B * a.solves / float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
-                                 mean_iters_last_solve=float(np.mean(its[mode])))
+                ms = measure.window(torch, st, lambda: s.solve_dev(B, tx, P, tg, X, U, u0, cost, status, iters, stream=cs), a.solves, prepare)
+                return ms / 1e3, float(iters.double().mean())
+
+            runs = measure.alternate({m: (lambda m=m: rep(m)) for m in MODES}, a.reps)
+            for mode in MODES:
+                sec, spread = measure.summary([r[0] for r in runs[mode]])
+                res[mode] = dict(kernel=names[mode], solves_per_s=B / sec, spread=spread, mean_iters_last_solve=float(np.mean([r[1] for r in runs[mode]])))
         res["inst_over_handle"] = res["inst"]["solves_per_s"] / res["handle"]["solves_per_s"]
         rows.append(dict(cell=name, batch=B, N=N, n_obst=no, **res))
         print(json.dumps(rows[-1]), flush=True)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(dict(reps=a.reps, solves_per_rep=a.solves, cells=rows), f, indent=1)
+    measure.write_json(a.out, dict(reps=a.reps, solves_per_rep=a.solves, cells=rows))
 
 
 if __name__ == "__main__":

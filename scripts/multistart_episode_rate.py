@@ -11,7 +11,7 @@ and spread (max - min over median) of `--reps` reps.
 (b) CLOSED-LOOP OUTCOME at the reference's 1000 seeds, recorded and not asserted: section 5h(b)'s four rows (K = 1; K = 5 with incumbent_margin 0, 0.1, 0.5)
     through run_multistart_episodes (start [-7, -7, pi/4, 0, 0], goal [7, 7], RANDOM, 5 obstacles, the reference's noise stream, 400 steps at most), and
     select_by="rollout" for the two margin rows.
-(c) bench.py --gpus 1 --steps 20 --warmup 5 with the parent commit's library (`--parent-lib PATH`) and this one's, alternating (scripts/rollout_merit_rate.py's
+(c) bench.py --gpus 1 --steps 20 --warmup 5 with the parent commit's library (`--parent-lib PATH`) and this one's, alternating (scripts/measure.py's
     bench_ab): the flagship path launches nothing of this change.
 (d) the largest difference between the fused tail and the composition over the lockstep shapes of tests/test_gpu_multistart_episodes.py.
 
@@ -20,13 +20,11 @@ and spread (max - min over median) of `--reps` reps.
 import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "scripts")]
+import measure
 
 GROUPS = (1024, 13107)      # x K = 5: 5120 and 65535 instances
 N, NO, TF = 20, 3, 2.0
@@ -40,8 +38,8 @@ def step_times(a, torch, mpc_gpu):
         x0, goal, obst0 = random_batch(G, NO, seed=4242 + G)
         x0[:, 3:] = 0.0
         with mpc_gpu.MultiStartMpc(N, NO, TF, scenarios=G) as ms:
-            K, B, st = ms.K, ms.B, ms.stream
-            with torch.cuda.stream(st):
+            K, B = ms.K, ms.B
+            with measure.own_stream(torch, ms.stream) as st:
                 cs = st.cuda_stream
                 up = lambda h: torch.from_numpy(np.ascontiguousarray(h)).to(ms.dev)
                 x_init, o_init, dgoal = up(x0), up(obst0), up(goal)
@@ -51,16 +49,8 @@ def step_times(a, torch, mpc_gpu):
                     ms.restart()
                     x.copy_(x_init); ob.copy_(o_init)
 
-                def timed(body, prepare):
-                    prepare()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(st)
-                    for _ in range(a.launches):
-                        body()
-                    e1.record(st)
-                    torch.cuda.synchronize()
-                    return e0.elapsed_time(e1) * 1e3 / a.launches      # microseconds per control step
+                def us(body, prepare):      # microseconds per control step
+                    return lambda: 1e3 * measure.window(torch, st, body, a.launches, prepare)
 
                 def solve():
                     ms.inner.closed_loop_step_dev(B, ms._x0, ms._obst, ms._goal, ms.X, ms.U, ms.cand_u0, ms.cand_cost, ms.cand_status, ms.cand_iters, flags=0, stream=cs)
@@ -74,17 +64,11 @@ def step_times(a, torch, mpc_gpu):
                     start()
                     ms.step_fused(x, ob, dgoal)
 
-                t = dict(composed=[], fused=[], solve=[], tail=[])
-                for rep in range(a.reps + 1):      # rep 0 warms every launch up
-                    r = dict(composed=timed(lambda: ms.step(x, ob, dgoal), start), fused=timed(lambda: ms.step_fused(x, ob, dgoal), start),
-                             solve=timed(solve, prepare_solved), tail=timed(tail, prepare_solved))
-                    if rep:
-                        for k, v in r.items():
-                            t[k].append(v)
+                t = measure.alternate(dict(composed=us(lambda: ms.step(x, ob, dgoal), start), fused=us(lambda: ms.step_fused(x, ob, dgoal), start),
+                                           solve=us(solve, prepare_solved), tail=us(tail, prepare_solved)), a.reps)
                 idle = int((ms.ep_flags & 1).sum().item())
                 kernel = ms.inner.kernel_name(B)
-            med = {k: float(np.median(v)) for k, v in t.items()}
-            spread = {k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()}
+            med, spread = measure.summaries(t)
             row_bytes = 8 * (5 * (N + 1) + 2 * N)
             # read: the winner's row, K (key, status), the u0 row, x, goal, obstacles, bookkeeping; written: K rows, x, obstacles, the members' inputs, bookkeeping
             moved = G * (row_bytes + K * 12 + 16 + 40 + 16 + NO * 32 + 24 + K * row_bytes + 40 + NO * 32 + K * (40 + NO * 32 + 16 + 4) + 44)
@@ -136,24 +120,19 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--bench-rounds", type=int, default=3)
     ap.add_argument("--this-first", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multistart_episode_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "multistart_episode_rates.json"))
     a = ap.parse_args()
     parts = a.part or (["a", "b", "d"] + (["c"] if a.parent_lib else []))
-    res = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    res = measure.read_json(a.out)
     if set(parts) & {"a", "b", "d"}:
-        import torch
+        torch = measure.require_gpu()
         import mpc_gpu
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU: this script measures on the device only")
         for part, name, fn in (("a", "step_times", step_times), ("b", "closed_loop", closed_loop), ("d", "lockstep", lockstep_difference)):
             if part in parts:
                 res[name] = fn(a, torch, mpc_gpu)
     if "c" in parts:
-        from rollout_merit_rate import bench_ab
-        res["bench"] = bench_ab(a)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+        res["bench"] = measure.bench_ab(a.parent_lib, a.bench_rounds, a.this_first)
+    measure.write_json(a.out, res)
 
 
 if __name__ == "__main__":

@@ -19,12 +19,10 @@ DESIGN.md sections 4o and 5l).
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+import measure
 
 GROUPS = (1024, 13107)      # x K = 5: 5120 and 65535 instances
 OBSTACLES = (3, 10)
@@ -44,8 +42,8 @@ def launch_times(a, torch, mpc_gpu):
                 x0[:, 3:] = 0.0
                 kw = dict(guess_geometry=mode) if has_mode else {}
                 with mpc_gpu.MultiStartMpc(N, no, TF, scenarios=G, **kw) as ms:
-                    K, st = ms.K, ms.stream
-                    with torch.cuda.stream(st):
+                    K = ms.K
+                    with measure.own_stream(torch, ms.stream) as st:
                         cs = st.cuda_stream
                         dev = ms.dev
                         x, ob, gl = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, obst, goal))
@@ -67,31 +65,17 @@ def launch_times(a, torch, mpc_gpu):
                             ms.ep_flags.fill_(1)
                             sw.refill(cs)
 
-                        def timed(body, before=None):
-                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                            if before:
-                                before()
-                            torch.cuda.synchronize()
-                            e0.record(st)
-                            for _ in range(a.launches):
-                                body()
-                            e1.record(st)
-                            torch.cuda.synchronize()
-                            return e0.elapsed_time(e1) * 1e3 / a.launches      # microseconds per launch
+                        def us(body, prepare=None):      # microseconds per launch
+                            return lambda: 1e3 * measure.window(torch, st, body, a.launches, prepare)
 
                         def sweep_reset():
                             sw.cursor.zero_(); sw.slot_seed.fill_(-1); ms.ep_flags.fill_(1)
 
-                        t = dict(seed=[], step=[], refill=[])
-                        for rep in range(a.reps + 1):             # rep 0 warms every launch up
-                            r = dict(seed=timed(seed), step=timed(step, lambda: ms.ep_flags.zero_()), refill=timed(refill, sweep_reset))
-                            if rep:
-                                for k, v in r.items():
-                                    t[k].append(v)
+                        t = measure.alternate(dict(seed=us(seed), step=us(step, lambda: ms.ep_flags.zero_()), refill=us(refill, sweep_reset)), a.reps)
                         started = int(sw.cursor[0].item())
                         torch.cuda.synchronize()
-                cell = dict(label=a.label, mode="on" if mode else "off", groups=G, K=K, instances=G * K, N=N, n_obst=no,
-                            us={k: float(np.median(v)) for k, v in t.items()}, spread={k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()},
+                med, spread = measure.summaries(t)
+                cell = dict(label=a.label, mode="on" if mode else "off", groups=G, K=K, instances=G * K, N=N, n_obst=no, us=med, spread=spread,
                             seeds_started_in_the_last_rep=started)
                 rows.append(cell)
                 print(json.dumps(cell), flush=True)
@@ -157,21 +141,17 @@ def main():
     ap.add_argument("--label", choices=["this", "parent"], default="this")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multistart_geometry_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "multistart_geometry_rates.json"))
     a = ap.parse_args()
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     parts = a.part or ["a", "b"]
-    res = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    res = measure.read_json(a.out)
     if "a" in parts:
         res.setdefault("launch_times", {})[a.label] = launch_times(a, torch, mpc_gpu)
     if "b" in parts:
         res["closed_loop"] = closed_loop(a, torch, mpc_gpu)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+    measure.write_json(a.out, res)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """What multi-start solves cost and what they buy (mpc_seed_guesses_dev, mpc_select_best_dev, mpc_gpu.MultiStartMpc; DESIGN.md sections 4k and 5h).
 
 (a) LAUNCH TIMES.  For G scenarios of K = 5 members (N = 20, 3 obstacles, random scenarios of tests/helpers.random_batch) the three launches of one group
-    solve, each timed over `--launches` back-to-back launches between two HIP events on the object's stream, `--reps` times after one warm-up rep:
+    solve, each timed by scripts/measure.py's protocol: `--launches` back-to-back launches between two HIP events on the object's stream, `--reps` times
+    after one warm-up rep:
       seed          mpc_seed_guesses_dev alone;
       seed + solve  the guess launch and the ordinary solve launch (closed_loop_step_dev with flags = 0) of the same G K instances -- every solve then
                     starts from the same iterates and does the same work; solve = (seed + solve) - seed is the yardstick, the parent commit's code;
@@ -20,12 +21,10 @@
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+import measure
 
 GROUPS = (1024, 13107)      # x K = 5: 5120 and 65535 instances
 N, NO, TF = 20, 3, 2.0
@@ -40,10 +39,8 @@ def launch_times(a, torch, mpc_gpu):
         x0[:, 3:] = 0.0
         with mpc_gpu.MultiStartMpc(N, NO, TF, scenarios=G) as ms:
             K, B = ms.K, ms.B
-            st = ms.stream
-            with torch.cuda.stream(st):
+            with measure.own_stream(torch, ms.stream) as st:
                 cs = st.cuda_stream
-                assert cs != 0
                 ms._load(x0, obst, goal)
                 x_rows, goal_rows = ms._x0[:, 0].contiguous(), ms._goal[:, 0].contiguous()
 
@@ -58,30 +55,17 @@ def launch_times(a, torch, mpc_gpu):
                                                         ms.X.data_ptr(), ms.U.data_ptr(), ms.winner.data_ptr(), ms.cost.data_ptr(), ms.u0.data_ptr(),
                                                         ms.cand_u0.data_ptr(), cs))
 
-                def timed(body):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(st)
-                    for _ in range(a.launches):
-                        body()
-                    e1.record(st)
-                    torch.cuda.synchronize()
-                    return e0.elapsed_time(e1) * 1e3 / a.launches      # microseconds per pass
+                def us(body, prepare=None):      # microseconds per pass
+                    return lambda: 1e3 * measure.window(torch, st, body, a.launches, prepare)
 
-                t = dict(seed=[], seed_solve=[], select=[])
-                for rep in range(a.reps + 1):      # rep 0 warms every launch up
-                    r = dict(seed=timed(seed), seed_solve=timed(lambda: (seed(), solve())))
-                    seed(); solve()                # the costs the selection reads: those of a solve from the guesses
-                    r["select"] = timed(select)
-                    if rep:
-                        for k, v in r.items():
-                            t[k].append(v)
+                seed_solve = lambda: (seed(), solve())
+                # in front of the selection's window one solve from the guesses: the costs it reads
+                t = measure.alternate(dict(seed=us(seed), seed_solve=us(seed_solve), select=us(select, seed_solve)), a.reps)
                 torch.cuda.synchronize()
                 kernel = ms.inner.kernel_name(B)
                 winners = ms.winner.cpu().numpy()
                 status = ms.cand_status.cpu().numpy()
-            med = {k: float(np.median(v)) for k, v in t.items()}
-            spread = {k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()}
+            med, spread = measure.summaries(t)
             solve_us = med["seed_solve"] - med["seed"]
             row_bytes = 8 * (5 * (N + 1) + 2 * N)
             moved = G * (K * row_bytes + K * 12 + 4 + 8 + 16 + 16)      # read 1 row + write K - 1 rows; cost + status; winner, best_cost, u0 row, best_u0
@@ -143,21 +127,17 @@ def main():
     ap.add_argument("--part", choices=["a", "b"], action="append")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multistart_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "multistart_rates.json"))
     a = ap.parse_args()
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     parts = a.part or ["a", "b"]
-    res = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    res = measure.read_json(a.out)
     if "a" in parts:
         res["launch_times"] = launch_times(a, torch, mpc_gpu)
     if "b" in parts:
         res["closed_loop"] = closed_loop(a, torch, mpc_gpu)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+    measure.write_json(a.out, res)
 
 
 if __name__ == "__main__":

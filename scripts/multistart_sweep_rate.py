@@ -12,20 +12,17 @@ spread (max - min over median) of `--reps` reps.  Handles are made in front of t
     (what all but a few control steps of a sweep launch), the refill that starts a seed in every group (the first call of a sweep), and the control step
     behind it (noise draw + member solve + group tail).
 (d) bench.py --gpus 1 --steps 20 --warmup 5 with the parent commit's library (`--parent-lib PATH`) and this one's, alternating, parent first
-    (scripts/rollout_merit_rate.py's bench_ab): the flagship path launches nothing of this change.
+    (scripts/measure.py's bench_ab): the flagship path launches nothing of this change.
 
     python scripts/multistart_sweep_rate.py [--part a] [--part c] [--part d --parent-lib PATH] [--out profiles/multistart_sweep_rates.json]
 (parts a and b are one run.)"""
 import argparse
 import json
 import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "scripts")]
+import measure
 
 SLOTS = (125, 250, 500)
 MARGINS = (0.0, 0.5)
@@ -42,14 +39,9 @@ def columns(r):
 
 
 def timed(reps, call):
-    """reps + 1 calls, the first a warm-up: (the last result, median wall seconds, spread)"""
-    walls = []
-    for rep in range(reps + 1):
-        t0 = time.perf_counter()
-        r = call()
-        if rep:
-            walls.append(time.perf_counter() - t0)
-    return r, float(np.median(walls)), float((max(walls) - min(walls)) / np.median(walls))
+    """reps + 1 calls, the first a warm-up: (the last result, median wall seconds, spread); the call ends in a synchronise of its own"""
+    runs = measure.alternate(dict(call=lambda: measure.wall(call)), reps)["call"]
+    return (runs[-1][1],) + measure.summary([seconds for seconds, _ in runs])
 
 
 def sweep_against_batch(a, torch, mpc_gpu):
@@ -90,19 +82,11 @@ def refill_share(a, torch, mpc_gpu):
     S, L = 250, a.launches
     with mpc_gpu.MultiStartMpc(w.N_SOLV, w.N_OBST, w.TF, scenarios=S) as ms:
         args = sweep_arguments(START, GOAL, "RANDOM", (0, S * (a.reps + 1)), S, offsets=ms.offsets_host, max_iter=MAX_ITER, solver=ms)
-        stream = ms.stream
-        with torch.cuda.stream(stream):
+        with measure.own_stream(torch, ms.stream) as stream:
             cs = stream.cuda_stream
 
-            def events(body, n):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record(stream)
-                for _ in range(n):
-                    body()
-                e1.record(stream)
-                torch.cuda.synchronize()
-                return e0.elapsed_time(e1) * 1e3 / n              # microseconds per call
+            def us(body, n, prepare=None):      # microseconds per call
+                return lambda: 1e3 * measure.window(torch, stream, body, n, prepare)
 
             def step():
                 ms.inner.noise_draw_dev(S, st.state, st.nbuf, ep_flags=ms.ep_flags, stream=cs)
@@ -110,17 +94,13 @@ def refill_share(a, torch, mpc_gpu):
 
             ms.restart()
             st = _sweep_state(torch, ms, args, "RANDOM")
-            t = dict(refill_starting_every_group=[], refill_nothing_finished=[], control_step=[])
-            for rep in range(a.reps + 1):      # rep 0 warms every launch up
-                ms.ep_flags.fill_(1)           # every group has ended: the next refill parks it and starts a seed in it
-                r = dict(refill_starting_every_group=events(lambda: st.refill(cs), 1), refill_nothing_finished=events(lambda: st.refill(cs), L),
-                         control_step=events(step, L))
-                if rep:
-                    for k, v in r.items():
-                        t[k].append(v)
+            refill = lambda: st.refill(cs)
+            # in front of the first window every group has ended: the refill parks it and starts a seed in it
+            t = measure.alternate(dict(refill_starting_every_group=us(refill, 1, lambda: ms.ep_flags.fill_(1)), refill_nothing_finished=us(refill, L),
+                                       control_step=us(step, L)), a.reps)
             assert int(st.cursor[0].item()) == S * (a.reps + 1) and not bool((ms.ep_flags & 1).any())      # every timed refill did what its name says
-    med = {k: float(np.median(v)) for k, v in t.items()}
-    return dict(group_slots=S, K=ms.K, reps=a.reps, calls_per_rep=L, us=med, spread={k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()},
+    med, spread = measure.summaries(t)
+    return dict(group_slots=S, K=ms.K, reps=a.reps, calls_per_rep=L, us=med, spread=spread,
                 share_of_a_control_step=med["refill_nothing_finished"] / (med["refill_nothing_finished"] + med["control_step"]),
                 share_when_every_group_starts=med["refill_starting_every_group"] / (med["refill_starting_every_group"] + med["control_step"]))
 
@@ -134,24 +114,19 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--bench-rounds", type=int, default=3)
     ap.add_argument("--this-first", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multistart_sweep_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "multistart_sweep_rates.json"))
     a = ap.parse_args()
     parts = a.part or (["a", "c"] + (["d"] if a.parent_lib else []))
-    res = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    res = measure.read_json(a.out)
     if set(parts) & {"a", "c"}:
-        import torch
+        torch = measure.require_gpu()
         import mpc_gpu
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU: this script measures on the device only")
         for part, name, fn in (("a", "sweep_against_batch", sweep_against_batch), ("c", "refill_share", refill_share)):
             if part in parts:
                 res[name] = fn(a, torch, mpc_gpu)
     if "d" in parts:
-        from rollout_merit_rate import bench_ab
-        res["bench"] = bench_ab(a)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+        res["bench"] = measure.bench_ab(a.parent_lib, a.bench_rounds, a.this_first)
+    measure.write_json(a.out, res)
 
 
 if __name__ == "__main__":

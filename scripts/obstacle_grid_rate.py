@@ -3,16 +3,17 @@
 at batch 1024 and 16384.  One fused control step (look-ahead, solve, plant, obstacle motion, shift) per launch on the reference's RANDOM draws,
 timed with HIP events around K launches after W warm-up launches; then the CPU oracle's rate on the same cells (rti_solve_batch, 16 threads,
 host only, after the GPU part).  Writes the JSON record to the path given by --out (default profiles/wide_obstacle_rates.json).
---only N NO B: one GPU cell, no oracle (for a profiler run)."""
+--only N NO B: one GPU cell, no oracle (for a profiler run).
+The protocol is this script's own -- W warm-up launches, a stream synchronise, ONE window, no reps -- so of scripts/measure.py it takes the path prelude and
+the JSON write only."""
 import argparse
 import json
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd")]
 import numpy as np
+
+import measure
 
 
 def gpu_rate(mpc_gpu, N, no, B, K, W):
@@ -66,7 +67,7 @@ def oracle_rate(orc, N, no, B):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wide_obstacle_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "wide_obstacle_rates.json"))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--oracle-instances", type=int, default=1024, help="instances per oracle measurement (its rate does not depend on the batch)")
@@ -92,8 +93,7 @@ def main():
         r = oracle_rate(orc, N, no, a.oracle_instances)
         rec["oracle"][f"N{N}_obst{no}"] = r
         print("oracle", N, no, r, flush=True)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    json.dump(rec, open(a.out, "w"), indent=1)
+    measure.write_json(a.out, rec)
 
 
 if __name__ == "__main__":

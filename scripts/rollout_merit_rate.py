@@ -17,13 +17,10 @@ rep, median and spread ((max - min) / median).
 import argparse
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+import measure
 
 GROUPS = (1024, 13107)      # x K = 5: 5120 and 65535 instances
 N, NO, TF = 20, 3, 2.0
@@ -37,10 +34,8 @@ def launch_times(a, torch, mpc_gpu):
         x0[:, 3:] = 0.0
         with mpc_gpu.MultiStartMpc(N, NO, TF, scenarios=G, select_by="rollout") as ms:
             K, B, m = ms.K, ms.B, ms.inner
-            st = ms.stream
-            with torch.cuda.stream(st):
+            with measure.own_stream(torch, ms.stream) as st:
                 cs = st.cuda_stream
-                assert cs != 0
                 ms._load(x0, obst, goal)
                 x_rows, goal_rows, obst_rows = ms._x0[:, 0].contiguous(), ms._goal[:, 0].contiguous(), ms._obst[:, 0].contiguous()
 
@@ -56,30 +51,18 @@ def launch_times(a, torch, mpc_gpu):
                 def merit():
                     m.rollout_merit_dev(B, x_rows, ms._P, goal_rows, ms.U, X=ms.X, merit=ms.cand_merit, defect=ms.cand_defect, margin=ms.cand_margin, members=K, stream=cs)
 
-                def timed(body):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(st)
-                    for _ in range(a.launches):
-                        body()
-                    e1.record(st)
-                    torch.cuda.synchronize()
-                    return e0.elapsed_time(e1) * 1e3 / a.launches      # microseconds per pass
+                def us(body, prepare=None):      # microseconds per pass
+                    return lambda: 1e3 * measure.window(torch, st, body, a.launches, prepare)
 
-                t = dict(seed=[], seed_solve=[], predict=[], merit=[], predict_merit=[])
-                for rep in range(a.reps + 1):      # rep 0 warms every launch up
-                    r = dict(seed=timed(seed), seed_solve=timed(lambda: (seed(), solve())))
-                    seed(); solve()                # the iterates the rollout reads: those of a solve from the guesses
-                    r.update(predict=timed(predict), merit=timed(merit), predict_merit=timed(lambda: (predict(), merit())))
-                    if rep:
-                        for k, v in r.items():
-                            t[k].append(v)
+                seed_solve = lambda: (seed(), solve())
+                # in front of the rollout's windows one solve from the guesses: the iterates they read
+                t = measure.alternate(dict(seed=us(seed), seed_solve=us(seed_solve), predict=us(predict, seed_solve), merit=us(merit),
+                                           predict_merit=us(lambda: (predict(), merit()))), a.reps)
                 torch.cuda.synchronize()
                 kernel = m.kernel_name(B)
                 merits, costs, status = ms.cand_merit.cpu().numpy(), ms.cand_cost.cpu().numpy(), ms.cand_status.cpu().numpy()
                 defect = ms.cand_defect.cpu().numpy()
-            med = {k: float(np.median(v)) for k, v in t.items()}
-            spread = {k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()}
+            med, spread = measure.summaries(t)
             solve_us = med["seed_solve"] - med["seed"]
             # what the merit launch must move: U and X read, P read once per group, x0 / goal; three doubles written per instance
             moved = B * 8 * (2 * N + 5 * (N + 1) + 3) + G * 8 * ((N + 1) * NO * 2 + 7)
@@ -143,32 +126,6 @@ def closed_loop(a, torch, mpc_gpu):
     return dict(runs=out)
 
 
-def bench_ab(a):
-    """bench.py with the parent's library and this one's, alternating; each run a process of its own under a time limit"""
-    if not a.parent_lib or not os.path.exists(a.parent_lib):
-        raise SystemExit("--part c needs --parent-lib PATH (a libmpcgpu.so built from the parent commit)")
-    runs = []
-    for rnd in range(a.bench_rounds):
-        pair = [("parent", os.path.abspath(a.parent_lib)), ("this", None)]
-        for side, lib in (pair[::-1] if a.this_first else pair):
-            env = dict(os.environ)
-            env.pop("MPC_GPU_LIB", None)
-            if lib:
-                env["MPC_GPU_LIB"] = lib
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], env=env, cwd=ROOT,
-                               capture_output=True, text=True, timeout=300)
-            if p.returncode != 0:      # nothing more is started behind a run that failed
-                raise SystemExit(f"bench.py ({side}, round {rnd}) ended with {p.returncode}:\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            line = json.loads(p.stdout.strip().splitlines()[-1])
-            runs.append(dict(side=side, round=rnd, value=line.get("value"), unit=line.get("unit"), ms_per_step=line.get("ms_per_step"),
-                             mean_ipm_iters=(line.get("config") or {}).get("mean_ipm_iters")))
-            print(json.dumps(runs[-1]), flush=True)
-    med = {s: float(np.median([r["value"] for r in runs if r["side"] == s])) for s in ("parent", "this")}
-    par = [r["value"] for r in runs if r["side"] == "parent"]
-    return dict(command="bench.py --gpus 1 --steps 20 --warmup 5", order="this, parent" if a.this_first else "parent, this", runs=runs, median=med, this_over_parent=med["this"] / med["parent"],
-                parent_spread=(max(par) - min(par)) / med["parent"])
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", choices=["a", "b", "c"], action="append")
@@ -177,24 +134,20 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--bench-rounds", type=int, default=3)
     ap.add_argument("--this-first", action="store_true", help="part c: this commit's library runs first in every round (recorded as bench_this_first)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rollout_merit_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "rollout_merit_rates.json"))
     a = ap.parse_args()
     parts = a.part or (["a", "b"] + (["c"] if a.parent_lib else []))
-    res = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    res = measure.read_json(a.out)
     if "a" in parts or "b" in parts:
-        import torch
+        torch = measure.require_gpu()
         import mpc_gpu
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU: this script measures on the device only")
         if "a" in parts:
             res["launch_times"] = launch_times(a, torch, mpc_gpu)
         if "b" in parts:
             res["closed_loop"] = closed_loop(a, torch, mpc_gpu)
     if "c" in parts:
-        res["bench_this_first" if a.this_first else "bench"] = bench_ab(a)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+        res["bench_this_first" if a.this_first else "bench"] = measure.bench_ab(a.parent_lib, a.bench_rounds, a.this_first)
+    measure.write_json(a.out, res)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,8 @@ Timing, per cell and K in (2, 3): the same seeded batch runs `--steps` control s
   "host_l4": the same K launches on the level-4 kernel (the handle's own bounds through mpc_set_instance_bounds_dev), the instantiation level 5 is built on.
 The three forms solve the same problems (same_final_state compares the plant states bit for bit).  Beside them "l4_single" and "l5_single" run ONE
 iteration per control step on the level-4 kernel and on the level-5 kernel (set_sqp(2, inf)): the cost of one iteration on either.  Each rep restarts
-from the same state; rep 0 warms every form up; the forms alternate rep by rep; timed with HIP events on the step's stream.
+from the same state; timed on the step's stream by scripts/measure.py's protocol (HIP event window, rep 0 a warm-up of every form, the forms alternating
+rep by rep).
 
 Rates: for K = 1, 2, 3 the episode harness over the RANDOM scenario (run_episodes, seeds 0 .. --episodes - 1, the reference's experiment: TF = 2,
 N = 20, 5 obstacles, QP_ITER = 100): reached and hit rates and the mean step count.
@@ -17,12 +18,10 @@ N = 20, 5 obstacles, QP_ITER = 100): reached and hit rates and the mean step cou
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+import measure
 
 CELLS = [("C2", 1024, 20, 3), ("N50x4096", 4096, 50, 10)]
 KS = (2, 3)
@@ -35,13 +34,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--episodes", type=int, default=2000)
     ap.add_argument("--no-rates", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sqp_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "sqp_rates.json"))
     a = ap.parse_args()
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
     from helpers import random_batch
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     L = mpc_gpu._lib
     dev = torch.device("cuda", 0)
     STEP = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES
@@ -51,10 +48,7 @@ def main():
             continue
         x0, goal, obst = random_batch(B, no, seed=2024 + B + N)
         x0[:, 3:] = 0.0
-        # a stream of its own: the legacy default stream's handle is 0, which the library reads as the handle's own stream
-        with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B) as s, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-            st = torch.cuda.current_stream()
-            assert st.cuda_stream != 0
+        with mpc_gpu.BatchedMpc(N, no, 0.1 * N, max_batch=B) as s, measure.own_stream(torch) as st:
             cs = st.cuda_stream
             tx0, to0, tg = (torch.tensor(v, device=dev) for v in (x0, obst, goal))
             tx, to = tx0.clone(), to0.clone()
@@ -68,32 +62,30 @@ def main():
                 forms[f"fused_K{K}"] = ((K, 0.0), None, 1)
                 forms[f"host_l0_K{K}"] = ((1, 0.0), None, K)
                 forms[f"host_l4_K{K}"] = ((1, 0.0), table, K)
-            names, times, last = {}, {f: [] for f in forms}, {}
-            for rep in range(a.reps + 1):            # rep 0: warm-up of every form
-                for form, (sqp, tab, launches) in forms.items():
-                    torch.cuda.synchronize()
+            names, last = {}, {}
+
+            def rep(form, sqp, tab, launches):      # milliseconds per control step
+                def prepare():
                     s.set_instance_bounds_dev(tab)
                     s.set_sqp(*sqp)
                     names[form] = s.kernel_name(B)
                     tx.copy_(tx0); to.copy_(to0)
                     s.reset_guess_dev(B, tx, X, U, stream=cs)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(st)
-                    for _ in range(a.steps):
-                        for _ in range(launches - 1):
-                            s.closed_loop_step_dev(B, tx, to, tg, X, U, u0, None, status, iters, flags=0, stream=cs)
-                        s.closed_loop_step_dev(B, tx, to, tg, X, U, u0, None, status, iters, flags=STEP, stream=cs)
-                    e1.record(st)
-                    torch.cuda.synchronize()
-                    last[form] = tx.clone()
-                    if rep:
-                        times[form].append(e0.elapsed_time(e1) / 1e3)
+
+                def step():
+                    for _ in range(launches - 1):
+                        s.closed_loop_step_dev(B, tx, to, tg, X, U, u0, None, status, iters, flags=0, stream=cs)
+                    s.closed_loop_step_dev(B, tx, to, tg, X, U, u0, None, status, iters, flags=STEP, stream=cs)
+                ms = measure.window(torch, st, step, a.steps, prepare)
+                last[form] = tx.clone()
+                return ms
+
+            times = measure.alternate({f: (lambda f=f, v=v: rep(f, *v)) for f, v in forms.items()}, a.reps)
             s.set_instance_bounds_dev(None); s.set_sqp()
             res = {}
             for form, (sqp, tab, launches) in forms.items():
-                ts = np.array(times[form])
-                res[form] = dict(kernel=names[form], launches_per_step=launches, ms_per_control_step=1e3 * float(np.median(ts)) / a.steps,
-                                 spread=float((ts.max() - ts.min()) / np.median(ts)))
+                ms, spread = measure.summary(times[form])
+                res[form] = dict(kernel=names[form], launches_per_step=launches, ms_per_control_step=ms, spread=spread)
             for K in KS:
                 f = res[f"fused_K{K}"]["ms_per_control_step"]
                 res[f"K{K}"] = dict(fused_over_host_l0=f / res[f"host_l0_K{K}"]["ms_per_control_step"], fused_over_host_l4=f / res[f"host_l4_K{K}"]["ms_per_control_step"],
@@ -110,16 +102,7 @@ def main():
             tb = mpc_gpu.run_episodes(x0, goal, "RANDOM", N=20, Tf=2.0, max_iter=400, first_seed=0, qp_iter_max=100, sqp=(K, 0.0))["table"]
             rates["per_K"][str(K)] = dict(reached=float(tb[:, 1].mean()), hit=float(tb[:, 0].mean()), out_of_bounds=float(tb[:, 5].mean()), mean_steps=float(tb[:, 4].mean()))
             print(json.dumps({f"rates_K{K}": rates["per_K"][str(K)]}), flush=True)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    old, old_rates = [], None
-    if os.path.exists(a.out):
-        prev = json.load(open(a.out))
-        old_rates = prev.get("rates")
-        if prev.get("reps") == a.reps and prev.get("steps_per_rep") == a.steps:
-            old = [c for c in prev.get("cells", []) if c["cell"] not in {r["cell"] for r in rows}]
-    order = [c[0] for c in CELLS]
-    with open(a.out, "w") as f:
-        json.dump(dict(reps=a.reps, steps_per_rep=a.steps, cells=sorted(old + rows, key=lambda c: order.index(c["cell"])), rates=rates or old_rates), f, indent=1)
+    measure.merge_cells(a.out, dict(reps=a.reps, steps_per_rep=a.steps), rows, [c[0] for c in CELLS], extra=dict(rates=rates))      # --no-rates keeps the file's
 
 
 if __name__ == "__main__":

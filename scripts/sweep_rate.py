@@ -5,12 +5,13 @@ Workload: the reference's experiment (RANDOM, N 20, 5 obstacles, Tf 2, QP_ITER 1
   "one_batch":  run_episodes on ONE batch of all seeds with its default compaction;
   "sweep":      run_seed_sweep through --slots slots;
   "sweep_wide": run_seed_sweep through 4 x --slots slots.
-Every form runs --reps times (default 3) behind one warm-up, the forms alternating rep by rep; wall time around calls that end in a device synchronise.
+Every form runs --reps times (default 3) behind one warm-up, the forms alternating rep by rep; wall time between device synchronises (scripts/measure.py's
+alternate and wall).
 Recorded per form: the times, their spread (max - min over median), episodes/s, fused steps launched.  Beside them the PREDICTED ratio of fused steps
 sweep / chunks -- refill_schedule over the lengths of the chunks' own tables against the sum of the chunks' longest episodes -- and whether the sweep's
 steps_run is what refill_schedule says (exactly, in one more run with poll_every = 1).
 
-Per-step overhead (HIP events on the step's stream, median of --launches single calls at --slots slots): mpc_episode_refill_dev with no slot finished,
+Per-step overhead (measure.per_call: HIP events on the step's stream, median of --launches single calls at --slots slots): mpc_episode_refill_dev with no slot finished,
 with one slot refilled and with every slot refilled, each with and without the noise draw; mpc_noise_draw_dev alone; the fused step.
 
     python scripts/sweep_rate.py [--seeds 16384] [--slots 1024] [--reps 3] [--launches 30] [--out profiles/sweep_rates.json]
@@ -37,12 +38,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dynamic-obstacle-avoidance-mpc_amd"), os.path.join(ROOT, "tests")]
+import measure
 
 
 def load_baseline(root):
@@ -59,12 +58,10 @@ def load_baseline(root):
 
 
 def ring_forms(a):
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
     import sweep_cases as sc
     import sweep_feature_cases as fc
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     L = mpc_gpu._lib
     E, scen = a.seeds, a.scenario
     prob = dict(sc.PROBLEM, max_iter=400)
@@ -80,21 +77,14 @@ def ring_forms(a):
         forms["ring"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, ring=S, ring_every=25, **prob)
         forms["features"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **some, **prob)
         forms["all"] = lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, ring=S, ring_every=25, status_log=True, **feat, **prob)
-        times, last = {f: [] for f in forms}, {}
-        for rep in range(a.reps + 1):               # rep 0: warm-up of every form
-            for f, fn in forms.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                last[f] = fn()
-                torch.cuda.synchronize()
-                if rep:
-                    times[f].append(time.perf_counter() - t0)
-                print(json.dumps(dict(slots=S, rep=rep, form=f, seconds=time.perf_counter() - t0, steps_run=last[f]["steps_run"])), flush=True)
-        res = {}
+        runs = measure.alternate({f: (lambda fn=fn: measure.wall(fn, torch)) for f, fn in forms.items()}, a.reps, on_run=lambda rep, f, v: print(json.dumps(
+            dict(slots=S, rep=rep, form=f, seconds=v[0], steps_run=v[1]["steps_run"])), flush=True))
+        res, last = {}, {f: r[-1][1] for f, r in runs.items()}
         for f in forms:
-            ts = np.array(times[f])
-            res[f] = dict(seconds=[float(t) for t in ts], median_s=float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
-                          episodes_per_s=float(E / np.median(ts)), fused_steps=int(last[f]["steps_run"]), ms_per_step=float(1e3 * np.median(ts) / last[f]["steps_run"]))
+            ts = [sec for sec, _ in runs[f]]
+            med, spread = measure.summary(ts)
+            res[f] = dict(seconds=ts, median_s=med, spread=spread, episodes_per_s=float(E / med), fused_steps=int(last[f]["steps_run"]),
+                          ms_per_step=float(1e3 * med / last[f]["steps_run"]))
         spread = max(r["spread"] for r in res.values())
         summary = dict(largest_spread=spread, ring_over_off=res["ring"]["median_s"] / res["off"]["median_s"],
                        ring_faster_than_off_beyond_spread=bool(res["ring"]["median_s"] < res["off"]["median_s"] * (1 - spread)),
@@ -111,8 +101,8 @@ def ring_forms(a):
     S = int(a.slot_counts.split(",")[0])
     dev = torch.device("cuda", 0)
     over = {}
-    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-        st = torch.cuda.current_stream(); cs = st.cuda_stream
+    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, measure.own_stream(torch) as st:
+        cs = st.cuda_stream
         plain = sc.Plain(torch, dev)
         arr = sc.SlotArrays(plain, m, S, E, L.lib().mpc_noise_state_words())
         words = L.lib().mpc_noise_state_words()
@@ -121,16 +111,7 @@ def ring_forms(a):
         step_flags = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES | L.STEP_METRICS | L.STEP_RESET_ON_FAIL | L.STEP_ALIAS_BUG
         fl = L.REFILL_ALIAS_BUG | L.REFILL_DRAW_NOISE
 
-        def timed(fn, before=None):
-            ms = []
-            for _ in range(a.launches):
-                if before:
-                    before()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st); fn(); e1.record(st)
-                st.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            return dict(median_us=1e3 * float(np.median(ms)), min_us=1e3 * float(np.min(ms)), max_us=1e3 * float(np.max(ms)))
+        timed = lambda fn, before=None: measure.per_call(torch, st, fn, a.launches, before)
 
         for _ in range(10):                     # a few control steps in: every slot runs
             arr.refill(m, scen, 0, 400, fl, cs); arr.step(m, step_flags, cs)
@@ -151,17 +132,13 @@ def ring_forms(a):
         m.episode_ring_dev(0)
     out["per_call"] = dict(slots=S, launches=a.launches, **over)
     print(json.dumps(dict(per_call=out["per_call"])), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.ring_out)), exist_ok=True)
-    with open(a.ring_out, "w") as f:
-        json.dump(out, f, indent=1)
+    measure.write_json(a.ring_out, out)
 
 
 def trace_forms(a):
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
     import sweep_cases as sc
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     L = mpc_gpu._lib
     E, S, scen = a.seeds, a.slots, a.scenario
     prob = dict(sc.PROBLEM, max_iter=400)
@@ -172,27 +149,22 @@ def trace_forms(a):
         forms["baseline"] = lambda: base.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **prob)
     for f in a.trace:
         forms[f] = {"off": lambda: run(), "all": lambda: run(trace=True), "all-nopred": lambda: run(trace=True, trace_pred=False)}[f]
-    times, last = {f: [] for f in forms}, {}
-    for rep in range(a.reps + 1):               # rep 0: warm-up of every form
-        for f, fn in forms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            r = fn()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            last[f] = dict(table=r["table"], steps_run=r["steps_run"], solves=r["solves"], traced=len(r.get("trace", ())),
-                           trace_rows=int(sum(t["u"].shape[0] for t in r["trace"].values())) if "trace" in r else 0)
-            del r                                # (a trace of every seed is gigabytes on the host: one at a time)
-            if rep:
-                times[f].append(dt)
-            print(json.dumps(dict(slots=S, rep=rep, form=f, seconds=dt, steps_run=last[f]["steps_run"])), flush=True)
+    last = {}
+
+    def timed_form(f, fn):      # seconds; of the result only what the record needs is kept (a trace of every seed is gigabytes on the host: one at a time)
+        dt, r = measure.wall(fn, torch)
+        last[f] = dict(table=r["table"], steps_run=r["steps_run"], solves=r["solves"], traced=len(r.get("trace", ())),
+                       trace_rows=int(sum(t["u"].shape[0] for t in r["trace"].values())) if "trace" in r else 0)
+        return dt
+
+    times = measure.alternate({f: (lambda f=f, fn=fn: timed_form(f, fn)) for f, fn in forms.items()}, a.reps, on_run=lambda rep, f, dt: print(json.dumps(
+        dict(slots=S, rep=rep, form=f, seconds=dt, steps_run=last[f]["steps_run"])), flush=True))
     res = {}
     for f in forms:
-        ts = np.array(times[f])
-        res[f] = dict(seconds=[float(t) for t in ts], median_s=float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
-                      solves=int(last[f]["solves"]), solves_per_s=float(last[f]["solves"] / np.median(ts)), episodes_per_s=float(E / np.median(ts)),
-                      fused_steps=int(last[f]["steps_run"]), ms_per_step=float(1e3 * np.median(ts) / last[f]["steps_run"]), traced_seeds=int(last[f]["traced"]),
-                      traced_steps=int(last[f]["trace_rows"]))
+        med, spread = measure.summary(times[f])
+        res[f] = dict(seconds=times[f], median_s=med, spread=spread, solves=int(last[f]["solves"]), solves_per_s=float(last[f]["solves"] / med),
+                      episodes_per_s=float(E / med), fused_steps=int(last[f]["steps_run"]), ms_per_step=float(1e3 * med / last[f]["steps_run"]),
+                      traced_seeds=int(last[f]["traced"]), traced_steps=int(last[f]["trace_rows"]))
     ref = "off" if "off" in res else next(iter(res))
     summary = dict(largest_spread=max(r["spread"] for r in res.values()))
     for f in res:
@@ -212,8 +184,8 @@ def trace_forms(a):
     # ---- the trace launches on their own: every slot a few steps into a traced episode
     dev = torch.device("cuda", 0)
     over = {}
-    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-        st = torch.cuda.current_stream(); cs = st.cuda_stream
+    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, measure.own_stream(torch) as st:
+        cs = st.cuda_stream
         plain = sc.Plain(torch, dev)
         arr = sc.SlotArrays(plain, m, S, E, L.lib().mpc_noise_state_words())
         N, no, T = m.N, m.n_obst, 400
@@ -224,16 +196,7 @@ def trace_forms(a):
         t = dict(seed_row=seed_row, slot_state=plain.i32(S, 2), len=plain.i32(S), x=plain.f64(S, T + 1, 5), obst=plain.f64(S, T + 1, no, 4), u=plain.f64(S, T, 2),
                  status=plain.i32(S, T), iters=plain.i32(S, T), pred=plain.f64(S, T, N + 1, 5))
 
-        def timed(fn, before=None):
-            ms = []
-            for _ in range(a.launches):
-                if before:
-                    before()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st); fn(); e1.record(st)
-                st.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            return dict(median_us=1e3 * float(np.median(ms)), min_us=1e3 * float(np.min(ms)), max_us=1e3 * float(np.max(ms)))
+        timed = lambda fn, before=None: measure.per_call(torch, st, fn, a.launches, before)
 
         def step():
             m.closed_loop_step_dev(S, arr.x0, arr.obst, arr.goal, arr.X, arr.U, u0, None, arr.status, arr.iters, arr.noise, flags=step_flags, min_margin=arr.margin,
@@ -254,35 +217,31 @@ def trace_forms(a):
         m.episode_trace_set_dev(0)
     out["per_call"] = dict(slots=S, launches=a.launches, **over)
     print(json.dumps(dict(per_call=out["per_call"])), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.trace_out)), exist_ok=True)
-    with open(a.trace_out, "w") as f:
-        json.dump(out, f, indent=1)
+    measure.write_json(a.trace_out, out)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trace", nargs="+", choices=["off", "all", "all-nopred"], default=None)
-    ap.add_argument("--trace-out", default=os.path.join(ROOT, "profiles", "sweep_trace_rates.json"))
+    ap.add_argument("--trace-out", default=os.path.join(measure.ROOT, "profiles", "sweep_trace_rates.json"))
     ap.add_argument("--ring-forms", action="store_true")
     ap.add_argument("--slot-counts", default="1024,4096")
     ap.add_argument("--baseline-root", default=None)
-    ap.add_argument("--ring-out", default=os.path.join(ROOT, "profiles", "sweep_ring_rates.json"))
+    ap.add_argument("--ring-out", default=os.path.join(measure.ROOT, "profiles", "sweep_ring_rates.json"))
     ap.add_argument("--seeds", type=int, default=16384)
     ap.add_argument("--slots", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--scenario", default="RANDOM")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_rates.json"))
+    ap.add_argument("--out", default=os.path.join(measure.ROOT, "profiles", "sweep_rates.json"))
     a = ap.parse_args()
     if a.ring_forms:
         return ring_forms(a)
     if a.trace:
         return trace_forms(a)
-    import torch
+    torch = measure.require_gpu()
     import mpc_gpu
     import sweep_cases as sc
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this script measures on the device only")
     L = mpc_gpu._lib
     E, S, scen = a.seeds, a.slots, a.scenario
     prob = dict(sc.PROBLEM, max_iter=400)
@@ -301,21 +260,13 @@ def main():
              "one_batch": lambda: mpc_gpu.run_episodes(x0(E), goal(E), scen, first_seed=0, **prob),
              "sweep": lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), S, **prob),
              "sweep_wide": lambda: mpc_gpu.run_seed_sweep(sc.START, sc.GOAL, scen, (0, E), 4 * S, **prob)}
-    times, last = {f: [] for f in forms}, {}
-    for rep in range(a.reps + 1):               # rep 0: warm-up of every form
-        for f, fn in forms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            last[f] = fn()
-            torch.cuda.synchronize()
-            if rep:
-                times[f].append(time.perf_counter() - t0)
-            print(json.dumps(dict(rep=rep, form=f, seconds=time.perf_counter() - t0, steps_run=last[f]["steps_run"])), flush=True)
-    res = {}
+    runs = measure.alternate({f: (lambda fn=fn: measure.wall(fn, torch)) for f, fn in forms.items()}, a.reps, on_run=lambda rep, f, v: print(json.dumps(
+        dict(rep=rep, form=f, seconds=v[0], steps_run=v[1]["steps_run"])), flush=True))
+    res, last = {}, {f: r[-1][1] for f, r in runs.items()}
     for f in forms:
-        ts = np.array(times[f])
-        res[f] = dict(seconds=[float(t) for t in ts], median_s=float(np.median(ts)), spread=float((ts.max() - ts.min()) / np.median(ts)),
-                      episodes_per_s=float(E / np.median(ts)), fused_steps=int(last[f]["steps_run"]),
+        ts = [sec for sec, _ in runs[f]]
+        med, spread = measure.summary(ts)
+        res[f] = dict(seconds=ts, median_s=med, spread=spread, episodes_per_s=float(E / med), fused_steps=int(last[f]["steps_run"]),
                       reached=float(last[f]["table"][:, 1].mean()), mean_steps=float(last[f]["table"][:, 4].mean()))
     base = last["chunks"]["table"]
     lengths = (base[:, 4] + base[:, 1]).astype(int)
@@ -342,22 +293,13 @@ def main():
     # ---- the per-step overhead: single launches between HIP events
     dev = torch.device("cuda", 0)
     over = {}
-    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, torch.cuda.stream(torch.cuda.Stream(device=dev)):
-        st = torch.cuda.current_stream(); cs = st.cuda_stream
+    with mpc_gpu.BatchedMpc(max_batch=S, **sc.PROBLEM) as m, measure.own_stream(torch) as st:
+        cs = st.cuda_stream
         arr = sc.SlotArrays(sc.Plain(torch, dev), m, S, E, L.lib().mpc_noise_state_words())
         step_flags = L.STEP_SHIFT | L.STEP_PLANT | L.STEP_OBSTACLES | L.STEP_METRICS | L.STEP_RESET_ON_FAIL | L.STEP_ALIAS_BUG
         base_fl = L.REFILL_ALIAS_BUG
 
-        def timed(fn, before=None):
-            ms = []
-            for _ in range(a.launches):
-                if before:
-                    before()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st); fn(); e1.record(st)
-                st.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            return dict(median_us=1e3 * float(np.median(ms)), min_us=1e3 * float(np.min(ms)), max_us=1e3 * float(np.max(ms)))
+        timed = lambda fn, before=None: measure.per_call(torch, st, fn, a.launches, before)
 
         def fresh():
             arr.flags.fill_(1); arr.slot_seed.fill_(-1); arr.cursor.zero_()
@@ -375,10 +317,8 @@ def main():
         over["fused_step"] = timed(lambda: arr.step(m, step_flags, cs))
         over["fused_step_kernel"] = m.kernel_name(S)
     print(json.dumps(dict(per_step_overhead=over)), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(dict(workload=dict(scenario=scen, seeds=E, slots=S, reps=a.reps, **prob), forms=res, prediction=pred, summary=summary,
-                       per_step_overhead=dict(slots=S, launches=a.launches, **over)), f, indent=1)
+    measure.write_json(a.out, dict(workload=dict(scenario=scen, seeds=E, slots=S, reps=a.reps, **prob), forms=res, prediction=pred, summary=summary,
+                                   per_step_overhead=dict(slots=S, launches=a.launches, **over)))
 
 
 if __name__ == "__main__":
