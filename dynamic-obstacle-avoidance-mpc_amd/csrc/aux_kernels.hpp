@@ -1293,6 +1293,69 @@ __global__ __launch_bounds__(kTraceThreads) void episode_trace_kernel(int slots,
     if (lane == 0) t.slot_state[2 * s + 1] = now;
 }
 
+// GROUP RECORD (mpc_group_record_set_dev, mpc_group_record_dev): the closed-loop record of the multi-start GROUPS that ask for it -- what the episode trace keeps
+// per seed, and the K candidates the group chose among at every step.  A recorded group g owns row r = group_row[g] of every array below (the host hands out
+// distinct rows).  Two launches per control step, because group_step_kernel selects the winner and overwrites the evidence in one launch (member 0 <- the shifted
+// winner, members 1 .. K - 1 reseeded, x and obst moved in place):
+//   SOLVED, behind the member solve (and the rollout merit) and in front of the group tail: a running group at episode step t = ep_steps[g] -- the states the
+//     solve started from are row t, the candidates' keys, status words, iterations, u0 and (with cand_X) solved iterates are row t of the candidate arrays;
+//   STEPPED, behind the group tail: with now = ep_steps + (ep_flags & 1), a group with now > len[r] solved at step t = len[r] -- winner, best key and the
+//     applied input are row t, the states it was left in are row `now`, and lane 0 writes len[r] = now last.
+// One wavefront per group, four groups per workgroup (group_step_kernel's launch shape).  Every lane loads the group's words first (the same addresses in all 64
+// lanes: wavefront-uniform); a group that is idle, unrecorded or past its rows leaves there.  The lanes then stride over the doubles of a row, 8 bytes per lane
+// and round: the K (N + 1) 5 doubles of a group's member iterates are contiguous in X, and so is their row in cand_X, so both sides are coalesced (rows are
+// not 16-byte aligned in general -- K (N + 1) 5 may be odd -- so no wider access is used).  The rules of the refill and the trace hold: no atomics, no LDS, no
+// waiting, loops bounded by ceil(K (N + 1) 5 / 64); every word written belongs to the group's own row; no thread reads a word that another wavefront of the
+// same launch writes (len[r] is read and written by the group's own wavefront only); every input is read-only here.
+struct GroupRecordArrays {
+    const int32_t *group_row; int32_t *len;
+    double *x, *obst, *u; int32_t *winner; double *best_key, *cand_key; int32_t *cand_status, *cand_iters; double *cand_u0, *cand_X;
+    int rows, max_steps;
+};
+constexpr int kGroupRecordSolved = 0, kGroupRecordStepped = 1;
+
+__global__ __launch_bounds__(kGroupThreads) void group_record_kernel(int groups, int K, int phase, int n_obst, int N, GroupRecordArrays t,
+                                                                     const double *__restrict__ x, const double *__restrict__ obst, const double *__restrict__ X,
+                                                                     const double *__restrict__ key, const int32_t *__restrict__ status,
+                                                                     const int32_t *__restrict__ iters, const double *__restrict__ u0,
+                                                                     const int32_t *__restrict__ winner, const double *__restrict__ best_key,
+                                                                     const double *__restrict__ best_u0, const int32_t *__restrict__ ep_flags,
+                                                                     const int32_t *__restrict__ ep_steps)
+{
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kGroupWaves + (threadIdx.x >> 6);
+    if (g >= groups) return;
+    const int r = t.group_row[g];
+    if (r < 0 || r >= t.rows) return;                           // not recorded
+    const int fl = ep_flags[g], steps = ep_steps[g];
+    const int T = t.max_steps, ow = 4 * n_obst;
+    const size_t T1 = (size_t)T + 1;                            // state rows of a group
+    const size_t base = (size_t)g * K;
+    if (phase == kGroupRecordSolved) {
+        if ((fl & 1) || steps < 0 || steps >= T) return;        // idle: not solved; or no row left
+        const size_t at = (size_t)r * T + steps;                // (0 <= steps < T: every index below is inside the group's row)
+        trace_copy_row(t.x + ((size_t)r * T1 + steps) * 5, x + (size_t)g * 5, 5, lane);
+        trace_copy_row(t.obst + ((size_t)r * T1 + steps) * ow, obst + (size_t)g * ow, ow, lane);
+        trace_copy_row(t.cand_key + at * K, key + base, K, lane);
+        trace_copy_row(t.cand_u0 + at * K * 2, u0 + base * 2, 2 * K, lane);
+        if (lane < K) { t.cand_status[at * K + lane] = status[base + lane]; t.cand_iters[at * K + lane] = iters[base + lane]; }
+        if (t.cand_X) trace_copy_row(t.cand_X + at * K * (N + 1) * 5, X + base * (N + 1) * 5, K * (N + 1) * 5, lane);
+        return;
+    }
+    const int now = steps + (fl & 1), seen = t.len[r];
+    if (seen < 0 || now <= seen || now > T) return;             // idle on entry to the step, or no row left
+    const size_t at = (size_t)r * T + seen;                     // (0 <= seen < now <= T)
+    const int w = winner[g];
+    const double bk = best_key[g];
+    trace_copy_row(t.x + ((size_t)r * T1 + now) * 5, x + (size_t)g * 5, 5, lane);
+    trace_copy_row(t.obst + ((size_t)r * T1 + now) * ow, obst + (size_t)g * ow, ow, lane);
+    trace_copy_row(t.u + at * 2, best_u0 + (size_t)g * 2, 2, lane);
+    if (lane == 0) {
+        t.winner[at] = w; t.best_key[at] = bk;
+        t.len[r] = now;
+    }
+}
+
 // Plant integrator, robot_ocp_problem.py:207-212.
 __global__ void plant_step_kernel(int batch, double dt, const double *__restrict__ x, const double *__restrict__ u, double *__restrict__ xn)
 {

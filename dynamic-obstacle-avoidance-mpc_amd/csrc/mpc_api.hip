@@ -123,6 +123,8 @@ struct mpc_handle {
     int ring_scenario, ring_seed_count; unsigned ring_seed_first; double ring_box[6];
     int trace_rows, trace_max_steps;  // per-seed trajectories of a sweep (mpc_episode_trace_set_dev): rows, 0 = none attached; the caller's device arrays, used in place
     mpc_episode_trace trace;
+    int grec_rows, grec_max_steps, grec_K;      // per-group record of multi-start episodes (mpc_group_record_set_dev): rows, 0 = none attached; the caller's device arrays
+    mpc_group_record grec;
     int gg_mode;                      // guess family from geometry (mpc_set_guess_geometry): 0 off, 1 the amplitudes of seeded members from the obstacles in the way
     double gg_clearance, gg_a_max, gg_lead;
 };
@@ -1275,6 +1277,7 @@ int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigne
     if (h->rt_on) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: per-seed tables and the status log (mpc_set_refill_tables_dev) are not offered for groups");
     if (h->ring_cap) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: the ring of seeded episodes (mpc_episode_ring_dev) is not offered for groups");
     if (h->trace_rows) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: per-seed trajectories (mpc_episode_trace_set_dev) are not offered for groups");
+    if (h->grec_rows) return fail(MPC_ERR_ARG, "mpc_group_refill_dev: the per-group record (mpc_group_record_set_dev) is keyed by group, a sweep moves seeds between groups: not offered for groups that are refilled");
     HIPCHK(hipSetDevice(h->device));
     int rc = own(h, &h->d_refill_assign, (size_t)h->max_batch); if (rc) return rc;
     hipStream_t s = pick(h, stream);
@@ -1386,6 +1389,52 @@ int mpc_episode_trace_dev(mpc_handle *h, int slots, int phase, const int32_t *d_
     constexpr int per = mpc::kTraceThreads / 64;
     hipLaunchKernelGGL(mpc::episode_trace_kernel, dim3((slots + per - 1) / per), dim3(mpc::kTraceThreads), 0, pick(h, stream), slots, phase, h->cfg.n_obst, h->cfg.N,
                        a, d_slot_seed, d_x0, d_obst, d_X, d_u0, d_status, d_iters, d_ep_flags, d_ep_steps);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+/* ------------------------------------------------- multi-start episodes: the per-group record -------------------------------------------------- */
+
+int mpc_group_record_set_dev(mpc_handle *h, int rows, int max_steps, int K, const mpc_group_record *r)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!r || rows == 0) { h->grec_rows = 0; h->grec_max_steps = 0; h->grec_K = 0; memset(&h->grec, 0, sizeof(h->grec)); return MPC_OK; }
+    if (rows < 0) return fail(MPC_ERR_ARG, "mpc_group_record_set_dev: rows must be >= 0 (0 detaches the record)");
+    if (max_steps < 1) return fail(MPC_ERR_ARG, "mpc_group_record_set_dev: max_steps must be >= 1");
+    if (K < 1 || K > 64) return fail(MPC_ERR_ARG, "mpc_group_record_set_dev: K must be in [1, 64] (one member per lane of the group's wavefront)");
+    const struct { const char *name; const void *p; } need[11] = {{"group_row", r->group_row}, {"len", r->len}, {"x", r->x}, {"obst", r->obst}, {"u", r->u},
+                                                                  {"winner", r->winner}, {"best_key", r->best_key}, {"cand_key", r->cand_key},
+                                                                  {"cand_status", r->cand_status}, {"cand_iters", r->cand_iters}, {"cand_u0", r->cand_u0}};
+    for (const auto &f : need)
+        if (!f.p) return fail(MPC_ERR_ARG, "mpc_group_record_set_dev: %s is null (cand_X alone may be)", f.name);
+    h->grec = *r; h->grec_rows = rows; h->grec_max_steps = max_steps; h->grec_K = K;
+    return MPC_OK;
+}
+
+int mpc_group_record_dev(mpc_handle *h, int groups, int K, int phase, const double *d_x, const double *d_obst, const double *d_X, const double *d_key,
+                         const int32_t *d_status, const int32_t *d_iters, const double *d_u0, const mpc_group_step_out *out, void *stream)
+{
+    if (!h) return fail(MPC_ERR_ARG, "null handle");
+    if (!h->grec_rows) return fail(MPC_ERR_ARG, "mpc_group_record_dev: no record attached (mpc_group_record_set_dev)");
+    if (K < 1 || K > 64) return fail(MPC_ERR_ARG, "mpc_group_record_dev: K must be in [1, 64]");
+    if (K != h->grec_K) return fail(MPC_ERR_ARG, "mpc_group_record_dev: K differs from the K the record was attached for (mpc_group_record_set_dev)");
+    if (groups < 1 || (long long)groups * K > h->max_batch) return fail(MPC_ERR_ARG, "mpc_group_record_dev: groups < 1 or groups * K > max_batch");
+    if (phase != MPC_GROUP_RECORD_SOLVED && phase != MPC_GROUP_RECORD_STEPPED)
+        return fail(MPC_ERR_ARG, "mpc_group_record_dev: phase must be MPC_GROUP_RECORD_SOLVED (0) or MPC_GROUP_RECORD_STEPPED (1)");
+    const struct { const char *name; const void *p; } need[8] = {{"d_x", d_x}, {"d_obst", d_obst}, {"d_X", d_X}, {"d_key", d_key}, {"d_status", d_status},
+                                                                 {"d_iters", d_iters}, {"d_u0", d_u0}, {"out", out}};
+    for (const auto &f : need)
+        if (!f.p) return fail(MPC_ERR_ARG, "mpc_group_record_dev: %s is null", f.name);
+    if (!out->winner || !out->ep_flags || !out->ep_steps) return fail(MPC_ERR_ARG, "mpc_group_record_dev: out->winner, out->ep_flags or out->ep_steps is null");
+    if (phase == MPC_GROUP_RECORD_STEPPED && (!out->best_key || !out->best_u0))
+        return fail(MPC_ERR_ARG, "mpc_group_record_dev: MPC_GROUP_RECORD_STEPPED without out->best_key or out->best_u0 (hand the group step both)");
+    HIPCHK(hipSetDevice(h->device));
+    const mpc_group_record &r = h->grec;
+    mpc::GroupRecordArrays a{r.group_row, r.len, r.x, r.obst, r.u, r.winner, r.best_key, r.cand_key, r.cand_status, r.cand_iters, r.cand_u0, r.cand_X,
+                             h->grec_rows, h->grec_max_steps};
+    hipLaunchKernelGGL(mpc::group_record_kernel, dim3((groups + mpc::kGroupWaves - 1) / mpc::kGroupWaves), dim3(mpc::kGroupThreads), 0, pick(h, stream), groups, K, phase,
+                       h->cfg.n_obst, h->cfg.N, a, d_x, d_obst, d_X, d_key, d_status, d_iters, d_u0, (const int32_t *)out->winner, (const double *)out->best_key,
+                       (const double *)out->best_u0, (const int32_t *)out->ep_flags, (const int32_t *)out->ep_steps);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }

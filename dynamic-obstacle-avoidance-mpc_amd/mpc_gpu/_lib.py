@@ -24,6 +24,7 @@ REFILL_ALIAS_BUG, REFILL_INTERP_GUESS, REFILL_DRAW_NOISE = 1, 2, 4      # MPC_RE
 TRACE_START, TRACE_STEP = 0, 1      # MPC_TRACE_* (mpc_episode_trace_dev)
 SELECT_BROADCAST = 1                # MPC_SELECT_BROADCAST (mpc_select_best_dev)
 GROUP_MARGIN_ALL = 1                # MPC_GROUP_MARGIN_ALL (mpc_group_step_dev)
+GROUP_RECORD_SOLVED, GROUP_RECORD_STEPPED = 0, 1      # MPC_GROUP_RECORD_* (mpc_group_record_dev)
 COMM_ID_BYTES = 128      # MPC_COMM_ID_BYTES (RCCL unique id)
 MAX_SQP_ITER = 100       # MPC_MAX_SQP_ITER
 ABI_VERSION = 7          # MPC_ABI_VERSION of include/mpc_gpu.h this mirror (MpcConfig, SYMBOLS) was written against
@@ -75,6 +76,11 @@ class GroupRefillArrays(C.Structure):
     member and per seed."""
     _fields_ = [(n, _vp) for n in ("x", "obst", "goal", "X", "U", "min_margin", "ep_flags", "ep_steps", "lost", "switched", "state", "slot_seed", "cursor",
                                    "res_f", "res_i", "member_x", "member_obst", "member_goal", "member_flags")]
+
+
+class GroupRecord(C.Structure):
+    """Mirror of `struct mpc_group_record` (include/mpc_gpu.h): device pointers only -- the row map and the per-group rows of a multi-start episode record."""
+    _fields_ = [(n, _vp) for n in ("group_row", "len", "x", "obst", "u", "winner", "best_key", "cand_key", "cand_status", "cand_iters", "cand_u0", "cand_X")]
 
 
 _cfgp = C.POINTER(MpcConfig)
@@ -147,6 +153,8 @@ SYMBOLS = {
     "mpc_episode_refill_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 15),
     "mpc_group_refill_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp,
                                        C.POINTER(GroupRefillArrays), _vp]),
+    "mpc_group_record_set_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(GroupRecord)]),
+    "mpc_group_record_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int] + [_vp] * 7 + [C.POINTER(GroupStepOut), _vp]),
     "mpc_set_refill_tables_dev": (C.c_int, [_vp, C.POINTER(RefillTables)]),
     "mpc_episode_status_log_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mpc_episode_ring_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),

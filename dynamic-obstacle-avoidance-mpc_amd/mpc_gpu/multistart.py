@@ -18,7 +18,9 @@ runs the member solve and then ONE launch, mpc_group_step_dev (select, plant, ob
 DESIGN.md section 4m), and run_multistart_episodes drives it to the reference's result table.  run_multistart_sweep streams more seeds than there are
 groups through the groups: a finished group starts the next seed on the device (mpc_group_refill_dev).  Neither driver has a loop of
 its own: they hand their launches to episodes._episode_loop and episodes._sweep_loop, the two loops run_episodes and run_seed_sweep run on, and the sweep's
-rows come back through episodes._sweep_table.  PipelinedMpc does not know about groups.
+rows come back through episodes._sweep_table.  PipelinedMpc does not know about groups.  run_multistart_episodes(record=...) returns the
+closed-loop record of the groups that ask for it -- trajectory, applied inputs and, per step, the K candidates with the winner -- written on the device around
+the group tail (mpc_group_record_dev); multistart_record hands one group to episodes.visualisation_inputs.
 
 guess_geometry (off by default) replaces the fixed lateral offsets of members 1 .. K - 1 by amplitudes computed on the device from the obstacles that are in the
 way -- the pass-left / pass-right candidates of the nearest blocking obstacles (mpc_set_guess_geometry); `offsets` is then the base family a
@@ -143,6 +145,7 @@ class MultiStartMpc:
             self.cand_merit, self.cand_defect, self.cand_margin = f64(B), f64(B), f64(B)
         self.solved_X = self.solved_U = None
         self._warm = self._fused_warm = False
+        self._recording = False                    # a per-group record is attached (group_record_set_dev): step_fused launches its two phases
         self.member_offsets = None                 # guess_geometry: the (G, K) amplitudes the last stand-alone seed launch wrote
         if self.guess_geometry is not None:
             q = self.guess_geometry
@@ -356,13 +359,33 @@ class MultiStartMpc:
             m.closed_loop_step_dev(B, self._x0, self._obst, self._goal, self.X, self.U, self.cand_u0, self.cand_cost, self.cand_status, self.cand_iters,
                                    flags=_lib.STEP_METRICS, min_margin=self._scratch_margin, ep_flags=self.member_flags, ep_steps=self._scratch_steps, stream=s)
             by = self._select_key(x, obst, goal, s)
+            rec = (G, K, x, obst, self.X, by, self.cand_status, self.cand_iters, self.cand_u0, self._out) if self._recording else None
+            if rec is not None:          # what the group chooses among: the tail below overwrites it
+                m.group_record_dev(rec[0], rec[1], _lib.GROUP_RECORD_SOLVED, *rec[2:], stream=s)
             _lib.check(_lib.lib().mpc_group_step_dev(m._h, G, K, by.data_ptr(), self.cand_status.data_ptr(), self.cand_u0.data_ptr(), self.margin,
                                                      _lib.GROUP_MARGIN_ALL if margin_all else 0, x.data_ptr(), obst.data_ptr(), goal.data_ptr(),
                                                      self.offsets.data_ptr(), None if noise is None else noise.data_ptr(), randomness, vmax,
                                                      self.X.data_ptr(), self.U.data_ptr(), self._out, s))
+            if rec is not None:          # what it chose, and the states that left it in
+                m.group_record_dev(rec[0], rec[1], _lib.GROUP_RECORD_STEPPED, *rec[2:], stream=s)
         outer.wait_stream(self.stream)
         return dict(self._result(), min_margin=self.min_margin, ep_flags=self.ep_flags, ep_steps=self.ep_steps, lost_steps=self.lost_steps,
                     switched_steps=self.switched_steps)
+
+    def group_record_set_dev(self, rows=0, max_steps=0, **arrays):
+        """attach a per-group record to the fused control step (BatchedMpc.group_record_set_dev with this object's K; the arrays by their names in
+        BatchedMpc.GROUP_RECORD_FIELDS, device tensors used in place): while one is attached, step_fused launches mpc_group_record_dev twice per control step --
+        SOLVED between the member solve (and the rollout merit) and the group tail, STEPPED behind the tail -- and with none attached exactly what it launches
+        without this feature.  rows 0 (the default) detaches: group_record_off().  The non-fused step() records nothing."""
+        if int(rows) == 0:
+            return self.group_record_off()
+        self.inner.group_record_set_dev(rows, max_steps, self.K, **arrays)
+        self._recording = True
+
+    def group_record_off(self):
+        """detach the per-group record (the handle keeps no pointer into its arrays)"""
+        self._recording = False
+        self.inner.group_record_set_dev(0)
 
     def iterates(self):
         """the iterates of all members as they stand, (G, K, N + 1, 5) and (G, K, N, 2) device views"""
@@ -443,9 +466,118 @@ def episode_arguments(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=
                 noise=noise, first_seed=int(first_seed), guess_geometry=geometry)
 
 
+def group_record_bytes(rows, max_iter, N, n_obst, K, plans=True):
+    """device bytes of a per-group record (mpc_group_record): per recorded group x (max_iter + 1, 5), obst (max_iter + 1, n_obst, 4), u (max_iter, 2), best_key
+    (max_iter,), cand_key (max_iter, K), cand_u0 (max_iter, K, 2) and, with plans, cand_X (max_iter, K, N + 1, 5) in float64; winner (max_iter,), cand_status and
+    cand_iters (max_iter, K) and one len word in int32"""
+    rows, T, N, n_obst, K = int(rows), int(max_iter), int(N), int(n_obst), int(K)
+    per_row = 8 * ((T + 1) * 5 + (T + 1) * n_obst * 4 + T * 2 + T + T * K + T * K * 2 + (T * K * (N + 1) * 5 if plans else 0)) + 4 * (T + 2 * T * K + 1)
+    return rows * per_row
+
+
+def _group_record(G, max_iter, N, n_obst, K, record=None, record_plans=True, record_max_bytes=2 ** 31):
+    """run_multistart_episodes' record arguments, checked on the host before anything touches a device, by the rules of episodes._sweep_trace.  Returns None
+    (no record) or dict(groups: the recorded group indices (rows,) in the order given, group_row: int32 (G,) = the row of each group or -1, plans, bytes)."""
+    if record is None or record is False:
+        return None
+    if not isinstance(record_plans, (bool, np.bool_)):
+        raise ValueError("record_plans must be True or False")
+    if isinstance(record_max_bytes, (bool, np.bool_)) or not isinstance(record_max_bytes, (int, np.integer)) or record_max_bytes < 0:
+        raise ValueError("record_max_bytes must be a whole number of bytes >= 0")
+    what = f"record must be None, True or a sequence of group indices in 0 .. {G - 1}"
+    if record is True:
+        groups = np.arange(G, dtype=np.int64)
+    else:
+        if isinstance(record, (str, bytes, dict, set, frozenset)) or not hasattr(record, "__len__"):
+            raise ValueError(what)
+        try:
+            a = np.asarray(record)
+        except Exception:
+            raise ValueError(what) from None
+        if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+            raise ValueError(f"record must be a non-empty 1-d sequence of whole group indices (0 .. {G - 1}), got {a.dtype} {a.shape}")
+        if (a < 0).any() or (a >= G).any():
+            raise ValueError(f"record holds a group index outside 0 .. {G - 1}: {a[(a < 0) | (a >= G)][0]}")
+        groups = a.astype(np.int64)
+        if np.unique(groups).size != groups.size:
+            raise ValueError("record names a group index twice (every recorded group owns one row)")
+    need = group_record_bytes(groups.size, max_iter, N, n_obst, K, plans=bool(record_plans))
+    if need > record_max_bytes:
+        raise ValueError(f"record: the arrays of {groups.size} groups x {int(max_iter)} control steps x {int(K)} members take {need} bytes, more than "
+                         f"record_max_bytes = {int(record_max_bytes)}: record fewer groups"
+                         + (" or pass record_plans=False (the candidates' plans are most of it)" if record_plans else ""))
+    group_row = np.full(G, -1, dtype=np.int32)
+    group_row[groups] = np.arange(groups.size, dtype=np.int32)
+    return dict(groups=groups, group_row=group_row, plans=bool(record_plans), bytes=need)
+
+
+def _group_lease(solver, make):
+    """episodes._HandleLease for a MultiStartMpc: the setters it undoes, and the per-group record's (group_record_set_dev(0) detaches)"""
+    from .episodes import _HandleLease
+
+    class _GroupLease(_HandleLease):
+        OFF = dict(_HandleLease.OFF, group_record_set_dev=(0,))
+    return _GroupLease(solver, make)
+
+
+def _attach_group_record(lease, torch, rc, max_iter):
+    """the per-group rows (mpc_group_record) on the lease's MultiStartMpc: row r belongs to group rc["groups"][r].  Returns the arrays by their names in
+    group_record_set_dev"""
+    ms = lease.m
+    R, N, no, K, T = rc["groups"].size, ms.N, ms.n_obst, ms.K, int(max_iter)
+    f64 = dict(dtype=torch.float64, device=ms.dev); i32 = dict(dtype=torch.int32, device=ms.dev)
+    arr = dict(group_row=torch.from_numpy(rc["group_row"]).to(ms.dev), len=torch.zeros(R, **i32), x=torch.zeros(R, T + 1, 5, **f64),
+               obst=torch.zeros(R, T + 1, no, 4, **f64), u=torch.zeros(R, T, 2, **f64), winner=torch.zeros(R, T, **i32), best_key=torch.zeros(R, T, **f64),
+               cand_key=torch.zeros(R, T, K, **f64), cand_status=torch.zeros(R, T, K, **i32), cand_iters=torch.zeros(R, T, K, **i32),
+               cand_u0=torch.zeros(R, T, K, 2, **f64), cand_X=torch.zeros(R, T, K, N + 1, 5, **f64) if rc["plans"] else None)
+    lease.attach("group_record_set_dev", R, T, **arr)
+    return arr
+
+
+_RECORD_CUT = dict(simX=("x", 1), obst_traj=("obst", 1), u=("u", 0), winner=("winner", 0), key=("best_key", 0), cand_key=("cand_key", 0),
+                   cand_status=("cand_status", 0), cand_iters=("cand_iters", 0), cand_u0=("cand_u0", 0), cand_X=("cand_X", 0))      # name -> (array, rows beyond L)
+
+
+def _collect_group_record(arr, rc, table):
+    """the recorded rows on the host, once the stream has drained, cut to each group's length and held to the table's lengths"""
+    th = {n: t.cpu().numpy() for n, t in arr.items() if t is not None and n != "group_row"}
+    want = (table[rc["groups"], 4] + table[rc["groups"], 1]).astype(np.int64)
+    if not np.array_equal(th["len"], want):
+        bad = np.nonzero(th["len"] != want)[0]
+        raise _lib.MpcError(f"record: group {int(rc['groups'][bad[0]])} recorded {int(th['len'][bad[0]])} control steps, its table row says {int(want[bad[0]])}")
+    return {g: {n: th[src][r, :int(th["len"][r]) + more].copy() for n, (src, more) in _RECORD_CUT.items() if src in th} for r, g in enumerate(rc["groups"].tolist())}
+
+
+def multistart_record(result, g, member=None):
+    """One recorded group of run_multistart_episodes(..., record=...) in run_episodes(record=True)'s layout, as a batch of one: dict(simX (L + 1, 1, 5),
+    obst_traj (L + 1, 1, n_obst, 4), pred (L, 1, N + 1, 5), table (1, 6), x_last (1, 5)), so that visualisation_inputs(multistart_record(result, g), 0) is
+    what the reference hands to its VisDynamicRobotEnv for that group.  pred[t] is the SOLVED plan of step t's winner -- of member 0 on a step without a
+    winner --, or with member=k always candidate k's (the pass-left or pass-right plan next to the one chosen), written in the SHIFTED layout
+    visualisation_inputs re-assembles (stage j at j - 1, stage N kept).  Needs record_plans=True."""
+    rec = result.get("record") if isinstance(result, dict) else None
+    if rec is None:
+        raise ValueError("the episodes were run without a record: pass record=True or the group indices to run_multistart_episodes")
+    if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, np.integer)) or int(g) not in rec:
+        raise ValueError(f"group {g!r} was not recorded (recorded: {sorted(rec)[:8]}{' ...' if len(rec) > 8 else ''})")
+    t = rec[int(g)]
+    if "cand_X" not in t:
+        raise ValueError("the record holds no plans (record_plans=False): a record for visualisation_inputs needs them")
+    L, K, N1 = t["cand_X"].shape[:3]
+    if member is None:
+        pick = np.where(t["winner"] >= 0, t["winner"], 0).astype(np.int64)
+    else:
+        if isinstance(member, (bool, np.bool_)) or not isinstance(member, (int, np.integer)) or not 0 <= int(member) < K:
+            raise ValueError(f"member must be None (the winner's plan) or a candidate in 0 .. {K - 1}, got {member!r}")
+        pick = np.full(L, int(member), dtype=np.int64)
+    solved = t["cand_X"][np.arange(L), pick]                                            # (L, N + 1, 5)
+    pred = solved[:, np.minimum(np.arange(N1) + 1, N1 - 1)]                             # stage j at j - 1, stage N kept
+    return dict(simX=t["simX"][:, None].copy(), obst_traj=t["obst_traj"][:, None].copy(), pred=pred[:, None].copy(),
+                table=np.array(result["table"][int(g)][None]), x_last=np.array(result["x_last"][int(g)][None]))
+
+
 def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_margin=0.0, select_by="cost", N=20, Tf=2.0, n_obst=5, max_iter=400, random_move=True,
                             first_seed=0, noise=None, sqp=None, r_safe=None, r_hit=None, active=None, margin_all=False, solver=None, device=0,
-                            guess_geometry=None, **cfg):
+                            guess_geometry=None, record=None, record_plans=True, record_max_bytes=2 ** 31, **cfg):
     """run_episodes for GROUPS: G closed-loop episodes of K = len(offsets) candidate iterates each, one MultiStartMpc.step_fused per control step (noise draw ->
     member solve -> [predict, rollout merit] -> group tail), episode bookkeeping per group on the device.  x0 (G, 5), goal (2,) or (G, 2), obst (G, n_obst, 4)
     -- or a scenario name ("RANDOM" | "CENTER" | "EDGE"): group s is then the reference's episode for np.random.seed(first_seed + s) (experiments.py:20-36), its
@@ -459,21 +591,32 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
     done flag goes to pinned host memory behind an event and is looked at once that event has passed -- no stall, at most ~25 steps on idle groups.
     solver: a caller's MultiStartMpc with the same groups, offsets, margin and select_by; it is restart()ed, and leaves with the features of this call switched
     OFF again whether the call returns or raises (_HandleLease).  The arguments that need no device are checked before a handle is touched (episode_arguments).
-    Not offered: PipelinedMpc, compaction, record / trace.  More seeds than groups, or groups that do not idle once their episode has
-    ended: run_multistart_sweep (the refill for groups).
+    record: None (off, the default), True (every group) or a sequence of group INDICES in 0 .. G-1 without duplicates: the closed-loop record of those groups,
+    written on the device (mpc_group_record_set_dev / mpc_group_record_dev: two small launches per control step, in front of and behind the group tail, which
+    selects the winner and overwrites the candidates in one launch).  `record` in the result is a dict keyed by group index; with L = the
+    group's control steps (= table[g, 4] + table[g, 1]) each value holds simX (L + 1, 5), obst_traj (L + 1, n_obst, 4), u (L, 2) = the input applied, winner (L,)
+    (-1: no member was eligible, u = 0), key (L,) = the winner's key, and per candidate cand_key (the reported cost, or the rollout merit), cand_status,
+    cand_iters (L, K), cand_u0 (L, K, 2) and, unless record_plans=False, cand_X (L, K, N + 1, 5): every member's SOLVED plan, stage j at row j.
+    multistart_record(result, g) puts one group into run_episodes(record=True)'s layout for visualisation_inputs.  The arrays take
+    group_record_bytes(rows, max_iter, N, n_obst, K, record_plans) device bytes (1.1 MB per group with plans and 0.13 MB without, at max_iter 400, N 20,
+    5 obstacles and K 3); above record_max_bytes the call is refused on the host.  table, x_last, lost_steps and switched_steps are those of the call without a
+    record, bit for bit.
+    Not offered: PipelinedMpc, compaction, a record of the non-fused step().  More seeds than groups, or groups that do not idle once their
+    episode has ended: run_multistart_sweep (the refill for groups; it takes no record: the record is keyed by group).
     Returns dict(table (G, 6) = [hit, reached, min_margin, dist_to_goal, iters, out_of_bounds] (episodes.result_table), x_last (G, 5), steps_run, solves = the
     member solves of running groups = K (sum of table[:, 4] + table[:, 1]), lost_steps (G,): control steps on which no member was eligible, switched_steps (G,):
-    control steps on which the winner was not member 0)."""
-    from .episodes import _HandleLease, _episode_loop, _noise_source, result_table
+    control steps on which the winner was not member 0), and with record: record)."""
+    from .episodes import _episode_loop, _noise_source, result_table
     from types import SimpleNamespace
     a = episode_arguments(x0, goal, obst, offsets, incumbent_margin, select_by, n_obst, max_iter, random_move, first_seed, noise, sqp, r_safe, r_hit, active, solver,
                           guess_geometry)
+    rc = _group_record(a["G"], a["max_iter"], solver.N if solver is not None else int(N), a["n_obst"], a["K"], record, record_plans, record_max_bytes)
     import torch
     G, K, no = a["G"], a["K"], a["n_obst"]
     dev = torch.device("cuda", device if solver is None else solver.dev.index)
     make = lambda: MultiStartMpc(N, no, Tf, scenarios=G, offsets=a["offsets"], incumbent_margin=a["margin"], device=device, select_by=a["select_by"],
                                  guess_geometry=a["guess_geometry"], **cfg)
-    with _HandleLease(solver, make) as lease:
+    with _group_lease(solver, make) as lease:
         ms = lease.m
         lease.stream = ms.stream
         if r_safe is not None or r_hit is not None:
@@ -493,6 +636,7 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
             else:
                 dobst = torch.from_numpy(a["obst"].copy()).to(dev)
             ms._group_arrays()
+            rarr = _attach_group_record(lease, torch, rc, a["max_iter"]) if rc is not None else None
             rows = SimpleNamespace(rows=G, obst=dobst, flags=ms.ep_flags, f64=f64, gen_state=None, nbuf=None)
             draw = _noise_source(torch, ms.inner, rows, a["noise"], a["scenario"], a["first_seed"], 0, s)
             def step(k):
@@ -503,7 +647,8 @@ def run_multistart_episodes(x0, goal, obst, offsets=DEFAULT_OFFSETS, incumbent_m
             xl = x.cpu().numpy()
             table = result_table(ms.ep_flags.cpu().numpy(), ms.min_margin.cpu().numpy(), xl, a["goal"], ms.ep_steps.cpu().numpy())
             lost, switched = ms.lost_steps.cpu().numpy().copy(), ms.switched_steps.cpu().numpy().copy()
-    return dict(table=table, x_last=xl, steps_run=k, solves=K * int(table[:, 4].sum() + table[:, 1].sum()), lost_steps=lost, switched_steps=switched)
+            rec = {} if rarr is None else dict(record=_collect_group_record(rarr, rc, table))
+    return dict(table=table, x_last=xl, steps_run=k, solves=K * int(table[:, 4].sum() + table[:, 1].sum()), lost_steps=lost, switched_steps=switched, **rec)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- seed sweeps of groups

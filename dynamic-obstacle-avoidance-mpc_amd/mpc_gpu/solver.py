@@ -442,6 +442,30 @@ class BatchedMpc:
         _lib.check(_lib.lib().mpc_episode_trace_dev(self._h, int(slots), int(phase), _ptr(slot_seed), _ptr(x0), _ptr(obst), _ptr(X), _ptr(u0), _ptr(status),
                                                     _ptr(iters), _ptr(ep_flags), _ptr(ep_steps), _ptr(stream)))
 
+    GROUP_RECORD_FIELDS = ("group_row", "len", "x", "obst", "u", "winner", "best_key", "cand_key", "cand_status", "cand_iters", "cand_u0", "cand_X")
+
+    def group_record_set_dev(self, rows=0, max_steps=0, K=0, group_row=None, len=None, x=None, obst=None, u=None, winner=None, best_key=None, cand_key=None,
+                             cand_status=None, cand_iters=None, cand_u0=None, cand_X=None):
+        """attach the per-group record of multi-start episodes (include/mpc_gpu.h mpc_group_record_set_dev), device tensors used in place: group_row (groups,)
+        int32 = the row of each group or -1 (the non-negative entries distinct: the caller's to guarantee), len (rows,) int32 preset 0, x (rows, max_steps + 1, 5),
+        obst (rows, max_steps + 1, n_obst, 4), u (rows, max_steps, 2), winner (rows, max_steps) int32, best_key (rows, max_steps), cand_key (rows, max_steps, K),
+        cand_status / cand_iters (rows, max_steps, K) int32, cand_u0 (rows, max_steps, K, 2), cand_X (rows, max_steps, K, N + 1, 5) or None.  rows 0 (the default)
+        detaches.  group_record_shapes keeps the shapes of the arrays last attached."""
+        given = dict(group_row=group_row, len=len, x=x, obst=obst, u=u, winner=winner, best_key=best_key, cand_key=cand_key, cand_status=cand_status,
+                     cand_iters=cand_iters, cand_u0=cand_u0, cand_X=cand_X)
+        if int(rows) == 0:
+            _lib.check(_lib.lib().mpc_group_record_set_dev(self._h, 0, 0, 0, None))
+            return
+        r = _lib.GroupRecord(**{n: _ptr(a) for n, a in given.items()})
+        _lib.check(_lib.lib().mpc_group_record_set_dev(self._h, int(rows), int(max_steps), int(K), C.byref(r)))
+        self.group_record_shapes = {n: tuple(a.shape) for n, a in given.items() if hasattr(a, "shape")}
+
+    def group_record_dev(self, groups, K, phase, x, obst, X, key, status, iters, u0, out, stream=None):
+        """one launch of the attached group record (include/mpc_gpu.h mpc_group_record_dev): phase _lib.GROUP_RECORD_SOLVED behind the member solve (and the
+        rollout merit) and in front of mpc_group_step_dev, _lib.GROUP_RECORD_STEPPED behind it, all on one stream; `out` is that call's _lib.GroupStepOut"""
+        _lib.check(_lib.lib().mpc_group_record_dev(self._h, int(groups), int(K), int(phase), _ptr(x), _ptr(obst), _ptr(X), _ptr(key), _ptr(status), _ptr(iters),
+                                                   _ptr(u0), None if out is None else C.byref(out), _ptr(stream)))
+
     # ------------------------------------------------------------------ multi-GPU: all-gather of the costs, RCCL called by the library itself
     @staticmethod
     def comm_unique_id():

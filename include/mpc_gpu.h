@@ -565,7 +565,7 @@ int mpc_episode_trace_dev(mpc_handle *h, int slots, int phase, const int32_t *d_
  * First call of a sweep: slot_seed = -1, ep_flags = 1, member_flags = 1, cursor = {0, 0} -- every group is then filled by the same code.  Two launches; the
  * decision is handed over in words of the handle, so consecutive calls on one handle belong on one stream.
  * NOT OFFERED for groups, and refused rather than ignored: a handle with per-seed tables or a status log (mpc_set_refill_tables_dev), a ring
- * (mpc_episode_ring_dev) or a trace (mpc_episode_trace_set_dev) attached.
+ * (mpc_episode_ring_dev), a trace (mpc_episode_trace_set_dev) or a per-group record (mpc_group_record_set_dev) attached.
  * MPC_ERR_ARG (with a message, nothing launched): a null handle or a null pointer (every argument and every field of `a` is mandatory), K outside 1 .. 64,
  * groups < 1 or groups * K > max_batch, seed_count < 0, max_steps < 1, scenario outside 0 .. 2, per_seed outside {0, 1}.
  * a: device pointers only, copied by the call. */
@@ -584,6 +584,57 @@ typedef struct mpc_group_refill_arrays {
 int mpc_group_refill_dev(mpc_handle *h, int groups, int K, int scenario, unsigned seed_first, int seed_count, int max_steps, const double *box,
                          const double *d_start, const double *d_goal_rows, int per_seed, const double *d_offsets, const mpc_group_refill_arrays *a,
                          void *stream);
+/* MULTI-START EPISODES, THE PER-GROUP RECORD (mpc_group_record_set_dev, mpc_group_record_dev), opt-in and additive like the trace above: a handle on which
+ * neither was made launches exactly what it launched before.  What mpc_episode_trace keeps per seed -- simX, the obstacle trajectories, the applied inputs
+ * (robot_ocp_problem.py:42-49, 234-241, 270-276) -- and, per control step, what the group chose among: the K candidates' keys, status words, iterations,
+ * first inputs and (optionally) solved plans, with the winner and its key.  It is recorded ON THE DEVICE and only for the groups that ask for it, because
+ * mpc_group_step_dev selects the winner and overwrites the evidence in one launch (member 0 becomes the shifted winner, members 1 .. K - 1 are reseeded,
+ * d_x and d_obst move in place): the candidates of a step exist on the device only between the member solve and the group step.
+ * group_row[g] >= 0 names the row of group g in the arrays below, -1 = not recorded; the NON-NEGATIVE ENTRIES MUST BE DISTINCT AND BELOW rows -- that is
+ * the host's to guarantee, nothing on the device checks distinctness (an entry >= rows is not recorded).  Rows hold max_steps = T control steps.  The struct
+ * holds device pointers only and is copied by the call; the arrays are the caller's and are used in place.  mpc_group_record_set_dev(h, 0, 0, 0, NULL)
+ * (NULL, or rows == 0) detaches.
+ *
+ * PROTOCOL of one control step, everything on one stream, in this order:
+ *   1. the member solve   2. with the rollout merit as key: mpc_predict_dev, mpc_rollout_merit_dev   3. mpc_group_record_dev, MPC_GROUP_RECORD_SOLVED
+ *   4. mpc_group_step_dev WITH out->best_key and out->best_u0   5. mpc_group_record_dev, MPC_GROUP_RECORD_STEPPED
+ * with the d_x, d_obst, d_X, d_key, d_status, d_u0 and `out` of call 4 and the d_iters of the solve.  Two phases, because call 4 reads the candidates and
+ * overwrites them: what the group chose among is recorded in front of it (SOLVED), what it chose and where that left it behind it (STEPPED).
+ * For group g with r = group_row[g] >= 0:
+ *   SOLVED acts when bit 0 of out->ep_flags[g] is clear and t = out->ep_steps[g] < T: x[r][t] = d_x[g], obst[r][t] = d_obst[g] (the states the solve started
+ *     from), cand_key[r][t][k] = d_key[g K + k], cand_status, cand_iters, cand_u0 likewise, and with cand_X, cand_X[r][t][k] = d_X[g K + k]: the SOLVED
+ *     iterate, stage j at row j, before the group step shifts or reseeds it.  Nothing else is written.
+ *   STEPPED: with now = ep_steps[g] + (ep_flags[g] & 1) (the status log's "episode steps solved"), acts when now > len[r] and now <= T; the group then solved
+ *     at step t = len[r]: winner[r][t] = out->winner[g] (-1: no member was eligible), best_key[r][t] = out->best_key[g], u[r][t] = out->best_u0[g],
+ *     x[r][now] = d_x[g], obst[r][now] = d_obst[g], and len[r] = now, written last.  A group that was idle on entry to the step has now == len[r]: nothing.
+ * One wavefront per group, four groups per workgroup; every lane loads the group's words first, the lanes then stride over the doubles of a row (the
+ * K (N + 1) 5 doubles of a group's iterates are contiguous on both sides).  No atomics, no LDS, no spinning, no grid-wide synchronisation, loops bounded
+ * by ceil(K (N + 1) 5 / 64); every word written belongs to the group's own row; no thread reads a word that another wavefront of the same launch writes
+ * (len[r] is read and written by the group's own wavefront only); no input is written.
+ * While a record is attached, mpc_group_refill_dev is refused (MPC_ERR_ARG, "not offered for groups"): a sweep moves seeds between groups, and this record
+ * is keyed by group.
+ * MPC_ERR_ARG (with a message naming the field, nothing launched): a null handle, rows < 0, max_steps < 1, K outside 1 .. 64, a null mandatory field
+ * (cand_X alone is optional); phase outside {0, 1}, groups < 1 or groups * K > max_batch, K differing from the attached K, no record attached, a null pointer
+ * argument, a null out->winner / ep_flags / ep_steps, and out->best_key or out->best_u0 null in phase STEPPED. */
+typedef struct mpc_group_record {
+    const int32_t *group_row;  /* [groups]: row of group g in the arrays below, or -1 = not recorded */
+    int32_t *len;              /* [rows]  control steps recorded for the row (preset 0) */
+    double *x;                 /* [rows][max_steps + 1][5]          plant state; row t = the state the solve of step t started from */
+    double *obst;              /* [rows][max_steps + 1][n_obst][4]  obstacle states, likewise */
+    double *u;                 /* [rows][max_steps][2]              the input applied at the step: the winner's u0, (0, 0) without a winner */
+    int32_t *winner;           /* [rows][max_steps]                 the member selected, -1 = none was eligible */
+    double *best_key;          /* [rows][max_steps]                 its key (+inf without a winner) */
+    double *cand_key;          /* [rows][max_steps][K]              what the selection compared: the reported cost, or the rollout merit */
+    int32_t *cand_status;      /* [rows][max_steps][K]              the members' solve status */
+    int32_t *cand_iters;       /* [rows][max_steps][K]              their interior-point iterations */
+    double *cand_u0;           /* [rows][max_steps][K][2]           their first inputs */
+    double *cand_X;            /* [rows][max_steps][K][N + 1][5] or NULL: their solved iterates (NULL: the plans are not kept) */
+} mpc_group_record;
+int mpc_group_record_set_dev(mpc_handle *h, int rows, int max_steps, int K, const mpc_group_record *r);
+#define MPC_GROUP_RECORD_SOLVED 0
+#define MPC_GROUP_RECORD_STEPPED 1
+int mpc_group_record_dev(mpc_handle *h, int groups, int K, int phase, const double *d_x, const double *d_obst, const double *d_X, const double *d_key,
+                         const int32_t *d_status, const int32_t *d_iters, const double *d_u0, const mpc_group_step_out *out, void *stream);
 /* MULTI-GPU: one process per GPU, every rank solves its own contiguous slice of the scenarios (the reference's 13 000 closed
  * loops, experiments.py:20-36, are independent), and the only exchange is an all-gather of the per-instance costs -- RCCL over xGMI, called directly
  * from this library (librccl.so.1 is loaded on first use; there is no link-time dependency and no other transport).  A C host does:
