@@ -1201,9 +1201,17 @@ __device__ __forceinline__ void rowpar_factor_six_rows(int lane, int N, const LT
 }
 
 // SIX: the six-row form above (the instantiations that answer the five-row form with more scratch), else rows 0..4 only
-template <class LT, int TERMS = (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), bool SIX = false>
+// PACKED: seven LDS requests per stage instead of ten (dense blocks with a result region of their own and row 4 of W~_t staged a second time in row 5 of the
+// stage's H~aug block, which this form of the sweep never fetches: the caller's part, rti_split_kernel.hpp kSweepPacked).  Same words, same arithmetic:
+//   reads   row 4 of W~_t comes from [40 + j] of the H~aug block, one ds_read2_b64 with row 4 of H~aug_t ([32 + j]): 2 + 4 requests, none fetches a dead word;
+//   writes  ONE ds_write2_b64 (offsets 0, 8) through a per-lane address.  Every lane holds 1/d0, l, 1/d1, and lanes 8..15 of the row are idle mirrors of
+//           0..7, so three v_mov_b64_dpp with a bank mask put (1/d0, 1/d1) where lanes 8..11 and (l, 1/d1) where lanes 12..15 hold (K~[0][j], K~[1][j]);
+//           lane 8 stores to [6], [14], lane 12 to [7], [15] ([15] is a word nothing reads), lanes 0..5 to [j], [8 + j] as before, all others to dead words.
+//           The mirrors' P~ is garbage from then on; no DPP operand ever selects a lane above 7.
+template <class LT, int TERMS = (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), bool SIX = false, bool PACKED = false>
 __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool worker_row, double dt)
 {
+    static_assert(!PACKED || (!SIX && !LT::COMPACT && TERMS == kSweepTermsOutOfPlace), "the packed requests exist for the dense five-row sweep only");
     if constexpr (SIX) {
         rowpar_factor_six_rows<LT, TERMS>(lane, N, L, worker_row, dt);
         return;
@@ -1217,6 +1225,7 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
     // (two per-lane pointers, the rest are immediate offsets: K~[1][j] is 8 words behind K~[0][j], 1/d1 8 words behind 1/d0, and the
     // dead words an idle lane hits instead -- 48, 56 resp. 50, 51, 58 -- lie in rows 6, 7 of the block, consumed one stage earlier)
     double *kp = L.R + (store ? j : LT::DEADK), *fp = L.R + (store0 ? 6 : LT::DEADF);
+    if constexpr (PACKED) kp = L.R + (store ? j : (worker_row && l15 == 8 ? 6 : (worker_row && l15 == 12 ? 7 : LT::DEADK)));     // fp is unused
     const double *wp = L.W + j, *hp = L.H + j;
     // compact layout only: rows 2..4 of W~ (lane 5: the stage's b[2..4], stride WS; other lanes: the wavefront's constant table, stride 0)
     // and rows 6, 7 of H~aug through a per-lane base
@@ -1237,10 +1246,11 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
             Hc[6] = h6p[HS * t]; Hc[7] = h6p[HS * t + 1];
         } else {
 #pragma unroll
-            for (int k = 0; k < 5; k++) Wc[k] = wp[WS * t + k * 8];
+            for (int k = 0; k < (PACKED ? 4 : 5); k++) Wc[k] = wp[WS * t + k * 8];
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if (i != 5) Hc[i] = hp[HS * t + i * 8];               // row 5 of H~aug feeds the dead row of M~ only: not fetched
+            if constexpr (PACKED) Wc[4] = hp[HS * t + 40];            // ... its words hold row 4 of W~_t
         }
     };
     // first half of a stage: T = P~ W~ from the previous stage's P~ (the upper-left 6 x 6 of its M registers)
@@ -1441,8 +1451,18 @@ __device__ __forceinline__ void rowpar_factor(int lane, int N, const LT L, bool 
                   "=&v"(K0), "=&v"(K1), "=&v"(i00), "=&v"(l), "=&v"(i11), "=&v"(m66), "=&v"(m67), "=&v"(m77), "=&v"(e_), "=&v"(r_)
                 : "v"(Wc[0]), "v"(Wc[1]), "v"(Wc[2]), "v"(Wc[3]), "v"(Wc[4]), "v"(T[0]), "v"(T[1]), "v"(T[2]), "v"(T[3]), "v"(T[4]));
         }
-        kp[HS * t] = K0; kp[HS * t + 8] = K1;
-        fp[HS * t] = i00; fp[HS * t + 1] = l; fp[HS * t + 8] = i11;
+        if constexpr (PACKED) {
+            // the factors into the K~ registers of the mirror lanes (bank mask 0xc: lanes 8..15, 0x8: lanes 12..15; every lane holds the same factors, so the
+            // broadcast lane does not matter).  The sources were written five and more instructions before the end of the block above
+            asm volatile("v_mov_b64_dpp %0, %2 row_newbcast:0 row_mask:0xf bank_mask:0xc\n"
+                         "v_mov_b64_dpp %1, %4 row_newbcast:0 row_mask:0xf bank_mask:0xc\n"
+                         "v_mov_b64_dpp %0, %3 row_newbcast:0 row_mask:0xf bank_mask:0x8\n"
+                         : "+v"(K0), "+v"(K1) : "v"(i00), "v"(l), "v"(i11));
+            kp[HS * t] = K0; kp[HS * t + 8] = K1;
+        } else {
+            kp[HS * t] = K0; kp[HS * t + 8] = K1;
+            fp[HS * t] = i00; fp[HS * t + 1] = l; fp[HS * t + 8] = i11;
+        }
         // P~+ = M~[0..4][0..5] + M~[0..4][u] K~   (M~[i][6] = M~[6][i] is lane i's register 6)
         asm volatile(
             "s_nop 1\n"

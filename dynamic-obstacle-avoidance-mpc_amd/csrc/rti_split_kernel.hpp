@@ -289,6 +289,10 @@ __global__ MPC_SPLIT_BOUNDS(W2) void rti_split_kernel(const KParams p)
     constexpr bool kRow5Staged = kSixRows;
 #endif
     constexpr bool kStagingDealt = !W2 && !BLK2 && !NSQP;
+    // the factor sweep with packed LDS requests (rowpar_factor<.., PACKED>, rti_kernel.hpp): row 4 of W~_t is staged a second time in the words of the dead row 5
+    // of H~aug_t ([40..47] of the stage's block: zeros, 1 at [44], dt at [47], the affine entry at [45]), where it shares a request with row 4 of H~aug_t.
+    // Only where nothing stages or fetches row 5 and the results have a region of their own
+    constexpr bool kSweepPacked = kStagingDealt && !kRow5Staged;
     // Acl = A + B K and c of the affine sweep formed and stored by the parts, two columns each (LPS = 3, dense blocks)
     constexpr bool kAclDealt = LPS == 3 && !W2 && !BLK2 && !NSQP;
     // the plant step of the fused epilogue with one quadrature node's sincos per lane of a quad (dyn_step_quad above)
@@ -487,6 +491,10 @@ sqp_again: ;
         for (int k = 0; k < 5; k++)
 #pragma unroll
             for (int c = 0; c < 8; c++) w[k * 8 + c] = Wrow[k][c];
+        if constexpr (kSweepPacked) {       // row 4 of W~_t again, behind the zeros written above: its two constant non-zeros
+            double *hc = RL.H + LT::HS * i;
+            hc[44] = 1.0; hc[47] = dt;
+        }
     }
     }
 
@@ -733,10 +741,11 @@ sqp_again: ;
                         if (has_u) {
 #pragma unroll
                             for (int k = 0; k < 5; k++) RL.W[LT::WS * i + k * 8 + 5] = bbr[k];
+                            if constexpr (kSweepPacked) hc[45] = bbr[4];
                         }
                     }
                 }
-            } else {                        // part 0: ua, ual, x; part 1: y, v, om (psi's gradient and the affine column of W~_t)
+            } else {                      // part 0: ua, ual, x; part 1: y, v, om (psi's gradient and the affine column of W~_t)
                 const double Sxx = ssum[0] + from_right(ssum[0]), Sxy = ssum[2] + from_right(ssum[2]), Sgx = ssum[3] + from_right(ssum[3]);
                 const double Syy = from_left(ssum[1]) + ssum[1], Sgy = from_left(ssum[4]) + ssum[4];
                 if (act) {
@@ -747,6 +756,7 @@ sqp_again: ;
                         if (has_u) {
 #pragma unroll
                             for (int k = 0; k < 5; k++) RL.W[LT::WS * i + k * 8 + 5] = bbr[k];
+                            if constexpr (kSweepPacked) hc[45] = bbr[4];
                         }
                     } else {
                         const double gx = g_[2] + Sgx;
@@ -992,7 +1002,7 @@ sqp_again: ;
             // kernels (W2: they spill as they are, and a changed live range moves their scratch by 8..24 bytes either way) and one 512-register
             // instantiation, <10, 2> with REF and IPAR alone (160 -> 176 bytes); these keep the six-row form, instruction for instruction:
             // kSixRows, defined at the top of the kernel
-            rowpar_factor<LT, (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), kSixRows>(lane, N, RL, lane < 16, dt);
+            rowpar_factor<LT, (LT::COMPACT ? kSweepTermsCopied : kSweepTermsOutOfPlace), kSixRows, kSweepPacked>(lane, N, RL, lane < 16, dt);
         }
         wave_sync();
         if (has_u) {
